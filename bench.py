@@ -19,12 +19,15 @@ Workload at every N: BASELINE config 2 per GPU (256 x 16000 @16 kHz, n_fft 1024 
 is exactly 8 of these, weak scaling).  N > 1: one process per GPU; run plainly (`python bench.py --gpus N`) the script
 spawns the N ranks itself, under torchrun it joins the group it finds in the environment.
 
-Prints ONE JSON line (rank 0).  See DESIGN.md for the roofline accounting.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline; `--full` adds the side
+measurements (other issue modes, fed and cold inputs, the C-ABI kernels, the roofline, other configs, the CPU baseline).
+`--dump-outputs DIR` writes what the last timed step computed.  See DESIGN.md for the roofline accounting.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import socket
 import subprocess
@@ -69,6 +72,11 @@ def parse(argv=None):
                          "(dmel_mailbox_*, include/dmel.h): no launch of its own")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the launcher and the reporting path (gloo, no kernels): "
                     "what tests/test_bench_launcher_cpu.py runs")
+    ap.add_argument("--full", action="store_true", help="also take every side measurement: the repeated timed regions, the other issue modes, "
+                    "the fed / cold / world-1 RCCL / LambdAdam / bf16 steps, the C-ABI kernels and the roofline, other_configs and cpu_baseline "
+                    "(the last two unless --no-other-configs / --no-cpu-baseline).  Off: the run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed -- the log-mel "
+                    "output, lambd.grad and the updated lambd, float32 -- as DIR/<name>.npy (rank 0; the inputs are seeded: identical from run to run)")
     return ap.parse_args(argv)
 
 
@@ -324,12 +332,25 @@ def main():
         assert ranks_seen == world, f"the reducer summed {ranks_seen} ranks, the job has {world}"
     lam_param = layer.lambd
 
-    def module_step():
+    def module_step(keep=None):
         opt.zero_grad(set_to_none=True)
-        layer(x).backward(g)
+        y = layer(x)
+        y.backward(g)
+        if keep is not None:                                            # --dump-outputs: the step's output and gradient stay referenced
+            keep[:] = [y.detach(), lam_param.grad]                      # (a captured graph replays into these tensors; no autograd graph kept)
+        del y                                                           # (the update does not need it: freed before it)
         if sar is not None:                                             # data-parallel: the update needs the SUM over ranks
             sar.reduce(lam_param.grad, torch.cuda.current_stream(dev).cuda_stream)
         opt.step()
+
+    # one holder per issue mode: each captured graph has tensors of its own, and a replay writes only into those
+    keeps = {}
+
+    def step_of(mode):
+        if not args.dump_outputs:
+            return module_step
+        keeps[mode] = []
+        return lambda: module_step(keeps[mode])
 
     for _ in range(3):                                                  # tables, allocator, optimizer state, lambd tracking
         module_step()
@@ -365,7 +386,7 @@ def main():
     # (dmel_amd.GraphedStep: watches the lambd the kernels report and re-captures when the n_fft or its guards change);
     # "graph xk" unrolls k steps into one graph, which pays the ~8-14 us between two graph launches once per k steps
     from dmel_amd import GraphedStep
-    modes, graph_why = {"eager": (module_step, 1)}, ""
+    modes, graph_why = {"eager": (step_of("eager"), 1)}, ""
     MAX_AHEAD = 8
     if args.mode in ("auto", "graph"):
         # (a graph launch costs ~8-14 us of idle time on the device between two replays -- profiles/r03_step_timeline_c2.json --
@@ -374,7 +395,7 @@ def main():
         for k in ks:
             ok = True
             try:
-                gs = GraphedStep(module_step, [layer], max_ahead=MAX_AHEAD, steps_per_replay=k)
+                gs = GraphedStep(step_of("graph" if k == 1 else f"graph x{k}"), [layer], max_ahead=MAX_AHEAD, steps_per_replay=k)
                 for _ in range(MAX_AHEAD + 4):                          # past the first delayed look: the graph without guards is in place
                     gs()
                 torch.cuda.synchronize()
@@ -421,10 +442,20 @@ def main():
     # With the driver's small K such a region is one or two graph launches (well under a millisecond), so it is REPEATED: the
     # first region is the one the contract describes (W warm-up steps before it) and the one reported; REGIONS - 1 more of exactly
     # K steps follow for the side fields (median, min, max).
-    REGIONS = 11 if args.steps * 0.05 < 50.0 else 3                       # (long regions, > ~50 ms of steps: three)
-    regions = [run_mode(chosen, args.warmup, args.steps)]
-    for _ in range(REGIONS - 1):
-        regions.append(run_mode(chosen, 0, args.steps))
+    # (a plain run times the first region only, unless --report median asks for the median of them)
+    REGIONS = (11 if args.steps * 0.05 < 50.0 else 3) if (args.full or args.report == "median") else 1   # (long regions: three)
+    # The warm-up is whole replays of EVERY mode built (W rounded up to a common multiple of their steps per replay, W itself when
+    # every k divides it): the number of steps before the timed region, and so what its last step computes, does not depend on the
+    # mode the trial picked
+    kmul = math.lcm(*(k for _, k in modes.values()))
+    warm = -(-args.warmup // kmul) * kmul
+    regions = [run_mode(chosen, warm, args.steps)]
+    if args.report == "median":
+        regions += [run_mode(chosen, 0, args.steps) for _ in range(REGIONS - 1)]
+    if args.dump_outputs and rank == 0:                                 # the region(s) `value` is taken from are over
+        dump_outputs(args.dump_outputs, keeps[chosen], lam_param, torch)
+    if args.report == "first":
+        regions += [run_mode(chosen, 0, args.steps) for _ in range(REGIONS - 1)]
     # `value` / `ms_per_step` are the FIRST region again -- W untimed steps, then exactly K timed ones, as the contract
     # describes and as rounds 1-3 reported (round 4 reported the median region: a different statistic); --report median restores that.
     # Median, minimum and maximum of all regions are side fields either way.
@@ -448,10 +479,10 @@ def main():
     # (>= 200 steps) is reported next to it (`steps` / `value` stay what was asked for)
     k_chosen = modes[chosen][1]
     long_steps = max(200, 50 * k_chosen)
-    if args.steps < long_steps:
+    if args.full and args.steps < long_steps:
         module_step_info["long_run_ms_per_step"] = round(1e3 * run_mode(chosen, 8, long_steps) / long_steps, 5)
         module_step_info["long_run_steps"] = long_steps
-    if dist is None:
+    if args.full and dist is None:
         for m in modes:                                                 # the other ways of issuing the same step, for the record
             if m != chosen:
                 module_step_info[m.replace(" ", "_") + "_ms_per_step"] = round(1e3 * run_mode(m, 8, 80) / 80, 4)
@@ -463,7 +494,7 @@ def main():
     # total, so neither L2 nor the 256 MiB Infinity Cache holds the next one: the copy reads HBM).
     # cold_inputs: the chosen issue mode with every step of a replay reading a DIFFERENT resident batch of that pool (no copy):
     # the forward's first touch of x comes from HBM, not from the cache the previous step left.
-    if dist is None and not args.no_other_configs:
+    if args.full and dist is None and not args.no_other_configs:
         try:
             POOL = 24 if B * L * 4 * 24 > (256 << 20) else max(24, (300 << 20) // (B * L * 4) + 1)
             pool = [torch.from_numpy(synth.waveforms(B, L, seed=1000 + i)).to(dev) for i in range(POOL)]
@@ -586,7 +617,7 @@ def main():
     # ---- the N > 1 code path on this one GPU (what DMEL_BENCH_FORCE_DIST=1 runs): a world-1 RCCL group, the ncclAllReduce of
     # lambd.grad captured inside the step.  The driver's scaling run starts at N = 1 on the plain path; this figure shows that the
     # path the other N take costs the same step when there is nobody to talk to (within 3 %: DMEL_BENCH_STRICT=1 asserts it).
-    if dist is None and not args.no_other_configs:
+    if args.full and dist is None and not args.no_other_configs:
         try:
             import torch.distributed as tdist
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -643,7 +674,7 @@ def main():
 
     # ---- side figure, never `value`: the same step with the opt-in dmel_amd.LambdAdam (torch.optim.Adam's update of lambd as
     # one launch instead of torch's two), issued the way the headline was
-    if dist is None and not args.no_other_configs:
+    if args.full and dist is None and not args.no_other_configs:
         try:
             from dmel_amd import LambdAdam
             layer2 = MelSpectrogramLayer(torch.tensor(lam), n_mels=M, n_points=L, sample_rate=sr, hop_length=hop, device=str(dev),
@@ -711,7 +742,7 @@ def main():
 
     # ---- side figure, never `value`: BASELINE config 2 read literally ("bf16 activations / fp32 grad"): the log-mel output stored
     # as bf16 and its gradient read as bf16 (arithmetic, tangent and d lambd stay fp32), issued the way the headline was
-    if dist is None and not args.no_other_configs and not args.bf16_activations:
+    if args.full and dist is None and not args.no_other_configs and not args.bf16_activations:
         try:
             layer3 = MelSpectrogramLayer(torch.tensor(lam), n_mels=M, n_points=L, sample_rate=sr, hop_length=hop, device=str(dev),
                                          optimized=True, log=True, out_dtype=torch.bfloat16).to(dev)
@@ -743,99 +774,100 @@ def main():
         except Exception as e:                                          # noqa: BLE001
             module_step_info["with_bf16_activations"] = {"error": f"{type(e).__name__}: {e}"[:200]}
 
-    # ---- the bare kernels through the C ABI (round 1's headline): fused forward + dot, lambd by value, no autograd, no update -
-    plan = capi.Plan(L, hop, M, sr, max_batch=B)
-    out = torch.empty((B, 1, M, T), dtype=act, device=dev)
-    tan = torch.empty((B, 1, M, T), dtype=torch.float32, device=dev)
-    dl = torch.zeros(1, dtype=torch.float32, device=dev)
-    count = out.numel()
-    cur = torch.cuda.current_stream(dev)
+    if args.full:
+        # ---- the bare kernels through the C ABI (round 1's headline): fused forward + dot, lambd by value, no autograd, no update -
+        plan = capi.Plan(L, hop, M, sr, max_batch=B)
+        out = torch.empty((B, 1, M, T), dtype=act, device=dev)
+        tan = torch.empty((B, 1, M, T), dtype=torch.float32, device=dev)
+        dl = torch.zeros(1, dtype=torch.float32, device=dev)
+        count = out.numel()
+        cur = torch.cuda.current_stream(dev)
 
-    def step_kernels():
-        plan.forward(x.data_ptr(), B, lam, out.data_ptr(), tan.data_ptr(), True, 1e-10, cur.cuda_stream,
-                     extra_flags=capi.DMEL_FLAG_OUT_BF16 if args.bf16_activations else 0)
-        plan.backward(g.data_ptr(), tan.data_ptr(), count, dl.data_ptr(), cur.cuda_stream, grad_bf16=args.bf16_activations)
+        def step_kernels():
+            plan.forward(x.data_ptr(), B, lam, out.data_ptr(), tan.data_ptr(), True, 1e-10, cur.cuda_stream,
+                         extra_flags=capi.DMEL_FLAG_OUT_BF16 if args.bf16_activations else 0)
+            plan.backward(g.data_ptr(), tan.data_ptr(), count, dl.data_ptr(), cur.cuda_stream, grad_bf16=args.bf16_activations)
 
-    step_kernels()
-    torch.cuda.synchronize()
-    info = plan.info()
-    n_k = max(20, min(200, args.steps))
-    for _ in range(10):
         step_kernels()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n_k):
-        step_kernels()
-    torch.cuda.synchronize()
-    kern_ms = 1e3 * (time.perf_counter() - t0) / n_k
-
-    # ---- dominant kernel: average launch duration from HIP events on the launch stream ------------------------------------
-    # An event pair around ONE launch also times the launch packets around it (1.5-4 us, varying from box to box).  The
-    # duration is therefore taken from trains of launches between two HIP events on the launch stream: a train of whole steps
-    # (forward + dot, so the forward sees the cache state the dot kernel leaves) minus a train of the dot launches alone.
-    # This is what rocprofv3 reports as the dispatch duration plus the sub-microsecond gap between dependent dispatches.
-    def kernel_times(pl, xx, gg, oo, tt, dd, lam_v, n_elems, batch, bf16):
-        pl.set_profiling(True)
-        for _ in range(20):
-            pl.forward(xx.data_ptr(), batch, lam_v, oo.data_ptr(), tt.data_ptr(), True, 1e-10, cur.cuda_stream,
-                       extra_flags=capi.DMEL_FLAG_OUT_BF16 if bf16 else 0)
-            pl.backward(gg.data_ptr(), tt.data_ptr(), n_elems, dd.data_ptr(), cur.cuda_stream, grad_bf16=bf16)
         torch.cuda.synchronize()
-        prof = pl.get_profile()
-        pl.set_profiling(False)
-        pair = 1e3 * prof["fwd_ms"] / max(1, prof["fwd_launches"])
-        prep = 1e3 * prof["prep_ms"] / max(1, prof["prep_launches"])
-        bwd = 1e3 * prof["bwd_ms"] / max(1, prof["bwd_launches"])
-        ntrain = 100
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        ev[0].record(cur)
-        for _ in range(ntrain):
-            pl.forward(xx.data_ptr(), batch, lam_v, oo.data_ptr(), tt.data_ptr(), True, 1e-10, cur.cuda_stream,
-                       extra_flags=capi.DMEL_FLAG_OUT_BF16 if bf16 else 0)
-            pl.backward(gg.data_ptr(), tt.data_ptr(), n_elems, dd.data_ptr(), cur.cuda_stream, grad_bf16=bf16)
-        ev[1].record(cur)
-        ev[2].record(cur)
-        for _ in range(ntrain):
-            pl.backward(gg.data_ptr(), tt.data_ptr(), n_elems, dd.data_ptr(), cur.cuda_stream, grad_bf16=bf16)
-        ev[3].record(cur)
+        info = plan.info()
+        n_k = max(20, min(200, args.steps))
+        for _ in range(10):
+            step_kernels()
         torch.cuda.synchronize()
-        step_us = 1e3 * ev[0].elapsed_time(ev[1]) / ntrain
-        dot_us = 1e3 * ev[2].elapsed_time(ev[3]) / ntrain
-        fwd = step_us - dot_us - (prep if prep > 0 else 0.0)   # long clips: every forward also launched the partial-sum kernel
-        return fwd, pair, prep, bwd, step_us
+        t0 = time.perf_counter()
+        for _ in range(n_k):
+            step_kernels()
+        torch.cuda.synchronize()
+        kern_ms = 1e3 * (time.perf_counter() - t0) / n_k
 
-    fwd_us, fwd_pair_us, prep_us, bwd_us, _ = kernel_times(plan, x, g, out, tan, dl, lam, count, B, args.bf16_activations)
-    # algorithmic bytes of ONE launch of the fused forward kernel: read x once + write out and tangent once
-    alg_bytes = 4 * (B * L + B * M * T) + (2 if args.bf16_activations else 4) * B * M * T
-    achieved = alg_bytes / (fwd_us * 1e-6) / 1e9
-    # HBM-side bytes per launch come from rocprofv3 PMC passes (FETCH_SIZE / WRITE_SIZE cannot be read from inside the
-    # process); the committed measurement is quoted only if it was taken on THIS kernel source, otherwise traffic is null
-    quoted, traffic_src = profile_quotes()
-    traffic = quoted.get(args.config, {}).get("dmel_fwd_kernel_bytes_per_launch")
-    # the contraction stage on the matrix cores: executed fp32 MFMA flops of one launch = non-zero 4x16 filterbank blocks
-    # x 16-row tiles x 2048 flop per v_mfma_f32_16x16x4_f32, against the dense fp32 matrix peak
-    mfma_flops = mfma_flops_of(info, B, T)
-    dense_flops = 2.0 * 2.0 * B * T * (info["n_fft"] // 2 + 1) * M                      # 2 F M per frame, power and tangent rows
-    mfma = {"contraction": {0: "16x16x4 fp32 tiles over the non-zero 4x16 blocks", 1: "wave-local 4x4x1 fp32 (kTrainW)", 2: "dense bf16x3 (kTrainH)"}.get(info.get("contraction"), "none"),
-            "executed_tflops": round(mfma_flops / (fwd_us * 1e-6) / 1e12, 2), "peak_tflops": FP32_MFMA_PEAK_TFLOPS,
-            "frac": round(mfma_flops / (fwd_us * 1e-6) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
-            "executed_flops_per_launch": mfma_flops, "dense_equivalent_flops_per_launch": dense_flops,
-            "note": "banded HTK bank: only its non-zero band is multiplied (the dense product of SURVEY 8(d) would be dense_equivalent_flops); the whole kernel is the "
-                    "denominator and it is not MFMA-bound -- north_star's >= 50 % MFMA utilisation is unmet by design on this path (DESIGN 4.2)"}
-    roofline = roofline_of(info, B, T, alg_bytes, fwd_us, mfma_flops)
-    # what binds: the vector pipe's instruction stream -- SQ_ACTIVE_INST_VALU x 4 / (1024 SIMDs x kernel cycles) and the
-    # vector instructions per wave, from the same PMC session as `traffic` (same source-sha rule)
-    qc = quoted.get(args.config, {})
-    roofline.update({"valu_busy": qc.get("valu_busy"), "valu_insts_per_wave": qc.get("valu_insts_per_wave"), "kernel_cycles": qc.get("kernel_cycles"),
-                     "effective_clock_ghz": qc.get("effective_clock_ghz"), "valu_busy_note": qc.get("valu_busy_note")})
-    # SURVEY 8(d)'s strict forward bytes (read x + write Y: the tangent this launch also writes is the backward's operand there)
-    roofline["frac_section8d"] = round((4 * B * L + (2 if args.bf16_activations else 4) * B * M * T) / (fwd_us * 1e-6) / (HBM_PEAK_GBS * 1e9), 4)
-    roofline["frac_note"] = ("frac: x + out + tangent (every tensor this launch touches, once) over the launch's live-measured duration and 8 TB/s; "
-                             "frac_section8d: SURVEY 8(d)'s forward bytes only (x + out); hbm_frac_cold: the same launch on a batch no cache holds; "
-                             "steady_state_frac: per-launch bytes of config 4's batch on this GPU (8 rounds of resident workgroups: launch, first touch and "
-                             "drain paid once) over its un-profiled train time")
-    roofline.update({"traffic": traffic, "traffic_source": traffic_src, "avg_launch_us_single_event_pair": round(fwd_pair_us, 2),
-                     "other_kernels_us": {"prep": round(prep_us, 2), "backward_dot": round(bwd_us, 2)}, "mfma_stage": mfma})
+        # ---- dominant kernel: average launch duration from HIP events on the launch stream ------------------------------------
+        # An event pair around ONE launch also times the launch packets around it (1.5-4 us, varying from box to box).  The
+        # duration is therefore taken from trains of launches between two HIP events on the launch stream: a train of whole steps
+        # (forward + dot, so the forward sees the cache state the dot kernel leaves) minus a train of the dot launches alone.
+        # This is what rocprofv3 reports as the dispatch duration plus the sub-microsecond gap between dependent dispatches.
+        def kernel_times(pl, xx, gg, oo, tt, dd, lam_v, n_elems, batch, bf16):
+            pl.set_profiling(True)
+            for _ in range(20):
+                pl.forward(xx.data_ptr(), batch, lam_v, oo.data_ptr(), tt.data_ptr(), True, 1e-10, cur.cuda_stream,
+                           extra_flags=capi.DMEL_FLAG_OUT_BF16 if bf16 else 0)
+                pl.backward(gg.data_ptr(), tt.data_ptr(), n_elems, dd.data_ptr(), cur.cuda_stream, grad_bf16=bf16)
+            torch.cuda.synchronize()
+            prof = pl.get_profile()
+            pl.set_profiling(False)
+            pair = 1e3 * prof["fwd_ms"] / max(1, prof["fwd_launches"])
+            prep = 1e3 * prof["prep_ms"] / max(1, prof["prep_launches"])
+            bwd = 1e3 * prof["bwd_ms"] / max(1, prof["bwd_launches"])
+            ntrain = 100
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record(cur)
+            for _ in range(ntrain):
+                pl.forward(xx.data_ptr(), batch, lam_v, oo.data_ptr(), tt.data_ptr(), True, 1e-10, cur.cuda_stream,
+                           extra_flags=capi.DMEL_FLAG_OUT_BF16 if bf16 else 0)
+                pl.backward(gg.data_ptr(), tt.data_ptr(), n_elems, dd.data_ptr(), cur.cuda_stream, grad_bf16=bf16)
+            ev[1].record(cur)
+            ev[2].record(cur)
+            for _ in range(ntrain):
+                pl.backward(gg.data_ptr(), tt.data_ptr(), n_elems, dd.data_ptr(), cur.cuda_stream, grad_bf16=bf16)
+            ev[3].record(cur)
+            torch.cuda.synchronize()
+            step_us = 1e3 * ev[0].elapsed_time(ev[1]) / ntrain
+            dot_us = 1e3 * ev[2].elapsed_time(ev[3]) / ntrain
+            fwd = step_us - dot_us - (prep if prep > 0 else 0.0)   # long clips: every forward also launched the partial-sum kernel
+            return fwd, pair, prep, bwd, step_us
+
+        fwd_us, fwd_pair_us, prep_us, bwd_us, _ = kernel_times(plan, x, g, out, tan, dl, lam, count, B, args.bf16_activations)
+        # algorithmic bytes of ONE launch of the fused forward kernel: read x once + write out and tangent once
+        alg_bytes = 4 * (B * L + B * M * T) + (2 if args.bf16_activations else 4) * B * M * T
+        achieved = alg_bytes / (fwd_us * 1e-6) / 1e9
+        # HBM-side bytes per launch come from rocprofv3 PMC passes (FETCH_SIZE / WRITE_SIZE cannot be read from inside the
+        # process); the committed measurement is quoted only if it was taken on THIS kernel source, otherwise traffic is null
+        quoted, traffic_src = profile_quotes()
+        traffic = quoted.get(args.config, {}).get("dmel_fwd_kernel_bytes_per_launch")
+        # the contraction stage on the matrix cores: executed fp32 MFMA flops of one launch = non-zero 4x16 filterbank blocks
+        # x 16-row tiles x 2048 flop per v_mfma_f32_16x16x4_f32, against the dense fp32 matrix peak
+        mfma_flops = mfma_flops_of(info, B, T)
+        dense_flops = 2.0 * 2.0 * B * T * (info["n_fft"] // 2 + 1) * M                      # 2 F M per frame, power and tangent rows
+        mfma = {"contraction": {0: "16x16x4 fp32 tiles over the non-zero 4x16 blocks", 1: "wave-local 4x4x1 fp32 (kTrainW)", 2: "dense bf16x3 (kTrainH)"}.get(info.get("contraction"), "none"),
+                "executed_tflops": round(mfma_flops / (fwd_us * 1e-6) / 1e12, 2), "peak_tflops": FP32_MFMA_PEAK_TFLOPS,
+                "frac": round(mfma_flops / (fwd_us * 1e-6) / 1e12 / FP32_MFMA_PEAK_TFLOPS, 4),
+                "executed_flops_per_launch": mfma_flops, "dense_equivalent_flops_per_launch": dense_flops,
+                "note": "banded HTK bank: only its non-zero band is multiplied (the dense product of SURVEY 8(d) would be dense_equivalent_flops); the whole kernel is the "
+                        "denominator and it is not MFMA-bound -- north_star's >= 50 % MFMA utilisation is unmet by design on this path (DESIGN 4.2)"}
+        roofline = roofline_of(info, B, T, alg_bytes, fwd_us, mfma_flops)
+        # what binds: the vector pipe's instruction stream -- SQ_ACTIVE_INST_VALU x 4 / (1024 SIMDs x kernel cycles) and the
+        # vector instructions per wave, from the same PMC session as `traffic` (same source-sha rule)
+        qc = quoted.get(args.config, {})
+        roofline.update({"valu_busy": qc.get("valu_busy"), "valu_insts_per_wave": qc.get("valu_insts_per_wave"), "kernel_cycles": qc.get("kernel_cycles"),
+                         "effective_clock_ghz": qc.get("effective_clock_ghz"), "valu_busy_note": qc.get("valu_busy_note")})
+        # SURVEY 8(d)'s strict forward bytes (read x + write Y: the tangent this launch also writes is the backward's operand there)
+        roofline["frac_section8d"] = round((4 * B * L + (2 if args.bf16_activations else 4) * B * M * T) / (fwd_us * 1e-6) / (HBM_PEAK_GBS * 1e9), 4)
+        roofline["frac_note"] = ("frac: x + out + tangent (every tensor this launch touches, once) over the launch's live-measured duration and 8 TB/s; "
+                                 "frac_section8d: SURVEY 8(d)'s forward bytes only (x + out); hbm_frac_cold: the same launch on a batch no cache holds; "
+                                 "steady_state_frac: per-launch bytes of config 4's batch on this GPU (8 rounds of resident workgroups: launch, first touch and "
+                                 "drain paid once) over its un-profiled train time")
+        roofline.update({"traffic": traffic, "traffic_source": traffic_src, "avg_launch_us_single_event_pair": round(fwd_pair_us, 2),
+                         "other_kernels_us": {"prep": round(prep_us, 2), "backward_dot": round(bwd_us, 2)}, "mfma_stage": mfma})
 
     par = f"batch-sharded x{world}"
     if dist is not None:
@@ -847,7 +879,7 @@ def main():
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "activations": "bf16 (output and its gradient; arithmetic, tangent and d lambd fp32)" if args.bf16_activations else "f32",
-        "config": {"workload": f"BASELINE config 2 per GPU: batch {B} x {L} samples @ {sr} Hz, n_fft {info['n_fft']} "
+        "config": {"workload": f"BASELINE config 2 per GPU: batch {B} x {L} samples @ {sr} Hz, n_fft {capi.n_fft(lam)} "
                                f"(lambd {lam}), hop {hop}, n_mels {M}, log fused; step = nn.Module forward + backward to lambd.grad + Adam update of lambd"
                    if args.config == "c2" else f"{args.config}: batch {B} x {L} @ {sr}, lambd {lam}, hop {hop}, n_mels {M}",
                    "global_batch": B * world, "frames_per_step": frames_per_rank * world, "parallelism": par, "reducer": reducer,
@@ -858,13 +890,16 @@ def main():
                               f"HIP graph captured from the nn.Module step (dmel_amd.GraphedStep), {modes[chosen][1]} step(s) per replay") +
                              "; lambd stays on the device, no host synchronisation inside the timed region"},
         "module_step": module_step_info,
-        "c_abi_kernels": {"frames_per_s": round(frames_per_rank / (kern_ms * 1e-3), 1), "ms_per_step": round(kern_ms, 5),
-                          "note": "fused forward + dot through include/dmel.h, lambd by value, no autograd, no optimizer (round 1's headline)"},
-        "roofline": roofline,
-        "kernel_info": info,
     }
+    if args.full:
+        result.update({
+            "c_abi_kernels": {"frames_per_s": round(frames_per_rank / (kern_ms * 1e-3), 1), "ms_per_step": round(kern_ms, 5),
+                              "note": "fused forward + dot through include/dmel.h, lambd by value, no autograd, no optimizer (round 1's headline)"},
+            "roofline": roofline,
+            "kernel_info": info,
+        })
 
-    if rank == 0 and world == 1 and not args.no_other_configs and args.config == "c2":
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs and args.config == "c2":
         result["other_configs"] = other_configs(torch, capi, synth, dev, kernel_times)
         # `frac` prices the forward with its input resident in cache (the timed loop re-reads one batch); the same kernel on a batch no
         # cache holds (other_configs.c2_cold: a pool > 256 MiB) beside it
@@ -876,13 +911,27 @@ def main():
         if r4.get("roofline", {}).get("frac") is not None:
             roofline["steady_state_frac"] = r4["roofline"]["frac"]
             roofline["steady_state_ns_per_frame"] = r4.get("ns_per_frame_forward")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(cfg)
     if dist is not None:
         dist.destroy_process_group()
     if rank == 0:
         _flush_c_stdio()            # RCCL prints a version banner through C stdio: keep the JSON line the last one
         print(json.dumps(result), flush=True)
+
+
+def dump_outputs(out_dir, kept, lambd, torch):
+    """--dump-outputs: what the last timed step handed its caller -- the log-mel output, lambd.grad (summed over the ranks when N > 1)
+    and lambd after the update -- as float32 DIR/<name>.npy"""
+    import numpy as np
+    torch.cuda.synchronize()
+    y, grad = kept
+    arrays = {"logmel": y.detach().float().cpu().numpy(), "lambd_grad": grad.detach().float().reshape(1).cpu().numpy(),
+              "lambd": lambd.detach().float().reshape(1).cpu().numpy()}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20, "outputs above 64 MB: dump a fixed sample instead"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _flush_c_stdio():

@@ -11,10 +11,10 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 has() { [[ " $PARTS " == *" $1 "* ]]; }
-BENCH="python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-other-configs"
-EAGER="python3 bench.py --steps 30 --warmup 5 --mode eager --no-cpu-baseline --no-other-configs"
+BENCH="python3 bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-other-configs"
+EAGER="python3 bench.py --full --steps 30 --warmup 5 --mode eager --no-cpu-baseline --no-other-configs"
 if has bench; then
-  python3 bench.py --steps 20 --warmup 5 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+  python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
 fi
 if has trace; then
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- $BENCH > $OUT/kt.log 2>&1
@@ -44,7 +44,7 @@ if has shapes; then
   python3 tools/batch_sweep.py > $OUT/batch_sweep.json 2> $OUT/batch_sweep.err
 fi
 if has reducers; then
-  A="--steps 200 --warmup 20 --no-cpu-baseline --no-other-configs"
+  A="--full --steps 200 --warmup 20 --no-cpu-baseline --no-other-configs"
   DMEL_BENCH_FORCE_DIST=1 python3 bench.py $A --reducer rccl 2> /dev/null | grep "^{" > $OUT/bench_1rank_rccl.json
   DMEL_BENCH_FORCE_DIST=1 python3 bench.py $A --reducer mailbox 2> /dev/null | grep "^{" > $OUT/bench_1rank_mailbox.json
   python3 bench.py $A 2> /dev/null | grep "^{" > $OUT/bench_1rank_plain.json
@@ -52,7 +52,7 @@ if has reducers; then
     DMEL_BENCH_SHARE_GPU=1 python3 bench.py $A --gpus 2 --reducer mailbox 2> /dev/null | grep "^{" > $OUT/bench_2ranks_one_gpu_mailbox_$i.json
   done
   DMEL_BENCH_SHARE_GPU=1 python3 bench.py $A --gpus 4 --reducer mailbox 2> /dev/null | grep "^{" > $OUT/bench_4ranks_one_gpu_mailbox.json
-  DMEL_BENCH_SHARE_GPU=1 python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-other-configs --gpus 8 --reducer mailbox 2> /dev/null | grep "^{" > $OUT/bench_8ranks_one_gpu_mailbox.json
+  DMEL_BENCH_SHARE_GPU=1 python3 bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-other-configs --gpus 8 --reducer mailbox 2> /dev/null | grep "^{" > $OUT/bench_8ranks_one_gpu_mailbox.json
 fi
 if has extras; then
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_f2 -- python3 tools/time_backward_extras.py > $OUT/kt_f2.log 2>&1

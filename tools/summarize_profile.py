@@ -175,7 +175,7 @@ if sq:
     clk_c2 = {k: statistics.median(v) for k, v in counters("clk", FWD_C2).items()}
     hbm.setdefault("c2", {}).update(valu_figures(sq, avg_c2, clk_c2))
     d = sq_digest(sq)
-    d["_how"] = ("rocprofv3 --pmc, two separate passes (tools/profile_session.sh: sq1, sq2) around `bench.py --steps 30 --warmup 5 --mode eager`; medians over the "
+    d["_how"] = ("rocprofv3 --pmc, two separate passes (tools/profile_session.sh: sq1, sq2) around `bench.py --full --steps 30 --warmup 5 --mode eager`; medians over the "
                  "dispatches of dmel_fwd_kernel<1024, train>; SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles")
     dump(f"{tag}_pmc_sq_c2.json", d)
 # (the bench line is written at the end: the counters of the other shapes are filled into it too)
@@ -265,7 +265,7 @@ if two:
                                            "median_frames_per_s": statistics.median(vals), "min_frames_per_s": min(vals), "max_frames_per_s": max(vals),
                                            "spread_max_over_min": round(max(vals) / min(vals), 3), "issued": [d["module_step"]["issued"] for d in two]}
 if red:
-    red["_how"] = ("bench.py --steps 200 --warmup 20 --no-other-configs: plain; DMEL_BENCH_FORCE_DIST=1 (one rank, the reducer still runs: one-rank RCCL communicator / "
+    red["_how"] = ("bench.py --full --steps 200 --warmup 20 --no-other-configs: plain; DMEL_BENCH_FORCE_DIST=1 (one rank, the reducer still runs: one-rank RCCL communicator / "
                    "mailbox addressed to itself); DMEL_BENCH_SHARE_GPU=1 --gpus 2 / 4 --reducer mailbox (processes on ONE GPU exchanging through IPC-mapped inboxes: the "
                    "code path of N GPUs, not their speed); the two-rank run repeated five times in fresh processes; ms_per_step is the median of 11 regions")
     dump(f"{tag}_reducers.json", red)
