@@ -28,6 +28,7 @@ DMEL_FLAG_FULL_WINDOW = 2
 DMEL_FLAG_OUT_BF16 = 4
 DMEL_DTYPE_F32, DMEL_DTYPE_BF16 = 0, 1
 MAX_NFFT = 16384          # largest transform of the HIP kernels (kMaxNfft in csrc/dmel_kernels.h)
+MIN_FAST_NFFT = 32        # smallest transform of the fused kernel (kMinFastNfft); the multi-window layer serves MIN_FAST_NFFT ... MAX_NFFT
 
 # every symbol include/dmel.h declares (tests check the library exports exactly these)
 SYMBOLS = (
@@ -41,6 +42,8 @@ SYMBOLS = (
     "dmel_plan_retain", "dmel_plan_release", "dmel_plan_lambd_report", "dmel_decide_launch", "dmel_plan_force_launch",
     "dmel_adam_step", "dmel_mailbox_create", "dmel_mailbox_connect", "dmel_mailbox_destroy", "dmel_mailbox_allreduce", "dmel_mailbox_error",
     "dmel_mailbox_set_spin_limit", "dmel_mailbox_set_timeout_ms", "dmel_plan_is_live", "dmel_lambd_ring_size", "dmel_spectrogram_ex_dev", "dmel_forward_dev_fixed_spec", "dmel_backward_fb_saved", "dmel_backward_fb_saved_dl", "dmel_backward_x_dev", "dmel_backward_x_spec_dev", "dmel_plan_attach_mailbox", "dmel_backward_x_spec", "dmel_plan_attach_adam",
+    "dmel_scratch_bytes_multi", "dmel_forward_multi", "dmel_forward_multi_dev", "dmel_backward_multi", "dmel_plan_lambd_status_channel",
+    "dmel_decide_launch_multi",
 )
 TORCH_LIB_PATH = os.path.join(_PKG_DIR, "libdmel_torch.so")
 
@@ -175,6 +178,18 @@ def load():
     L.dmel_decide_launch.restype = C.c_int
     L.dmel_plan_force_launch.argtypes = [vp, C.c_int32, C.c_int32]
     L.dmel_plan_force_launch.restype = C.c_int
+    L.dmel_scratch_bytes_multi.argtypes = [vp, C.c_int32, C.c_int32]
+    L.dmel_scratch_bytes_multi.restype = C.c_size_t
+    L.dmel_forward_multi.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.c_double, vp, vp, vp, vp]
+    L.dmel_forward_multi.restype = C.c_int
+    L.dmel_forward_multi_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.c_double, vp, vp, vp, vp]
+    L.dmel_forward_multi_dev.restype = C.c_int
+    L.dmel_backward_multi.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
+    L.dmel_backward_multi.restype = C.c_int
+    L.dmel_plan_lambd_status_channel.argtypes = [vp, C.c_int32, C.POINTER(DmelLambdStatus)]
+    L.dmel_plan_lambd_status_channel.restype = C.c_int
+    L.dmel_decide_launch_multi.argtypes = [fp, fp, C.c_int32, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+    L.dmel_decide_launch_multi.restype = C.c_int
     L.dmel_mailbox_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(vp), C.c_char_p]
     L.dmel_mailbox_create.restype = C.c_int
     L.dmel_mailbox_connect.argtypes = [vp, C.c_char_p]
@@ -257,6 +272,16 @@ def decide_launch(lambd: float, rate: float, stale_forwards: float) -> tuple[int
     n, g = C.c_int32(0), C.c_int32(0)
     _check(load().dmel_decide_launch(C.c_float(float(lambd)), C.c_float(float(rate)), C.c_float(float(stale_forwards)), C.byref(n), C.byref(g)))
     return int(n.value), int(g.value)
+
+
+def decide_launch_multi(lambds, rates, stale_forwards: float) -> list[tuple[int, int]]:
+    """[(n_fft, channel mask), ...] in ascending n_fft: the union over channels of decide_launch (dmel_decide_launch_multi)."""
+    k = len(lambds)
+    lam = (C.c_float * max(k, 1))(*[float(v) for v in lambds])
+    rate = (C.c_float * max(k, 1))(*[float(v) for v in rates])
+    ns, masks, cnt = (C.c_int32 * (3 * max(k, 1)))(), (C.c_uint32 * (3 * max(k, 1)))(), C.c_int32(0)
+    _check(load().dmel_decide_launch_multi(lam, rate, k, C.c_float(float(stale_forwards)), ns, masks, C.byref(cnt)))
+    return [(int(ns[i]), int(masks[i])) for i in range(cnt.value)]
 
 
 def adam_step(param_ptr: int, grad_ptr: int, exp_avg_ptr: int, exp_avg_sq_ptr: int, step_ptr: int, ticket_ptr: int, n: int, lr: float,
@@ -421,6 +446,33 @@ class Plan:
 
     def lambd_reset(self):
         _check(load().dmel_plan_lambd_reset(self._h))
+
+    # -- the multi-window layer (dmel_forward_multi*, dmel_backward_multi) --
+    def scratch_bytes_multi(self, batch: int, channels: int) -> int:
+        return int(load().dmel_scratch_bytes_multi(self._h, int(batch), int(channels)))
+
+    def forward_multi(self, x_ptr: int, batch: int, lambd, out_ptr: int, tangent_ptr: int | None, log: bool, eps: float, stream: int,
+                      scratch_ptr: int, out_bf16: bool = False):
+        """lambd: the K host values (a sequence of floats)"""
+        lam = (C.c_float * len(lambd))(*[float(v) for v in lambd])
+        flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
+        _check(load().dmel_forward_multi(self._h, x_ptr, batch, lam, len(lambd), flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream))
+
+    def forward_multi_dev(self, x_ptr: int, batch: int, lambd_ptr: int, channels: int, out_ptr: int, tangent_ptr: int | None, log: bool,
+                          eps: float, stream: int, scratch_ptr: int, out_bf16: bool = False):
+        flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
+        _check(load().dmel_forward_multi_dev(self._h, x_ptr, batch, lambd_ptr, int(channels), flags, float(eps), out_ptr, tangent_ptr,
+                                             scratch_ptr, stream))
+
+    def backward_multi(self, grad_ptr: int, tangent_ptr: int, batch: int, channels: int, dlambd_ptr: int, stream: int, scratch_ptr: int,
+                       accumulate: bool = False, grad_bf16: bool = False):
+        _check(load().dmel_backward_multi(self._h, grad_ptr, DMEL_DTYPE_BF16 if grad_bf16 else DMEL_DTYPE_F32, tangent_ptr, int(batch),
+                                          int(channels), int(accumulate), dlambd_ptr, scratch_ptr, stream))
+
+    def lambd_status_channel(self, channel: int) -> dict:
+        st = DmelLambdStatus()
+        _check(load().dmel_plan_lambd_status_channel(self._h, int(channel), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
 
     def lambd_report(self, number: int):
         """lambd as read by execution ``number`` (None if its report has left the ring): timing-independent, see include/dmel.h."""

@@ -140,6 +140,17 @@ struct dmel_plan {
     int guard_mode = 0;            // 0 auto, 1 always both neighbours, 2 never, 3 auto also under capture
     int forced_n_fft = 0, forced_guards = 0;    // dmel_plan_force_launch: the caller chooses the launches (0: the library does)
     int last_guards = 0;           // bit 0: n_fft/2 launched, bit 1: 2 n_fft launched (most recent call)
+    // the multi-window layer (dmel_forward_multi_dev): one picture of lambd per channel, kept like the fields above, and its own words on
+    // the device side (made at the first multi-window call): channel c reports into multi_words + c kLamMultiStride and counts on multi_exec[c]
+    struct LamTrack {
+        unsigned issued = 0, seq_seen = 0, seq_floor = 0;
+        bool lam_known = false;
+        float lam_seen = 0.f, lam_rate = 0.f;
+        int n_obs = 0, last_guards = 0;
+    };
+    LamTrack multi[dmel::kMaxChannels];
+    unsigned long long* multi_words = nullptr;
+    unsigned* multi_exec = nullptr;
     int refs = 1;                  // dmel_plan_retain / dmel_plan_release (guarded by g_plans_mu)
     dmel_mailbox* mailbox = nullptr;    // dmel_plan_attach_mailbox: the backward's result is the sum over the mailbox's ranks
     dmel::AdamParams fused_adam{};      // dmel_plan_attach_adam: param != nullptr -> the backward's dot kernel applies this update
@@ -628,7 +639,13 @@ size_t scratch_bytes(const dmel_plan* pl, int batch)
     return kScratchPsum + ps;
 }
 
-Scratch carve(void* base)
+// the multi-window layer's scratch: the same layout with one window table per channel in front of the partial clip sums
+size_t scratch_bytes_multi(const dmel_plan* pl, int batch, int channels)
+{
+    return scratch_bytes(pl, batch) + (size_t)(channels - 1) * dmel::kMaxNfft * 8;
+}
+
+Scratch carve(void* base, int channels = 1)
 {
     unsigned char* b = static_cast<unsigned char*>(base);
     Scratch sc;
@@ -636,7 +653,7 @@ Scratch carve(void* base)
     sc.partials = reinterpret_cast<double*>(b + kScratchPartials);
     sc.counter = reinterpret_cast<unsigned*>(b + kScratchCounter);
     sc.win = reinterpret_cast<float2*>(b + kScratchWin);
-    sc.psum = reinterpret_cast<float*>(b + kScratchPsum);
+    sc.psum = reinterpret_cast<float*>(b + kScratchPsum + (size_t)(channels - 1) * dmel::kMaxNfft * 8);
     return sc;
 }
 
@@ -756,13 +773,18 @@ dmel_status big_tables_for(dmel_plan* pl, int N, dmel_plan::BigTab* out, const f
 // One launch (plus, when needed, the partial-sum / window-table kernel in front of it) of the forward for a given n_fft.
 // `lam` says where lambd comes from and whether the kernels check it against N (dmel_kernels.h); `sc` is the scratch of
 // this call.  Shared by every entry point; the plan mutex is held by the caller.
+// one launch of the multi-window layer: `count` channels (nibbles of `list`, with their lambd roles in `roles`) of an output with `ch_out` channels
+struct MultiLaunch { int ch_out = 0, count = 0; unsigned list = 0, roles = 0; float vals[dmel::kMaxChannels] = {}; };
+
 dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dmel::LamArgs lam, unsigned flags, double eps,
                              float* out, float* tangent, int mode, int remove_dc, const Scratch& sc, hipStream_t s, int win_half,
-                             bool* sums_done, float* spec_out = nullptr)
+                             bool* sums_done, float* spec_out = nullptr, const MultiLaunch* ml = nullptr)
 {
     if (N < 1) return fail(DMEL_ERR_UNSUPPORTED, "n_fft = " + std::to_string(N));
     const bool pow2 = (N & (N - 1)) == 0;
     const bool big = !pow2 || N > dmel::kMaxNfft;
+    if (ml && (big || N < dmel::kMinFastNfft || spec_out))
+        return fail(DMEL_ERR_UNSUPPORTED, "the multi-window layer runs n_fft 32 ... 16384 only (n_fft = " + std::to_string(N) + ")");
     if (spec_out && (big || N < dmel::kMinFastNfft || mode != dmel::kTrain))
         return fail(DMEL_ERR_UNSUPPORTED, "the spectrogram is saved by the fused training kernel only (power-of-two n_fft from 32 to 16384, tangent requested)");
     if (big && (N & 1)) return fail(DMEL_ERR_UNSUPPORTED, "n_fft = " + std::to_string(N) + " is odd");
@@ -868,7 +890,18 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
         pp.B = need_sums ? batch : 0; pp.L = pl->cfg.n_points; pp.nchunks = pl->nchunks; pp.chunk = pl->chunk;
         pp.N = need_window ? N : 0; pp.normalize = pl->cfg.normalize_window; pp.win_half = win_half; pp.center = center;
         pp.lam = lam; pp.lam.role = dmel::kLamQuiet;
-        DMEL_HIP(dmel::launch_prep(pp, s));
+        if (ml && need_window) {
+            // the multi-window layer: one window table per channel (win + c kMaxNfft, lambd[c]); the clip sums once for all of them
+            for (int i = 0; i < ml->count; ++i) {
+                const int c = (int)((ml->list >> (4 * i)) & 15u);
+                pp.lam = dmel::lam_for_channel(lam, c, 0, dmel::kLamQuiet, ml->vals);
+                pp.win2 = sc.win + (size_t)c * dmel::kMaxNfft;
+                pp.B = (need_sums && i == 0) ? batch : 0;
+                DMEL_HIP(dmel::launch_prep(pp, s));
+            }
+        } else {
+            DMEL_HIP(dmel::launch_prep(pp, s));
+        }
         if (need_sums) *sums_done = true;
     }
     const size_t m1 = prof_mark(pl, s);
@@ -928,7 +961,12 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     if (force_tpw == 1 || (force_tpw == 2 && dmel::forward_two_tiles(N, mode))) tpw = force_tpw;
     if (hsplit) tpw = 1;
     fp.wgs_per_clip = (fp.tiles_per_clip + tpw - 1) / tpw;
-    const long long grid = (long long)batch * fp.wgs_per_clip;
+    long long grid = (long long)batch * fp.wgs_per_clip;
+    if (ml) {
+        fp.ch_out = ml->ch_out; fp.ch_grid = (int)grid; fp.ch_list = ml->list; fp.ch_roles = ml->roles;
+        for (int c = 0; c < dmel::kMaxChannels; ++c) fp.ch_val[c] = ml->vals[c];
+        grid *= ml->count;
+    }
     if (grid > 0x7fffffffLL) return fail(DMEL_ERR_INVALID_ARGUMENT, "too many tiles for one launch");
     if (grid <= dmel::forward_resident_workgroups(N, mode)) fp.flags |= dmel::kFwdEdgeFirst;      // one round: see the kernel's prologue
     DMEL_HIP(dmel::launch_forward(N, mode, tpw, fp, (int)grid, s));
@@ -1013,7 +1051,8 @@ dmel_status run_forward(dmel_plan* pl, const float* x, int batch, float lambd, u
 }
 
 // ---- device-resident lambd ---------------------------------------------------------------------------------------------
-void lam_reset(dmel_plan* pl)
+// (templates: the plan's own picture and the multi-window layer's per-channel ones, dmel_plan::LamTrack, have the same fields)
+template <class P> void lam_reset(P* pl)
 {
     pl->lam_known = false; pl->n_obs = 0; pl->lam_rate = 0.f; pl->seq_seen = pl->issued; pl->seq_floor = pl->issued + 1;
 }
@@ -1036,18 +1075,17 @@ void decide_launch(float lambd, float rate, float stale, int* n_fft, int* guards
 // which n_fft the next dmel_forward_dev launches for and which neighbours it guards (bit 0: n_fft / 2, bit 1: 2 n_fft), from
 // the host's current picture: both neighbours while the drift per call is unknown, on request, and under a graph capture
 // nobody manages; otherwise only the ones within reach of a boundary before the host would notice
-void lam_decide(const dmel_plan* pl, bool capturing, int* n_fft, int* guards)
+template <class P> void lam_decide_track(const dmel_plan* pl, const P* tr, bool capturing, int* n_fft, int* guards)
 {
-    if (pl->forced_n_fft > 0) { *n_fft = pl->forced_n_fft; *guards = pl->forced_guards; return; }
-    const int N = dmel_n_fft(pl->lam_seen);
+    const int N = dmel_n_fft(tr->lam_seen);
     int g = 0;
     if (pl->guard_mode == 1 || (capturing && pl->guard_mode != 3 && pl->guard_mode != 2)) g = 3;
     else if (pl->guard_mode == 0 || pl->guard_mode == 3) {
-        if (pl->n_obs < 2) g = 3;
+        if (tr->n_obs < 2) g = 3;
         else {
-            const float stale = (float)(pl->issued - pl->seq_seen) + 2.0f + (capturing ? (float)pl->max_ahead : 0.f);
+            const float stale = (float)(tr->issued - tr->seq_seen) + 2.0f + (capturing ? (float)pl->max_ahead : 0.f);
             int n2 = 0;
-            decide_launch(pl->lam_seen, pl->lam_rate, stale, &n2, &g);
+            decide_launch(tr->lam_seen, tr->lam_rate, stale, &n2, &g);
         }
     }
     if (2 * N > dmel::kMaxBigFft) g &= ~2;
@@ -1055,15 +1093,21 @@ void lam_decide(const dmel_plan* pl, bool capturing, int* n_fft, int* guards)
     *n_fft = N; *guards = g;
 }
 
+void lam_decide(const dmel_plan* pl, bool capturing, int* n_fft, int* guards)
+{
+    if (pl->forced_n_fft > 0) { *n_fft = pl->forced_n_fft; *guards = pl->forced_guards; return; }
+    lam_decide_track(pl, pl, capturing, n_fft, guards);
+}
+
 // fold the kernels' latest report into the host's picture; returns false if nothing new.  The ring is scanned for the
 // highest execution number past the last one seen (and past the last reset): whichever forward executed last -- an eager
 // call or a replay of a captured one -- is what the picture follows.
-bool lam_observe(dmel_plan* pl)
+template <class P> bool lam_observe_ring(P* pl, const unsigned long long* ring)
 {
     bool any = false;
     unsigned best_seq = 0; unsigned best_bits = 0;
     for (unsigned i = 0; i < dmel::kLamRing; ++i) {
-        const unsigned long long w = __atomic_load_n(&pl->host_words[i], __ATOMIC_RELAXED);
+        const unsigned long long w = __atomic_load_n(&ring[i], __ATOMIC_RELAXED);
         const unsigned seq = (unsigned)(w >> 32);
         if (seq == 0 || (int)(seq - pl->seq_floor) < 0) continue;                       // empty, or older than the last reset
         if (pl->lam_known ? (int)(seq - pl->seq_seen) <= 0 : false) continue;           // not newer than what is known
@@ -1080,6 +1124,8 @@ bool lam_observe(dmel_plan* pl)
     if ((int)(best_seq - pl->issued) > 0) pl->issued = best_seq;                      // replays executed forwards the host never counted
     return true;
 }
+
+bool lam_observe(dmel_plan* pl) { return lam_observe_ring(pl, pl->host_words); }
 
 std::mutex g_plans_mu;             // guards dmel_plan::refs and g_live_plans
 std::unordered_set<const dmel_plan*> g_live_plans;     // every plan between dmel_plan_create and its last release (dmel_plan_is_live)
@@ -1279,6 +1325,8 @@ dmel_status dmel_plan_release(dmel_plan* plan)
     (void)hipFree(plan->big_win); (void)hipFree(plan->big_z);
     (void)hipFree(plan->exec_counter);
     if (plan->host_words) (void)hipHostFree(plan->host_words);
+    (void)hipFree(plan->multi_exec);
+    if (plan->multi_words) (void)hipHostFree(plan->multi_words);
     if (plan->xev) (void)hipEventDestroy(plan->xev);
     if (switched) (void)hipSetDevice(cur);
     (void)hipGetLastError();
@@ -1590,6 +1638,7 @@ dmel_status dmel_plan_lambd_reset(dmel_plan* plan)
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
     std::lock_guard<std::mutex> lock(plan->mu);
     lam_reset(plan);
+    for (auto& tr : plan->multi) lam_reset(&tr);
     return DMEL_OK;
 }
 
@@ -1619,6 +1668,266 @@ dmel_status dmel_decide_launch(float lambd, float rate, float stale_forwards, in
     int n = 0, g = 0;
     decide_launch(lambd, rate, stale_forwards, &n, &g);
     *n_fft = n; *guards = g;
+    return DMEL_OK;
+}
+
+// ---- the multi-window layer: K window widths as K output channels -----------------------------------------------------
+// The launch choice: each channel's dmel_decide_launch, united.  Entries in ascending n_fft, each with the mask of the channels that need it.
+dmel_status dmel_decide_launch_multi(const float* lambd, const float* rate, int32_t channels, float stale_forwards, int32_t* n_ffts,
+                                     uint32_t* channel_masks, int32_t* count)
+{
+    if (!lambd || !rate || !n_ffts || !channel_masks || !count || channels < 1 || channels > dmel::kMaxChannels || !(stale_forwards >= 0.f))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_decide_launch_multi: bad arguments");
+    std::map<int, uint32_t> u;
+    for (int c = 0; c < channels; ++c) {
+        if (!(rate[c] >= 0.f)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_decide_launch_multi: rate < 0");
+        int n = 0, g = 0;
+        decide_launch(lambd[c], rate[c], stale_forwards, &n, &g);
+        u[n] |= 1u << c;
+        if (g & 2) u[2 * n] |= 1u << c;
+        if (g & 1) u[n / 2] |= 1u << c;
+    }
+    int k = 0;
+    for (const auto& kv : u) { n_ffts[k] = kv.first; channel_masks[k] = kv.second; ++k; }
+    *count = k;
+    return DMEL_OK;
+}
+
+size_t dmel_scratch_bytes_multi(const dmel_plan* plan, int32_t batch, int32_t channels)
+{
+    if (!plan || batch < 0 || channels < 1 || channels > dmel::kMaxChannels) return 0;
+    return scratch_bytes_multi(plan, batch, channels);
+}
+
+namespace {
+
+dmel_status check_multi_args(dmel_plan* pl, const float* x, int batch, int channels, uint32_t flags, const void* out, void* scratch)
+{
+    dmel_status st = check_forward_args(pl, x, batch, out);
+    if (st != DMEL_OK) return st;
+    if (channels < 1 || channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, "channels must be 1 ... 8");
+    if (flags & ~(uint32_t)(DMEL_FLAG_LOG | DMEL_FLAG_OUT_BF16))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi: only DMEL_FLAG_LOG and DMEL_FLAG_OUT_BF16 are accepted");
+    if (batch > 0 && !scratch) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi: scratch (dmel_scratch_bytes_multi) is required");
+    if ((long long)batch * channels > 65534) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch x channels > 65534 (split the call)");
+    return DMEL_OK;
+}
+
+bool multi_in_range(int n) { return n >= dmel::kMinFastNfft && n <= dmel::kMaxFastNfft; }
+
+// one launch per distinct n_fft: `mask[i]` = the channels of launch i, in ascending channel order; a channel's lambd roles are first / last
+// among the launches that carry it
+dmel_status issue_multi(dmel_plan* pl, const float* x, int batch, int channels, const int* ns, const uint32_t* mask, int nl,
+                        const dmel::LamArgs& base, const float* vals, uint32_t flags, double eps, void* out, float* tangent,
+                        const Scratch& sc, hipStream_t s)
+{
+    int first[dmel::kMaxChannels], last[dmel::kMaxChannels];
+    for (int c = 0; c < channels; ++c) { first[c] = -1; last[c] = -1; }
+    for (int i = 0; i < nl; ++i)
+        for (int c = 0; c < channels; ++c)
+            if (mask[i] >> c & 1u) { if (first[c] < 0) first[c] = i; last[c] = i; }
+    bool sums_done = false;
+    dmel_plan_info primary_info = pl->info;
+    for (int i = 0; i < nl; ++i) {
+        MultiLaunch ml;
+        ml.ch_out = channels;
+        for (int c = 0; c < dmel::kMaxChannels; ++c) ml.vals[c] = c < channels && vals ? vals[c] : 0.f;
+        for (int c = 0; c < channels; ++c) {
+            if (!(mask[i] >> c & 1u)) continue;
+            const unsigned role = (first[c] == i ? dmel::kLamFirst : 0u) | (last[c] == i ? dmel::kLamLast : 0u);
+            ml.list |= (unsigned)c << (4 * ml.count);
+            ml.roles |= role << (4 * ml.count);
+            ++ml.count;
+        }
+        dmel::LamArgs lam = base;
+        lam.n_expected = base.n_expected ? ns[i] : 0;
+        if (i != 0) lam.dot_counter = nullptr;
+        const dmel_status st = launch_forward_n(pl, x, batch, ns[i], lam, flags, eps, static_cast<float*>(out), tangent,
+                                                tangent ? dmel::kTrain : dmel::kInfer, /*remove_dc=*/1, sc, s, 0, &sums_done, nullptr, &ml);
+        if (st != DMEL_OK) return st;
+        if (i == 0) primary_info = pl->info;
+    }
+    pl->info = primary_info;
+    return DMEL_OK;
+}
+
+}  // namespace
+
+dmel_status dmel_forward_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, uint32_t flags,
+                               double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, scratch);
+    if (st != DMEL_OK) return st;
+    if (!lambd_host) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_host is NULL");
+    std::map<int, uint32_t> u;
+    for (int c = 0; c < channels; ++c) {
+        if (!std::isfinite(lambd_host[c])) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd of channel " + std::to_string(c) + " is not finite");
+        const int n = dmel_n_fft(lambd_host[c]);
+        if (!multi_in_range(n))
+            return fail(DMEL_ERR_UNSUPPORTED, "channel " + std::to_string(c) + ": lambd = " + std::to_string(lambd_host[c]) + " gives n_fft " +
+                        std::to_string(n) + ", the multi-window layer serves 32 ... 16384");
+        u[n] |= 1u << c;
+    }
+    if (batch == 0) return DMEL_OK;
+    std::lock_guard<std::mutex> lock(plan->mu);
+    int ns[dmel::kMaxChannels]; uint32_t mask[dmel::kMaxChannels]; int nl = 0;
+    for (const auto& kv : u) { ns[nl] = kv.first; mask[nl] = kv.second; ++nl; }
+    const Scratch sc = carve(scratch, channels);
+    dmel::LamArgs base{};
+    base.n_expected = 0;                          // every n_fft was derived from these very values
+    base.dot_counter = sc.counter;
+    return issue_multi(plan, x, batch, channels, ns, mask, nl, base, lambd_host, flags, eps, out, tangent, sc,
+                       reinterpret_cast<hipStream_t>(stream));
+}
+
+dmel_status dmel_forward_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
+                                   double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, scratch);
+    if (st != DMEL_OK) return st;
+    if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
+    std::lock_guard<std::mutex> lock(plan->mu);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool capturing = is_capturing(s);
+    if (!plan->multi_words) {
+        if (capturing) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_dev: run the layer once eagerly before capturing it into a graph");
+        const size_t bytes = (size_t)dmel::kMaxChannels * dmel::kLamMultiStride * sizeof(unsigned long long);
+        DMEL_HIP(hipHostMalloc(reinterpret_cast<void**>(&plan->multi_words), bytes, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(plan->multi_words, 0, bytes);
+        DMEL_HIP(hipMalloc(reinterpret_cast<void**>(&plan->multi_exec), dmel::kMaxChannels * sizeof(unsigned)));
+        DMEL_HIP(hipMemset(plan->multi_exec, 0, dmel::kMaxChannels * sizeof(unsigned)));
+    }
+    auto ring = [&](int c) { return plan->multi_words + (size_t)c * dmel::kLamMultiStride; };
+    // a channel that no launch covered: NaN in that channel on the device; tell the caller once, naming it, and start that channel over
+    std::string msg;
+    for (int c = 0; c < channels; ++c) {
+        const unsigned long long err = __atomic_load_n(&ring(c)[dmel::kLamRing], __ATOMIC_RELAXED);
+        if (err == 0) continue;
+        float lam; const unsigned bits = (unsigned)err; std::memcpy(&lam, &bits, 4);
+        __atomic_store_n(&ring(c)[dmel::kLamRing], 0ull, __ATOMIC_RELAXED);
+        const float seen = plan->multi[c].lam_seen;
+        lam_reset(&plan->multi[c]);
+        if (msg.empty())
+            msg = "channel " + std::to_string(c) + ": lambd moved from " + std::to_string(seen) + " (n_fft " + std::to_string(dmel_n_fft(seen)) +
+                  ") to " + std::to_string(lam) + " (n_fft " + std::to_string(dmel_n_fft(lam)) + ") where no launch of the sync-free forward "
+                  "covered it (or out of the range 32 ... 16384): execution " + std::to_string((unsigned)(err >> 32)) + " of that channel "
+                  "produced NaN in it.  Its tracking has been reset";
+    }
+    if (!msg.empty()) return fail(DMEL_ERR_LAMBD_TRACKING, msg);
+    if (batch == 0) return DMEL_OK;
+    bool cold = false;
+    for (int c = 0; c < channels; ++c) { lam_observe_ring(&plan->multi[c], ring(c)); cold |= !plan->multi[c].lam_known; }
+    if (cold) {
+        // cold start (any channel): the one blocking read of the K values
+        if (capturing) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_dev: run the layer once eagerly before capturing it into a graph");
+        float lam[dmel::kMaxChannels];
+        DMEL_HIP(hipMemcpyAsync(lam, lambd_dev, channels * sizeof(float), hipMemcpyDeviceToHost, s));
+        DMEL_HIP(hipStreamSynchronize(s));
+        for (int c = 0; c < channels; ++c) {
+            if (!std::isfinite(lam[c])) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd of channel " + std::to_string(c) + " is not finite");
+            if (!multi_in_range(dmel_n_fft(lam[c])))
+                return fail(DMEL_ERR_UNSUPPORTED, "channel " + std::to_string(c) + ": lambd = " + std::to_string(lam[c]) + " gives n_fft " +
+                            std::to_string(dmel_n_fft(lam[c])) + ", the multi-window layer serves 32 ... 16384");
+        }
+        for (int c = 0; c < channels; ++c) {
+            auto& tr = plan->multi[c];
+            if (tr.lam_known) continue;
+            for (unsigned i = 0; i < dmel::kLamRing; ++i) {
+                const unsigned q = (unsigned)(__atomic_load_n(&ring(c)[i], __ATOMIC_RELAXED) >> 32);
+                if (q != 0 && (int)(q - tr.issued) > 0) tr.issued = q;
+            }
+            tr.lam_seen = lam[c]; tr.seq_seen = tr.issued; tr.lam_known = true; tr.n_obs = 0; tr.lam_rate = 0.f;
+        }
+    } else if (!capturing && plan->max_ahead > 0) {
+        // bounded run-ahead, per channel (all channels execute in the same forwards: in practice the first wait covers the others)
+        for (int c = 0; c < channels; ++c) {
+            auto& tr = plan->multi[c];
+            for (long spins = 0; tr.issued - tr.seq_seen > (unsigned)plan->max_ahead && spins < 200000000L; ++spins) {
+                if (!lam_observe_ring(&tr, ring(c)) && (spins & 1023) == 1023 && hipStreamQuery(s) == hipSuccess) { lam_observe_ring(&tr, ring(c)); break; }
+            }
+        }
+        (void)hipGetLastError();
+    }
+    // each channel's launches, clamped to the range the fused kernel serves (a channel whose lambd left it is then poisoned and reported)
+    std::map<int, uint32_t> u;
+    for (int c = 0; c < channels; ++c) {
+        int N = 0, g = 0;
+        lam_decide_track(plan, &plan->multi[c], capturing, &N, &g);
+        plan->multi[c].last_guards = g;
+        N = std::min(std::max(N, dmel::kMinFastNfft), dmel::kMaxFastNfft);
+        u[N] |= 1u << c;
+        if ((g & 2) && multi_in_range(2 * N)) u[2 * N] |= 1u << c;
+        if ((g & 1) && multi_in_range(N / 2)) u[N / 2] |= 1u << c;
+    }
+    int ns[3 * dmel::kMaxChannels]; uint32_t mask[3 * dmel::kMaxChannels]; int nl = 0;
+    for (const auto& kv : u) { ns[nl] = kv.first; mask[nl] = kv.second; ++nl; }
+    if (!capturing) {
+        // tables of the neighbouring sizes exist before they are needed (as dmel_forward_dev)
+        NfftTables* tb = nullptr;
+        for (int i = 0; i < nl; ++i)
+            for (int n : {ns[i], 2 * ns[i], ns[i] / 2})
+                if (multi_in_range(n) && (st = build_tables(plan, n, &tb)) != DMEL_OK) return st;
+    }
+    ++plan->calls;
+    if (!capturing) for (int c = 0; c < channels; ++c) ++plan->multi[c].issued;
+    const Scratch sc = carve(scratch, channels);
+    dmel::LamArgs base{};
+    base.dev = lambd_dev; base.n_expected = 1;    // (issue_multi: check against the n_fft of each launch)
+    base.exec_counter = plan->multi_exec; base.handled = sc.handled;
+    base.host_seen = plan->multi_words; base.host_error = plan->multi_words + dmel::kLamRing;
+    base.dot_counter = sc.counter;
+    return issue_multi(plan, x, batch, channels, ns, mask, nl, base, nullptr, flags, eps, out, tangent, sc, s);
+}
+
+dmel_status dmel_backward_multi(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int32_t batch, int32_t channels,
+                                int32_t accumulate, float* dlambd, void* scratch, void* stream)
+{
+    if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
+    if (batch < 0 || channels < 1 || channels > dmel::kMaxChannels || !dlambd || !scratch || (batch > 0 && (!grad_out || !tangent)))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: bad arguments");
+    if (grad_dtype != DMEL_DTYPE_F32 && grad_dtype != DMEL_DTYPE_BF16)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
+    if (plan->mailbox || plan->fused_adam.param)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: a plan with an attached mailbox or fused Adam serves the scalar layer only");
+    { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
+    const long long per_row = (long long)plan->cfg.n_mels * plan->T;
+    if ((long long)batch * per_row >= (1LL << 31)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: more than 2^31 elements per channel");
+    std::lock_guard<std::mutex> lock(plan->mu);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const Scratch sc = carve(scratch, channels);
+    // the ticket tree holds at most kDotMaxBlocks partials in all (its group counters live in the upper half of the partials array)
+    const int bpc = dmel::dot_multi_blocks_per_channel((long long)batch * per_row, channels);
+    if ((long long)bpc * channels > dmel::kDotMaxBlocks) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: too many partials");
+    const size_t m0 = prof_mark(plan, s);
+    DMEL_HIP(dmel::launch_dot_multi(grad_out, grad_dtype == DMEL_DTYPE_BF16, tangent, batch, channels, per_row, bpc, accumulate,
+                                    sc.partials, sc.counter, dlambd, s));
+    prof_span(plan, m0, prof_mark(plan, s), 2);
+    return DMEL_OK;
+}
+
+dmel_status dmel_plan_lambd_status_channel(dmel_plan* plan, int32_t channel, dmel_lambd_status* status)
+{
+    if (!plan || !status || channel < 0 || channel >= dmel::kMaxChannels)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_plan_lambd_status_channel: bad arguments");
+    std::lock_guard<std::mutex> lock(plan->mu);
+    dmel_lambd_status r{};
+    r.calls = plan->calls;
+    if (plan->multi_words) {
+        const unsigned long long* ring = plan->multi_words + (size_t)channel * dmel::kLamMultiStride;
+        auto& tr = plan->multi[channel];
+        lam_observe_ring(&tr, ring);
+        r.known = tr.lam_known ? 1 : 0;
+        r.lambd_seen = tr.lam_seen;
+        r.n_fft_seen = tr.lam_known ? dmel_n_fft(tr.lam_seen) : 0;
+        r.seq_issued = tr.issued; r.seq_seen = tr.seq_seen;
+        r.rate = tr.lam_rate; r.guards = tr.last_guards;
+        if (tr.lam_known) lam_decide_track(plan, &tr, false, &r.next_n_fft, &r.next_guards);
+        const unsigned long long err = __atomic_load_n(&ring[dmel::kLamRing], __ATOMIC_RELAXED);
+        r.error = err != 0 ? 1 : 0;
+        r.error_seq = (uint32_t)(err >> 32);
+        { const unsigned bits = (unsigned)err; std::memcpy(&r.error_lambd, &bits, 4); }
+    }
+    *status = r;
     return DMEL_OK;
 }
 

@@ -233,6 +233,90 @@ hipError_t launch_dot(const void* g, int g_bf16, const float* t, long long count
     return hipGetLastError();
 }
 
+// ---- the multi-window layer's backward: K gradients in one launch ------------------------------------------------------
+// dmel_dot_kernel segmented by channel: workgroup w works for channel w / bpc on the elements of that channel (rows (b, c) of the
+// (B, K, per_row) tensors, taken 4 at a time when rows are whole 16-byte pieces), publishes one fp64 partial, and goes through the same
+// two-level ticket tree; the last one adds each channel's partials in index order (the same bits every run) and writes all K results.
+static_assert(kDotMaxBlocks * sizeof(double) == 4096 && kMaxChannels <= kDotMaxBlocks,
+              "the multi dot writes at most kDotMaxBlocks partials: the ticket tree's group counters live in the upper half of the 1024");
+template <bool GBF16>
+__global__ void __launch_bounds__(kDotThreads) dmel_dot_multi_kernel(const void* __restrict__ g, const float* __restrict__ t, int K,
+                                                                  unsigned rows_b, unsigned per_row, int bpc, double* partials,
+                                                                  unsigned* counter, int accumulate, float* result)
+{
+    __shared__ double red4[kDotThreads / 16];
+    __shared__ int is_last;
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x / bpc, j = blockIdx.x - c * bpc;
+    const unsigned stride = (unsigned)bpc * kDotThreads;
+    double acc = 0.0;
+    const uintptr_t galign = GBF16 ? 7 : 15;
+    const bool vec = (per_row & 3u) == 0 && ((reinterpret_cast<uintptr_t>(g) & galign) | (reinterpret_cast<uintptr_t>(t) & 15)) == 0;
+    if (vec) {
+        const unsigned row4 = per_row / 4, n4 = rows_b * row4;          // this channel's float4 count (host: < 2^31)
+        const float4* t4 = reinterpret_cast<const float4*>(t);
+        for (unsigned i = (unsigned)j * kDotThreads + tid; i < n4; i += stride) {
+            const unsigned b = i / row4, r = i - b * row4;
+            const long long e = ((long long)b * K + c) * row4 + r;
+            const float4 a = load_g4<GBF16>(g, e), v = t4[e];
+            acc += ((double)a.x * (double)v.x + (double)a.y * (double)v.y) + ((double)a.z * (double)v.z + (double)a.w * (double)v.w);
+        }
+    } else {
+        const unsigned n1 = rows_b * per_row;
+        for (unsigned i = (unsigned)j * kDotThreads + tid; i < n1; i += stride) {
+            const unsigned b = i / per_row, r = i - b * per_row;
+            const long long e = ((long long)b * K + c) * per_row + r;
+            acc += (double)load_g1<GBF16>(g, e) * (double)t[e];
+        }
+    }
+    const double bsum = block_sum(acc, red4);
+    if (tid == 0) {
+        __hip_atomic_store(&partials[blockIdx.x], bsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // the ticket tree of dmel_dot_kernel, over the whole grid
+        const unsigned grp = blockIdx.x / kDotGroup, ngroups = (gridDim.x + kDotGroup - 1) / kDotGroup;
+        const unsigned gsize = grp + 1 < ngroups ? (unsigned)kDotGroup : gridDim.x - grp * kDotGroup;
+        unsigned* gc = dot_group_counters(counter) + 16 * grp;
+        bool last = false;
+        if (__hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1u) {
+            __hip_atomic_store(gc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ngroups - 1u;
+        }
+        is_last = last;
+    }
+    __syncthreads();
+    if (!is_last) return;
+    for (int k = 0; k < K; ++k) {
+        double sum = 0.0;
+        for (int q = tid; q < bpc; q += kDotThreads)
+            sum += __hip_atomic_load(&partials[k * bpc + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const double total = block_sum(sum, red4);
+        if (tid == 0) result[k] = accumulate ? (float)((double)result[k] + total) : (float)total;
+        __syncthreads();                                   // red4 is reused by the next channel
+    }
+    if (tid == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+int dot_multi_blocks_per_channel(long long per_channel, int channels)
+{
+    const long long want = (per_channel + 4095) / 4096;          // 4096 elements per workgroup and tensor, as dot_blocks_for
+    const long long cap = channels > 0 ? kDotMaxBlocks / channels : 1;
+    return (int)(want < 1 ? 1 : (want > cap ? cap : want));
+}
+
+hipError_t launch_dot_multi(const void* g, int g_bf16, const float* t, int batch, int channels, long long per_row, int blocks_per_channel,
+                            int accumulate, double* partials, unsigned* counter, float* result, hipStream_t s)
+{
+    if (channels < 1 || channels > kMaxChannels || blocks_per_channel < 1 || (long long)blocks_per_channel * channels > kDotMaxBlocks)
+        return hipErrorInvalidValue;
+    const dim3 gr(blocks_per_channel * channels), bl(kDotThreads);
+    if (g_bf16) hipLaunchKernelGGL((dmel_dot_multi_kernel<true>), gr, bl, 0, s, g, t, channels, (unsigned)batch, (unsigned)per_row,
+                                   blocks_per_channel, partials, counter, accumulate, result);
+    else hipLaunchKernelGGL((dmel_dot_multi_kernel<false>), gr, bl, 0, s, g, t, channels, (unsigned)batch, (unsigned)per_row,
+                            blocks_per_channel, partials, counter, accumulate, result);
+    return hipGetLastError();
+}
+
 // ---- filterbank tables from a device matrix -----------------------------------------------------------------
 // grid.x = runs (one (group, wave, run) entry of tile_ranges each) + the workgroups that copy / transpose the matrix (one
 // workgroup doing all of it took 64 us for 513 x 128 entries: the longest kernel of a trainable-filterbank step)

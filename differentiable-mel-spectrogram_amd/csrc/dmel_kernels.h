@@ -84,6 +84,24 @@ __host__ __device__ inline unsigned* dot_group_counters(unsigned* ticket_word)
     return reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(ticket_word) - 4096);
 }
 
+// The multi-window layer keeps one set of lambd words per channel: channel c of a launch uses lambd_dev + c, handled + 2 c, exec_counter + c
+// and the pinned words host_seen + c kLamMultiStride (its ring, then its sticky error word).  The scalar layer's words are untouched.
+constexpr int kMaxChannels = 8;
+constexpr unsigned kLamMultiStride = kLamRing + 1;
+__host__ __device__ inline LamArgs lam_for_channel(const LamArgs& base, int c, int slot, unsigned roles, const float* vals)
+{
+    LamArgs la = base;
+    if (la.dev) la.dev += c;
+    la.val = vals[c];
+    la.role = (roles >> (4 * slot)) & 15u;
+    if (la.handled) la.handled += 2 * c;
+    if (la.exec_counter) la.exec_counter += c;
+    if (la.host_seen) la.host_seen += (size_t)c * kLamMultiStride;
+    if (la.host_error) la.host_error += (size_t)c * kLamMultiStride;
+    if (slot != 0) la.dot_counter = nullptr;        // the dot scratch is armed once per forward, by the first channel of its first launch
+    return la;
+}
+
 enum LamAction : int { kLamRun = 0, kLamSkip = 1, kLamPoison = 2 };
 struct LamState {
     float lam, a, denom;              // lambd, |lambd| (models.py:38), |lambd| + 1e-15 (time_frequency.py:24)
@@ -384,6 +402,13 @@ struct FwdParams {
     // quads split over 2 or 4 blocks of a phase (one-frame waves): after the phase's loop the pieces' partial sums are added across lanes
     const int* wl_merge;        // [phase * 64 + lane]: partner lane of round 1 | of round 2 << 8 | this lane receives in round 1 << 16 | in round 2 << 17
     int wl_mg[kWlMaxPhases];    // per phase: bit 0 / 1 = round 1 / 2 has anything to do
+    // The multi-window layer (dmel_forward_multi*): one launch serves ch_n channels of one n_fft.  ch_out = 0 is the scalar layer's launch and
+    // leaves everything above as it is; otherwise out / tangent are (B, ch_out, M, T), workgroup w of the grid (after the XCD relabelling) works
+    // for channel slot w / ch_grid, and that slot's channel c = nibble `slot` of ch_list reads lambd[c] (lam.dev + c, or ch_val[c] by value),
+    // the window table win2 + c kMaxNfft, and its own words of the lambd bookkeeping (LamMulti below; role = nibble `slot` of ch_roles).
+    int ch_out, ch_grid;
+    unsigned ch_list, ch_roles;
+    float ch_val[kMaxChannels];
 };
 
 struct PrepParams {
@@ -571,6 +596,12 @@ struct MailboxArgs {
 hipError_t launch_dot(const void* g, int g_bf16, const float* t, long long count, int accumulate, double* partials,
                       unsigned* counter, int max_partials, float* result, hipStream_t s, const MailboxArgs* mb = nullptr,
                       const AdamParams* fused = nullptr);
+// the multi-window layer's backward: dlambd[c] = sum over clips of grad_out[:, c] . tangent[:, c] for the `channels` channels of (batch, channels,
+// `per_row`) tensors, in ONE launch of `blocks_per_channel` x channels workgroups (<= kDotMaxBlocks: the ticket tree's layout) -- same scratch,
+// same fp64 accumulation, fixed-order combine of each channel's partials by the workgroup that draws the last ticket
+int dot_multi_blocks_per_channel(long long per_channel, int channels);
+hipError_t launch_dot_multi(const void* g, int g_bf16, const float* t, int batch, int channels, long long per_row, int blocks_per_channel,
+                            int accumulate, double* partials, unsigned* counter, float* result, hipStream_t s);
 // the same exchange for a value that is already in memory (one wave): buf[0] = sum over ranks of buf[0]
 hipError_t launch_mailbox_allreduce(float* buf, const MailboxArgs& mb, hipStream_t s);
 

@@ -169,6 +169,8 @@ class GraphedStep:
     def __init__(self, step_fn, layers, max_ahead: int = 8, steps_per_replay: int = 1, warmup: int = 0, backend=None, decide=None,
                  inputs=None, zero_copy=None):
         self.step_fn, self.layers = step_fn, list(layers)
+        if any(getattr(lay, "MAX_CHANNELS", 0) for lay in self.layers):
+            raise ValueError("GraphedStep does not drive a MultiWindowMelSpectrogram: capture its step with torch.cuda.graph")
         self.inputs = None if inputs is None else list(inputs)
         if zero_copy is not None and self.inputs is None:
             raise ValueError("GraphedStep(zero_copy=...) needs inputs=[...]")

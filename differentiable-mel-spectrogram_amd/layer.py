@@ -491,6 +491,158 @@ class MelSpectrogramLayer(nn.Module):
                 f"normalize_window={self.normalize_window}, log={self.log}")
 
 
+class _MultiFunction(torch.autograd.Function):
+    """forward: dmel_forward_multi(_dev) -- one launch per distinct n_fft for all K channels, carrying d out / d lambd[k] per channel;
+    backward: dmel_backward_multi (K dot products in one launch)."""
+
+    @staticmethod
+    def forward(ctx, x, lambd, plan, lam_host, log, eps, out_dtype, want_tangent):
+        B, K = x.shape[0], lambd.shape[0]
+        out = torch.empty((B, K, plan.n_mels, plan.n_time), dtype=out_dtype, device=x.device)
+        tangent = torch.empty(out.shape, dtype=torch.float32, device=x.device) if want_tangent else None
+        scratch = torch.empty((plan.scratch_bytes_multi(B, K),), dtype=torch.uint8, device=x.device)
+        bf16 = out_dtype == torch.bfloat16
+        with _on_device(x.device):
+            if lam_host is not None:
+                plan.forward_multi(x.data_ptr(), B, lam_host, out.data_ptr(), tangent.data_ptr() if want_tangent else None, log, eps,
+                                   _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
+            else:
+                lam = lambd.detach()
+                if lam.dtype != torch.float32 or not lam.is_contiguous():
+                    lam = lam.to(torch.float32).contiguous()
+                plan.forward_multi_dev(x.data_ptr(), B, lam.data_ptr(), K, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
+                                       log, eps, _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
+        ctx.plan, ctx.K, ctx.lambd_dtype = plan, K, lambd.dtype
+        if want_tangent:
+            ctx.save_for_backward(tangent, scratch)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        tangent, scratch = ctx.saved_tensors
+        bf16 = grad_out.dtype == torch.bfloat16
+        g = grad_out
+        if not bf16 and g.dtype != torch.float32:
+            g = g.to(torch.float32)
+        if not g.is_contiguous():
+            g = g.contiguous()
+        dl = torch.empty((ctx.K,), dtype=torch.float32, device=g.device)
+        with _on_device(g.device):
+            ctx.plan.backward_multi(g.data_ptr(), tangent.data_ptr(), g.shape[0], ctx.K, dl.data_ptr(), _stream_ptr(g.device),
+                                    scratch.data_ptr(), grad_bf16=bf16)
+        if ctx.lambd_dtype != torch.float32:
+            dl = dl.to(ctx.lambd_dtype)
+        return None, dl, None, None, None, None, None, None
+
+
+class MultiWindowMelSpectrogram(nn.Module):
+    """K trainable window widths at once, returned as K output channels.
+
+        MultiWindowMelSpectrogram(init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1,
+                                  normalize_window=False, *, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False)
+        forward(x: (B, n_points)) -> (B, K, n_mels, n_points // hop_length + 1)
+
+    ``y[:, k:k+1]`` is what ``MelSpectrogramLayer(lambd[k], ..., optimized=True)`` returns for the same ``x``, bit for bit (each
+    channel has its own n_fft = next_pow2(int(6 |lambd[k]|)) and HTK bank), and ``lambd.grad[k]`` is that channel's gradient.  The
+    parameter ``lambd`` has shape ``(K,)``, 1 <= K <= 8; every channel's n_fft must lie in 32 ... 16384 (about 2.84 <= |lambd| <= 2730).
+    A channel whose lambd leaves that range (or moves further than the sync-free forward covers) is NaN and the next forward raises.
+    The kernels launch once per distinct n_fft for all the channels that need it; the backward is one launch for all K gradients.
+    Not supported: a waveform gradient (x.requires_grad), ``SlotInput``, ``GraphedStep`` and ``LambdAdam(fused_into_backward=...)``."""
+
+    MAX_CHANNELS = 8
+
+    def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
+                 log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False):
+        super().__init__()
+        lam = init_lambd.detach().clone() if torch.is_tensor(init_lambd) else torch.tensor([float(v) for v in init_lambd])
+        if lam.dim() != 1:
+            raise ValueError(f"init_lambd must be 1-D (K values), got shape {tuple(lam.shape)}")
+        K = lam.shape[0]
+        if not 1 <= K <= self.MAX_CHANNELS:
+            raise ValueError(f"the multi-window layer has 1 ... {self.MAX_CHANNELS} channels, got K = {K}")
+        lam = lam.to(torch.float32)
+        for k, v in enumerate(lam.tolist()):
+            n = capi.n_fft(v) if v == v else 0
+            if not capi.MIN_FAST_NFFT <= n <= capi.MAX_NFFT:
+                raise ValueError(f"init_lambd[{k}] = {v} gives n_fft {n}: the multi-window layer serves n_fft {capi.MIN_FAST_NFFT} ... "
+                                 f"{capi.MAX_NFFT} (about 2.84 <= |lambd| <= 2730)")
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("out_dtype must be torch.float32 or torch.bfloat16")
+        self.lambd = nn.Parameter(lam)
+        self.n_mels, self.n_points, self.sample_rate, self.hop_length = n_mels, n_points, sample_rate, hop_length
+        self.f_min = f_min
+        self.f_max = f_max if f_max is not None else sample_rate // 2
+        self.normalize_window = normalize_window
+        self.n_time = n_points // hop_length + 1
+        self.log, self.eps, self.out_dtype, self.lambd_sync = bool(log), float(eps), out_dtype, bool(lambd_sync)
+        self._plans = {}
+
+    @property
+    def channels(self) -> int:
+        return self.lambd.shape[0]
+
+    def _plan_for(self, dev: torch.device) -> capi.Plan:
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        plan = self._plans.get(idx)
+        if plan is None:
+            with torch.cuda.device(idx):
+                plan = capi.Plan(self.n_points, self.hop_length, self.n_mels, self.sample_rate, float(self.f_min), float(self.f_max),
+                                 bool(self.normalize_window))
+            if getattr(self, "_tracking", None) is not None:
+                plan.set_tracking(*self._tracking)
+            self._plans[idx] = plan
+        return plan
+
+    def resync(self):
+        """Forget what the sync-free path knows about every channel's lambd (after writing it through ``.data``)."""
+        for plan in self._plans.values():
+            plan.lambd_reset()
+
+    def lambd_status(self, channel: int = 0, device=None) -> dict:
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return self._plan_for(dev).lambd_status_channel(channel)
+
+    def set_tracking(self, max_ahead: int = 8, guard_mode: int = 0):
+        self._tracking = (int(max_ahead), int(guard_mode))
+        for plan in self._plans.values():
+            plan.set_tracking(*self._tracking)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self.resync()
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_plans"] = {}
+        return state
+
+    def forward(self, x):
+        if isinstance(x, SlotInput):
+            raise RuntimeError("MultiWindowMelSpectrogram does not take a SlotInput")
+        if x.dim() != 2:
+            raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
+        if x.shape[1] != self.n_points:
+            raise RuntimeError(f"input has {x.shape[1]} points, the layer was built for n_points={self.n_points}")
+        if not x.is_cuda:
+            raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
+        if x.requires_grad:
+            raise RuntimeError("MultiWindowMelSpectrogram has no waveform gradient: pass x.detach()")
+        if self.lambd.device != x.device:
+            raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
+        xf = x if x.dtype == torch.float32 else _to_f32(x)
+        if not xf.is_contiguous():
+            xf = xf.contiguous()
+        lam_host = [float(v) for v in self.lambd.detach().cpu().tolist()] if self.lambd_sync else None
+        # the tangent only when a gradient will be asked for (as torch.ops.dmel.mel_spectrogram: grad mode and lambd.requires_grad);
+        # otherwise the inference kernels, which pair two frames per FFT
+        want = torch.is_grad_enabled() and self.lambd.requires_grad
+        return _MultiFunction.apply(xf, self.lambd, self._plan_for(x.device), lam_host, self.log, self.eps, self.out_dtype, want)
+
+    def extra_repr(self):
+        return (f"channels={self.channels}, n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
+                f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}")
+
+
 class _DspecFunction(torch.autograd.Function):
     """forward: dmel_spectrogram_ex (carries d spec / d lambd); backward: dmel_backward and, for a waveform that requires grad,
     dmel_backward_x_spec."""

@@ -427,6 +427,32 @@ dmel_status dmel_adam_step(float* param, const float* grad, float* exp_avg, floa
 dmel_status dmel_plan_attach_adam(dmel_plan* plan, float* param, float* exp_avg, float* exp_avg_sq, float* step,
                                   double lr, double beta1, double beta2, double eps, double weight_decay, int32_t maximize);
 
+/* ---- the multi-window layer: K trainable window widths as K output channels (dmel_amd.MultiWindowMelSpectrogram) ------------------
+ * Channel k of (batch, K, n_mels, n_time) is what dmel_forward* computes for lambd[k], bit for bit; 1 <= K <= 8, every channel's n_fft in
+ * 32 ... 16384 (the fused kernel).  One launch per DISTINCT n_fft covers all the channels that need it.  out and tangent are (batch, K, M, T);
+ * flags: DMEL_FLAG_LOG, DMEL_FLAG_OUT_BF16.  scratch: dmel_scratch_bytes_multi(plan, batch, K) bytes owned by the caller for the forward and
+ * the dmel_backward_multi that consumes its tangent (required).
+ * dmel_forward_multi takes the K values from the host (channels grouped by n_fft; a value outside the range: DMEL_ERR_UNSUPPORTED).
+ * dmel_forward_multi_dev reads them on the device as dmel_forward_dev does, with one host picture per channel: each channel's launches and
+ * guards are chosen as dmel_forward_dev would, and their union is issued.  A channel that no launch covered is NaN (the others are
+ * untouched) and the next call returns DMEL_ERR_LAMBD_TRACKING naming it.  The first call (and the first after a reset) reads the K values
+ * once, blocking.  dmel_plan_lambd_reset forgets every channel. */
+size_t dmel_scratch_bytes_multi(const dmel_plan* plan, int32_t batch, int32_t channels);
+dmel_status dmel_forward_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, uint32_t flags,
+                               double eps, void* out, float* tangent, void* scratch, void* stream);
+dmel_status dmel_forward_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
+                                   double eps, void* out, float* tangent, void* scratch, void* stream);
+/* dlambd[k] (= or += with accumulate) sum over clips of grad_out[:, k] . tangent[:, k], K values in ONE deterministic launch (fp64
+ * accumulation, fixed-order combine; bf16 gradients widened exactly).  Not with an attached mailbox or fused Adam. */
+dmel_status dmel_backward_multi(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int32_t batch, int32_t channels,
+                                int32_t accumulate, float* dlambd, void* scratch, void* stream);
+/* dmel_plan_lambd_status for channel `channel` of the multi-window forward (calls counts every dmel_forward_dev* / _multi_dev call) */
+dmel_status dmel_plan_lambd_status_channel(dmel_plan* plan, int32_t channel, dmel_lambd_status* status);
+/* The launch choice of dmel_forward_multi_dev as a pure function: the union over channels of dmel_decide_launch(lambd[k], rate[k],
+ * stale_forwards), `count` entries in ascending n_fft, channel_masks[i] bit k = channel k needs n_ffts[i].  Arrays of 3 x channels entries. */
+dmel_status dmel_decide_launch_multi(const float* lambd, const float* rate, int32_t channels, float stale_forwards, int32_t* n_ffts,
+                                     uint32_t* channel_masks, int32_t* count);
+
 /* Introspection for tests / benchmarks */
 typedef struct dmel_plan_info {
     int32_t n_fft;             /* of the most recent forward                                */
