@@ -43,7 +43,7 @@ SYMBOLS = (
     "dmel_adam_step", "dmel_mailbox_create", "dmel_mailbox_connect", "dmel_mailbox_destroy", "dmel_mailbox_allreduce", "dmel_mailbox_error",
     "dmel_mailbox_set_spin_limit", "dmel_mailbox_set_timeout_ms", "dmel_plan_is_live", "dmel_lambd_ring_size", "dmel_spectrogram_ex_dev", "dmel_forward_dev_fixed_spec", "dmel_backward_fb_saved", "dmel_backward_fb_saved_dl", "dmel_backward_x_dev", "dmel_backward_x_spec_dev", "dmel_plan_attach_mailbox", "dmel_backward_x_spec", "dmel_plan_attach_adam",
     "dmel_scratch_bytes_multi", "dmel_forward_multi", "dmel_forward_multi_dev", "dmel_backward_multi", "dmel_plan_lambd_status_channel",
-    "dmel_decide_launch_multi",
+    "dmel_decide_launch_multi", "dmel_backward_x_multi", "dmel_backward_x_multi_dev", "dmel_plan_last_multi_launch",
 )
 TORCH_LIB_PATH = os.path.join(_PKG_DIR, "libdmel_torch.so")
 
@@ -190,6 +190,13 @@ def load():
     L.dmel_plan_lambd_status_channel.restype = C.c_int
     L.dmel_decide_launch_multi.argtypes = [fp, fp, C.c_int32, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
     L.dmel_decide_launch_multi.restype = C.c_int
+    L.dmel_backward_x_multi.argtypes = [vp, vp, C.c_int32, fp, C.c_int32, C.c_uint32, vp, vp, vp, vp]
+    L.dmel_backward_x_multi.restype = C.c_int
+    L.dmel_backward_x_multi_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32, C.c_uint32,
+                                            vp, vp, vp, vp]
+    L.dmel_backward_x_multi_dev.restype = C.c_int
+    L.dmel_plan_last_multi_launch.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+    L.dmel_plan_last_multi_launch.restype = C.c_int
     L.dmel_mailbox_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(vp), C.c_char_p]
     L.dmel_mailbox_create.restype = C.c_int
     L.dmel_mailbox_connect.argtypes = [vp, C.c_char_p]
@@ -468,6 +475,29 @@ class Plan:
                        accumulate: bool = False, grad_bf16: bool = False):
         _check(load().dmel_backward_multi(self._h, grad_ptr, DMEL_DTYPE_BF16 if grad_bf16 else DMEL_DTYPE_F32, tangent_ptr, int(batch),
                                           int(channels), int(accumulate), dlambd_ptr, scratch_ptr, stream))
+
+    def backward_x_multi(self, x_ptr: int, batch: int, lambd, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int, log: bool, stream: int):
+        """dmel_backward_x_multi: grad_x = sum over channels (ascending) of the scalar layer's waveform gradient; lambd: the K host values;
+        grad_ptr / out_ptr: (B, K, M, T) fp32"""
+        lam = (C.c_float * len(lambd))(*[float(v) for v in lambd])
+        _check(load().dmel_backward_x_multi(self._h, x_ptr, batch, lam, len(lambd), DMEL_FLAG_LOG if log else 0, grad_ptr, out_ptr, grad_x_ptr,
+                                            stream))
+
+    def backward_x_multi_dev(self, x_ptr: int, batch: int, lambd_ptr: int, channels: int, launches, grad_ptr: int, out_ptr: int | None,
+                             grad_x_ptr: int, log: bool, stream: int):
+        """dmel_backward_x_multi_dev: lambd read on the device; launches: [(n_fft, channel mask), ...] of the forward whose gradient
+        this is (last_multi_launch() right after it)"""
+        k = max(len(launches), 1)
+        ns = (C.c_int32 * k)(*[int(n) for n, _ in launches])
+        masks = (C.c_uint32 * k)(*[int(m) for _, m in launches])
+        _check(load().dmel_backward_x_multi_dev(self._h, x_ptr, batch, lambd_ptr, int(channels), ns, masks, len(launches),
+                                                DMEL_FLAG_LOG if log else 0, grad_ptr, out_ptr, grad_x_ptr, stream))
+
+    def last_multi_launch(self) -> list[tuple[int, int]]:
+        """[(n_fft, channel mask), ...] in ascending n_fft: what the most recent forward_multi(_dev) on this plan issued (host bookkeeping)"""
+        ns, masks, cnt = (C.c_int32 * 24)(), (C.c_uint32 * 24)(), C.c_int32(0)
+        _check(load().dmel_plan_last_multi_launch(self._h, ns, masks, C.byref(cnt)))
+        return [(int(ns[i]), int(masks[i])) for i in range(cnt.value)]
 
     def lambd_status_channel(self, channel: int) -> dict:
         st = DmelLambdStatus()

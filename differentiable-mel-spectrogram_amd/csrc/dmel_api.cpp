@@ -151,6 +151,13 @@ struct dmel_plan {
     LamTrack multi[dmel::kMaxChannels];
     unsigned long long* multi_words = nullptr;
     unsigned* multi_exec = nullptr;
+    // what the most recent dmel_forward_multi(_dev) issued (dmel_plan_last_multi_launch), and the workspace of dmel_backward_x_multi(_dev)
+    // (per channel: segments or frame rows + fp64 sums; window tables; staged grad_out / out rows of the LDS path), grown on demand
+    int last_multi_ns[3 * dmel::kMaxChannels] = {};
+    uint32_t last_multi_mask[3 * dmel::kMaxChannels] = {};
+    int last_multi_nl = 0;
+    float* xmw = nullptr;
+    size_t xmw_floats = 0;
     int refs = 1;                  // dmel_plan_retain / dmel_plan_release (guarded by g_plans_mu)
     dmel_mailbox* mailbox = nullptr;    // dmel_plan_attach_mailbox: the backward's result is the sum over the mailbox's ranks
     dmel::AdamParams fused_adam{};      // dmel_plan_attach_adam: param != nullptr -> the backward's dot kernel applies this update
@@ -1318,7 +1325,7 @@ dmel_status dmel_plan_release(dmel_plan* plan)
     plan->mailbox = nullptr;
     for (auto& kv : plan->tables) kv.second.release();
     for (hipEvent_t e : plan->ev_pool) (void)hipEventDestroy(e);
-    (void)hipFree(plan->own_scratch); (void)hipFree(plan->fbw);
+    (void)hipFree(plan->own_scratch); (void)hipFree(plan->fbw); (void)hipFree(plan->xmw);
     for (auto& kv : plan->big_tabs) { (void)hipFree(kv.second.chirp); (void)hipFree(kv.second.hbr); }
     for (auto& kv : plan->big_tw) (void)hipFree(kv.second);
     for (auto& kv : plan->big_wodd) (void)hipFree(kv.second);
@@ -1723,6 +1730,8 @@ dmel_status issue_multi(dmel_plan* pl, const float* x, int batch, int channels, 
 {
     int first[dmel::kMaxChannels], last[dmel::kMaxChannels];
     for (int c = 0; c < channels; ++c) { first[c] = -1; last[c] = -1; }
+    pl->last_multi_nl = nl;                       // (host code: runs under capture too)
+    for (int i = 0; i < nl; ++i) { pl->last_multi_ns[i] = ns[i]; pl->last_multi_mask[i] = mask[i]; }
     for (int i = 0; i < nl; ++i)
         for (int c = 0; c < channels; ++c)
             if (mask[i] >> c & 1u) { if (first[c] < 0) first[c] = i; last[c] = i; }
@@ -2344,6 +2353,238 @@ dmel_status dmel_backward_x_spec_dev(dmel_plan* plan, const float* x, int32_t ba
     if (!x || !grad_spec || !grad_x) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_spec_dev: x / grad_spec / grad_x is NULL");
     if (!(flags & DMEL_SPEC_REMOVE_DC)) return fail(DMEL_ERR_UNSUPPORTED, "dmel_backward_x_spec_dev: only the DC-removed spectrogram (models.py:187) is differentiated");
     return backward_x_impl(plan, x, batch, 0.f, n_fft, (flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0, 1, false, grad_spec, nullptr, grad_x, stream, lambd_dev);
+}
+
+}  // extern "C"
+
+namespace {
+// the multi-window layer's gradient w.r.t. the waveform: at n_fft N every channel takes the path backward_x_impl takes for the scalar layer
+// (win_half = 0): the wave-FFT kernel when the shape fits, its own window and clip mean when own_prep; the LDS frames kernel otherwise
+struct XgShape { bool wave, own_prep; int tiles, span, ts; size_t frame_floats, csum_doubles; };
+
+dmel_status xgrad_multi_shape(const dmel_plan* pl, int N, int batch, XgShape* r)
+{
+    int fpt = 0;
+    r->wave = dmel::xgrad_wave_shape(N, pl->cfg.n_mels, N / 2 + 1, &fpt) && std::getenv("DMEL_XGRAD_LDS") == nullptr;
+    r->own_prep = r->wave && !pl->cfg.normalize_window && pl->cfg.n_points <= 32768 && std::getenv("DMEL_XGRAD_PREP") == nullptr;
+    r->tiles = r->wave ? (pl->T + fpt - 1) / fpt : 0;
+    const long long span = r->wave ? (long long)(fpt - 1) * pl->cfg.hop_length + N : 0;
+    if (span > 0x3fffffffLL) return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: hop_length too large");
+    r->span = (int)span;
+    r->ts = r->wave ? fpt * pl->cfg.hop_length : 0;
+    const size_t rows = r->wave ? (size_t)r->tiles : (size_t)pl->T, row_len = r->wave ? (size_t)span : (size_t)N;
+    r->frame_floats = ((size_t)batch * rows * row_len + 63) / 64 * 64;
+    r->csum_doubles = (size_t)batch * rows;
+    return DMEL_OK;
+}
+
+dmel_status check_x_multi_args(dmel_plan* pl, const float* x, int batch, int channels, uint32_t flags, const float* grad_out,
+                               const float* out, float* grad_x, const char* who)
+{
+    if (!pl) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
+    if (batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": batch < 0");
+    if (channels < 1 || channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": channels must be 1 ... 8");
+    if (flags & ~(uint32_t)DMEL_FLAG_LOG) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": only DMEL_FLAG_LOG is accepted");
+    if (batch > 0 && (!x || !grad_out || !grad_x)) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": x / grad_out / grad_x is NULL");
+    if (batch > 0 && (flags & DMEL_FLAG_LOG) && !out) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": DMEL_FLAG_LOG needs the saved log output");
+    if ((long long)batch * channels > 65534) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch x channels > 65534 (split the call)");
+    return DMEL_OK;
+}
+
+// ns / mask / nl: the launch list (checked by the caller); lam_host (K values) or lam_dev (K device words) -- exactly one of them
+dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, const float* lam_host, const float* lam_dev, int channels,
+                                  const int* ns, const uint32_t* mask, int nl, bool log, const float* grad_out, const float* out,
+                                  float* grad_x, void* stream)
+{
+    { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
+    std::lock_guard<std::mutex> lock(plan->mu);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool capturing = is_capturing(s);
+    // each channel's candidates (its launches, ascending) and their shapes
+    int ncand[dmel::kMaxChannels] = {}, cand[dmel::kMaxChannels][dmel::kXgMaxCand] = {};
+    for (int i = 0; i < nl; ++i)
+        for (int c = 0; c < channels; ++c)
+            if (mask[i] >> c & 1u) cand[c][ncand[c]++] = ns[i];
+    std::map<int, XgShape> shape;
+    dmel_status st = DMEL_OK;
+    for (int i = 0; i < nl; ++i)
+        for (int n : {ns[i], ns[i] / 2, 2 * ns[i]}) {
+            if (!multi_in_range(n) || shape.count(n) || (capturing && n != ns[i])) continue;      // eager: the neighbours too (see below)
+            XgShape sh;
+            if ((st = xgrad_multi_shape(plan, n, batch, &sh)) != DMEL_OK) return st;
+            shape[n] = sh;
+        }
+    NfftTables* tb[3 * dmel::kMaxChannels] = {};
+    for (int i = 0; i < nl; ++i) if ((st = build_tables(plan, ns[i], &tb[i])) != DMEL_OK) return st;
+    if ((st = order_after_last_stream(plan, s)) != DMEL_OK) return st;
+    Scratch sc;
+    if ((st = ensure_own_scratch(plan, batch, s, &sc)) != DMEL_OK) return st;
+    // workspace: per channel a region of the largest shape it may take -- eagerly also at n_fft / 2 and 2 n_fft of every launch, so that a
+    // capture after the lambd of a channel crossed a boundary needs no growth -- then the window tables (channel x candidate) of the
+    // launches that do not evaluate their own window, then grad_out / out of one channel staged as (B, M, T) for the LDS frames kernel
+    size_t fr_stride = 0, cs_floats = 0;
+    bool any_prep = false, any_lds = false;
+    for (const auto& kv : shape) {
+        fr_stride = std::max(fr_stride, kv.second.frame_floats);
+        cs_floats = std::max(cs_floats, (2 * kv.second.csum_doubles + 63) / 64 * 64);
+        any_prep |= !kv.second.own_prep;
+        any_lds |= !kv.second.wave;
+    }
+    const size_t region = fr_stride + cs_floats;
+    const size_t bmt = (size_t)batch * plan->cfg.n_mels * plan->T;
+    const size_t win_floats = any_prep ? (size_t)channels * dmel::kXgMaxCand * dmel::kMaxNfft * 2 : 0;
+    const size_t stage_floats = any_lds ? (2 * bmt + 63) / 64 * 64 : 0;
+    const size_t need = (size_t)channels * region + win_floats + stage_floats + 16;
+    if (need > plan->xmw_floats) {
+        if (capturing) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi: the workspace must grow but the stream is capturing: run one call eagerly first");
+        DMEL_HIP(hipStreamSynchronize(s));
+        (void)hipFree(plan->xmw); plan->xmw = nullptr; plan->xmw_floats = 0;
+        DMEL_HIP(hipMalloc(&plan->xmw, need * sizeof(float)));
+        plan->xmw_floats = need;
+    }
+    float* frames[dmel::kMaxChannels] = {};
+    double* csum[dmel::kMaxChannels] = {};
+    for (int c = 0; c < channels; ++c) {
+        frames[c] = plan->xmw + (size_t)c * region;
+        csum[c] = reinterpret_cast<double*>(frames[c] + fr_stride);           // 256-byte aligned: region and fr_stride are multiples of 64
+    }
+    float2* wins = any_prep ? reinterpret_cast<float2*>(plan->xmw + (size_t)channels * region) : nullptr;
+    float* stage = any_lds ? plan->xmw + (size_t)channels * region + win_floats : nullptr;
+    auto table = [&](int c, int n) -> float2* {
+        for (int j = 0; j < ncand[c]; ++j) if (cand[c][j] == n) return wins ? wins + (size_t)(c * dmel::kXgMaxCand + j) * dmel::kMaxNfft : nullptr;
+        return nullptr;
+    };
+    const int L = plan->cfg.n_points, M = plan->cfg.n_mels, T = plan->T;
+    const size_t m0 = prof_mark(plan, s);
+    for (int i = 0; i < nl; ++i) {
+        const int N = ns[i];
+        const XgShape& sh = shape[N];
+        // window tables (and the partial clip sums) where the kernel does not evaluate its own: one dmel_prep_kernel per channel
+        if (!sh.own_prep)
+            for (int c = 0; c < channels; ++c) {
+                if (!(mask[i] >> c & 1u)) continue;
+                dmel::PrepParams pp{};
+                pp.x = x; pp.psum = sc.psum; pp.win2 = table(c, N);
+                pp.B = batch; pp.L = L; pp.nchunks = plan->nchunks; pp.chunk = plan->chunk;
+                pp.N = N; pp.normalize = plan->cfg.normalize_window; pp.win_half = 0; pp.center = (float)N / 2.0f;
+                pp.lam.dev = lam_dev ? lam_dev + c : nullptr; pp.lam.val = lam_dev ? 0.f : lam_host[c]; pp.lam.role = dmel::kLamQuiet;
+                DMEL_HIP(dmel::launch_prep(pp, s));
+            }
+        dmel::XgradParams xp{};
+        xp.own_prep = sh.own_prep ? 1 : 0; xp.lam_dev = lam_dev; xp.check_nfft = lam_dev ? 1 : 0;
+        xp.x = x; xp.psum = sc.psum; xp.tw = tb[i]->tw_long;
+        xp.fb = tb[i]->fb_dense; xp.rowband = tb[i]->rowband; xp.rowpk = tb[i]->rowpk; xp.long_rows = tb[i]->long_rows ? 1 : 0;
+        xp.grad_out = grad_out; xp.out = log ? out : nullptr; xp.grad_x = grad_x;
+        xp.B = batch; xp.L = L; xp.T = T; xp.hop = plan->cfg.hop_length; xp.M = M;
+        xp.nchunks = plan->nchunks; xp.N = N; xp.F = tb[i]->F; xp.remove_dc = 1; xp.spec_mode = 0;
+        xp.logN = 0; while ((1 << xp.logN) < N) ++xp.logN;
+        xp.inv_L = 1.0f / (float)L;
+        xp.tw1 = tb[i]->tw1p; xp.tw2 = tb[i]->tw2p;
+        xp.win_n = N / 2 + 1; xp.tiles = sh.tiles; xp.span = sh.span; xp.tile_step = sh.ts;
+        if (sh.wave) {
+            // one launch for every channel of this n_fft
+            dmel::XgradMultiParams mp{};
+            mp.p = xp;
+            for (int c = 0; c < channels; ++c) {
+                mp.win2[c] = table(c, N); mp.frames[c] = frames[c]; mp.csum[c] = csum[c];
+                mp.win_denom[c] = lam_host ? std::fabs(lam_host[c]) + 1e-15f : 0.f;
+                if (mask[i] >> c & 1u) { mp.ch_list |= (unsigned)c << (4 * mp.count); ++mp.count; }
+            }
+            mp.ch_grid = batch * sh.tiles; mp.ch_out = channels;
+            if ((long long)batch * sh.tiles * mp.count > 0x7fffffffLL) return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: grid too large");
+            DMEL_HIP(dmel::launch_xgrad_wave_multi(mp, s));
+        } else {
+            // the LDS path (cold): per channel, its rows of grad_out / out staged as (B, M, T), then the scalar frames kernel
+            for (int c = 0; c < channels; ++c) {
+                if (!(mask[i] >> c & 1u)) continue;
+                const size_t row = (size_t)M * T * sizeof(float);
+                DMEL_HIP(hipMemcpy2DAsync(stage, row, grad_out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
+                if (log) DMEL_HIP(hipMemcpy2DAsync(stage + bmt, row, out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
+                dmel::XgradParams q = xp;
+                q.grad_out = stage; q.out = log ? stage + bmt : nullptr;
+                q.win2 = table(c, N); q.frames = frames[c]; q.csum = csum[c];
+                q.lam_dev = lam_dev ? lam_dev + c : nullptr;
+                DMEL_HIP(dmel::launch_xgrad_frames(q, s));
+            }
+        }
+    }
+    // one combine: the channels' terms in ascending channel order
+    dmel::XgradCombineMultiParams cp{};
+    cp.grad_x = grad_x; cp.lam_dev = lam_dev; cp.L = L; cp.T = T; cp.hop = plan->cfg.hop_length; cp.channels = channels;
+    for (int c = 0; c < channels; ++c) {
+        cp.ncand[c] = ncand[c]; cp.frames[c] = frames[c]; cp.csum[c] = csum[c];
+        for (int j = 0; j < ncand[c]; ++j) {
+            const XgShape& sh = shape[cand[c][j]];
+            cp.n[c][j] = cand[c][j]; cp.tiles[c][j] = sh.tiles; cp.span[c][j] = sh.span; cp.tile_step[c][j] = sh.ts;
+        }
+    }
+    DMEL_HIP(dmel::launch_xgrad_combine_multi(cp, batch, s));
+    prof_span(plan, m0, prof_mark(plan, s), 2);
+    return DMEL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+dmel_status dmel_backward_x_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels,
+                                  uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    dmel_status st = check_x_multi_args(plan, x, batch, channels, flags, grad_out, out, grad_x, "dmel_backward_x_multi");
+    if (st != DMEL_OK) return st;
+    if (!lambd_host) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi: lambd_host is NULL");
+    std::map<int, uint32_t> u;
+    for (int c = 0; c < channels; ++c) {
+        if (!std::isfinite(lambd_host[c])) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd of channel " + std::to_string(c) + " is not finite");
+        const int n = dmel_n_fft(lambd_host[c]);
+        if (!multi_in_range(n))
+            return fail(DMEL_ERR_UNSUPPORTED, "channel " + std::to_string(c) + ": lambd = " + std::to_string(lambd_host[c]) + " gives n_fft " +
+                        std::to_string(n) + ", the multi-window layer serves 32 ... 16384");
+        u[n] |= 1u << c;
+    }
+    if (batch == 0) return DMEL_OK;
+    int ns[dmel::kMaxChannels]; uint32_t mask[dmel::kMaxChannels]; int nl = 0;
+    for (const auto& kv : u) { ns[nl] = kv.first; mask[nl] = kv.second; ++nl; }
+    return backward_x_multi_impl(plan, x, batch, lambd_host, nullptr, channels, ns, mask, nl, (flags & DMEL_FLAG_LOG) != 0, grad_out, out,
+                                 grad_x, stream);
+}
+
+dmel_status dmel_backward_x_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
+                                      const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count, uint32_t flags,
+                                      const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    dmel_status st = check_x_multi_args(plan, x, batch, channels, flags, grad_out, out, grad_x, "dmel_backward_x_multi_dev");
+    if (st != DMEL_OK) return st;
+    if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: lambd_dev is NULL");
+    if (!n_ffts || !channel_masks || count < 1 || count > 3 * dmel::kMaxChannels)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: the launch list (n_ffts, channel_masks, count) is missing or empty");
+    uint32_t seen = 0;
+    int per[dmel::kMaxChannels] = {};
+    for (int i = 0; i < count; ++i) {
+        const int n = n_ffts[i];
+        if (!multi_in_range(n) || (n & (n - 1)))
+            return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: n_ffts[" + std::to_string(i) + "] = " + std::to_string(n) +
+                        " is not a power of two in 32 ... 16384");
+        if (i > 0 && n <= n_ffts[i - 1]) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: n_ffts must be strictly ascending");
+        if (channel_masks[i] == 0 || (channels < 32 && (channel_masks[i] >> channels) != 0))
+            return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: channel_masks[" + std::to_string(i) + "] is empty or names a channel >= channels");
+        seen |= channel_masks[i];
+        for (int c = 0; c < channels; ++c)
+            if ((channel_masks[i] >> c & 1u) && ++per[c] > dmel::kXgMaxCand)
+                return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: channel " + std::to_string(c) + " is in more than 3 launches");
+    }
+    if (seen != (1u << channels) - 1u) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: a channel is in no launch");
+    if (batch == 0) return DMEL_OK;
+    return backward_x_multi_impl(plan, x, batch, nullptr, lambd_dev, channels, n_ffts, channel_masks, count, (flags & DMEL_FLAG_LOG) != 0,
+                                 grad_out, out, grad_x, stream);
+}
+
+dmel_status dmel_plan_last_multi_launch(dmel_plan* plan, int32_t* n_ffts, uint32_t* channel_masks, int32_t* count)
+{
+    if (!plan || !n_ffts || !channel_masks || !count) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_plan_last_multi_launch: bad arguments");
+    std::lock_guard<std::mutex> lock(plan->mu);
+    for (int i = 0; i < plan->last_multi_nl; ++i) { n_ffts[i] = plan->last_multi_ns[i]; channel_masks[i] = plan->last_multi_mask[i]; }
+    *count = plan->last_multi_nl;
+    return DMEL_OK;
 }
 
 dmel_status dmel_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* step, uint32_t* ticket, int64_t n,

@@ -517,6 +517,35 @@ hipError_t launch_xgrad_gather(const XgradParams& p, hipStream_t s);           /
 hipError_t xgrad_prepare_attributes();
 bool xgrad_wave_shape(int n_fft, int n_mels, int win_n, int* frames_per_tile);   // the wave-FFT kernel takes this shape
 int xgrad_chunks(int L);      // gather chunks per clip (size of XgradParams::csum per clip)
+hipError_t launch_xgrad_frames(const XgradParams& p, hipStream_t s);           // the LDS radix-2 frames kernel alone (no gather)
+
+// the multi-window layer's gradient w.r.t. the waveform.  grad_out / out are (B, K, M, T); every channel has its own window table, segment
+// (or frame) region and fp64 sums.  dmel_xgrad_wave_multi_kernel<N>: grid = count x B x tiles, channel slot w / ch_grid, channel = nibble
+// `slot` of ch_list (as FwdParams::ch_list); p.lam_dev is the base of the K device values (channel c reads lam_dev + c) or nullptr,
+// then win_denom[c] carries |lambd[c]| + 1e-15.
+struct XgradMultiParams {
+    XgradParams p;
+    const float2* win2[kMaxChannels];
+    float* frames[kMaxChannels];
+    double* csum[kMaxChannels];
+    float win_denom[kMaxChannels];
+    unsigned ch_list;
+    int count, ch_grid, ch_out;
+};
+// dmel_xgrad_combine_multi_kernel, grid (chunks, B): grad_x = 0 + term_0 + term_1 + ... in ascending channel order, every term with the
+// arithmetic of the scalar path of that channel (combine kernel: tiles > 0; gather kernel: tiles == 0).  With lambd on the device a
+// channel takes the candidate whose n_fft lambd asks for; none: its term is NaN (as that channel's forward output).
+constexpr int kXgMaxCand = 3;
+struct XgradCombineMultiParams {
+    float* grad_x; const float* lam_dev;
+    int L, T, hop, channels;
+    int ncand[kMaxChannels];
+    int n[kMaxChannels][kXgMaxCand], tiles[kMaxChannels][kXgMaxCand], span[kMaxChannels][kXgMaxCand], tile_step[kMaxChannels][kXgMaxCand];
+    const float* frames[kMaxChannels];
+    const double* csum[kMaxChannels];
+};
+hipError_t launch_xgrad_wave_multi(const XgradMultiParams& p, hipStream_t s);
+hipError_t launch_xgrad_combine_multi(const XgradCombineMultiParams& p, int batch, hipStream_t s);
 
 // gradient w.r.t. the filterbank matrix of models.py:53 (adjoint of  mel = spec^T @ fb):
 //   grad_fb[f][m] = sum_{b,t} spec[b][f][t] * gm[b][m][t],   gm = grad_out            (linear output)

@@ -493,15 +493,21 @@ class MelSpectrogramLayer(nn.Module):
 
 class _MultiFunction(torch.autograd.Function):
     """forward: dmel_forward_multi(_dev) -- one launch per distinct n_fft for all K channels, carrying d out / d lambd[k] per channel;
-    backward: dmel_backward_multi (K dot products in one launch)."""
+    backward: dmel_backward_multi (K dot products in one launch) and, for a waveform that requires grad (waveform_grad=True),
+    dmel_backward_x_multi(_dev): one x-gradient for all K channels, the sum of the K scalar layers' in ascending channel order."""
 
     @staticmethod
     def forward(ctx, x, lambd, plan, lam_host, log, eps, out_dtype, want_tangent):
         B, K = x.shape[0], lambd.shape[0]
-        out = torch.empty((B, K, plan.n_mels, plan.n_time), dtype=out_dtype, device=x.device)
+        want_x = ctx.needs_input_grad[0]
+        # the waveform gradient rebuilds 1 / (mel + eps) from the saved log output: fp32 here, rounded to bf16 afterwards (as _DmelFunction)
+        round_later = out_dtype == torch.bfloat16 and log and want_x
+        kdtype = torch.float32 if round_later else out_dtype
+        out = torch.empty((B, K, plan.n_mels, plan.n_time), dtype=kdtype, device=x.device)
         tangent = torch.empty(out.shape, dtype=torch.float32, device=x.device) if want_tangent else None
         scratch = torch.empty((plan.scratch_bytes_multi(B, K),), dtype=torch.uint8, device=x.device)
-        bf16 = out_dtype == torch.bfloat16
+        bf16 = kdtype == torch.bfloat16
+        lam = None
         with _on_device(x.device):
             if lam_host is not None:
                 plan.forward_multi(x.data_ptr(), B, lam_host, out.data_ptr(), tangent.data_ptr() if want_tangent else None, log, eps,
@@ -513,33 +519,54 @@ class _MultiFunction(torch.autograd.Function):
                 plan.forward_multi_dev(x.data_ptr(), B, lam.data_ptr(), K, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
                                        log, eps, _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
         ctx.plan, ctx.K, ctx.lambd_dtype = plan, K, lambd.dtype
-        if want_tangent:
-            ctx.save_for_backward(tangent, scratch)
-        return out
+        ctx.want_tangent, ctx.want_x, ctx.log, ctx.lam_host = want_tangent, want_x, bool(log), lam_host
+        # what this forward launched for (host bookkeeping of the plan, no device read): a later forward cannot change what the backward covers
+        ctx.launches = plan.last_multi_launch() if (want_x and lam_host is None) else None
+        saved = [tangent, scratch] if want_tangent else []
+        if want_x:
+            saved += [x] + ([lam] if lam is not None else []) + ([out] if log else [])
+        ctx.save_for_backward(*saved)
+        return out.to(torch.bfloat16) if round_later else out
 
     @staticmethod
     def backward(ctx, grad_out):
-        tangent, scratch = ctx.saved_tensors
+        saved = list(ctx.saved_tensors)
         bf16 = grad_out.dtype == torch.bfloat16
         g = grad_out
         if not bf16 and g.dtype != torch.float32:
             g = g.to(torch.float32)
         if not g.is_contiguous():
             g = g.contiguous()
-        dl = torch.empty((ctx.K,), dtype=torch.float32, device=g.device)
+        dl = gx = None
         with _on_device(g.device):
-            ctx.plan.backward_multi(g.data_ptr(), tangent.data_ptr(), g.shape[0], ctx.K, dl.data_ptr(), _stream_ptr(g.device),
-                                    scratch.data_ptr(), grad_bf16=bf16)
-        if ctx.lambd_dtype != torch.float32:
-            dl = dl.to(ctx.lambd_dtype)
-        return None, dl, None, None, None, None, None, None
+            if ctx.want_tangent:
+                tangent, scratch = saved.pop(0), saved.pop(0)
+                dl = torch.empty((ctx.K,), dtype=torch.float32, device=g.device)
+                ctx.plan.backward_multi(g.data_ptr(), tangent.data_ptr(), g.shape[0], ctx.K, dl.data_ptr(), _stream_ptr(g.device),
+                                        scratch.data_ptr(), grad_bf16=bf16)
+                if ctx.lambd_dtype != torch.float32:
+                    dl = dl.to(ctx.lambd_dtype)
+            if ctx.want_x:
+                x = saved.pop(0)
+                lam = saved.pop(0) if ctx.lam_host is None else None
+                out = saved.pop(0) if ctx.log else None
+                g32 = g.to(torch.float32)
+                gx = torch.empty_like(x)
+                if lam is None:
+                    ctx.plan.backward_x_multi(x.data_ptr(), x.shape[0], ctx.lam_host, g32.data_ptr(), out.data_ptr() if ctx.log else None,
+                                              gx.data_ptr(), ctx.log, _stream_ptr(g.device))
+                else:
+                    ctx.plan.backward_x_multi_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.K, ctx.launches, g32.data_ptr(),
+                                                  out.data_ptr() if ctx.log else None, gx.data_ptr(), ctx.log, _stream_ptr(g.device))
+        return gx, dl, None, None, None, None, None, None
 
 
 class MultiWindowMelSpectrogram(nn.Module):
     """K trainable window widths at once, returned as K output channels.
 
         MultiWindowMelSpectrogram(init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1,
-                                  normalize_window=False, *, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False)
+                                  normalize_window=False, *, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False,
+                                  waveform_grad=False)
         forward(x: (B, n_points)) -> (B, K, n_mels, n_points // hop_length + 1)
 
     ``y[:, k:k+1]`` is what ``MelSpectrogramLayer(lambd[k], ..., optimized=True)`` returns for the same ``x``, bit for bit (each
@@ -547,12 +574,15 @@ class MultiWindowMelSpectrogram(nn.Module):
     parameter ``lambd`` has shape ``(K,)``, 1 <= K <= 8; every channel's n_fft must lie in 32 ... 16384 (about 2.84 <= |lambd| <= 2730).
     A channel whose lambd leaves that range (or moves further than the sync-free forward covers) is NaN and the next forward raises.
     The kernels launch once per distinct n_fft for all the channels that need it; the backward is one launch for all K gradients.
-    Not supported: a waveform gradient (x.requires_grad), ``SlotInput``, ``GraphedStep`` and ``LambdAdam(fused_into_backward=...)``."""
+    ``waveform_grad=True`` accepts an ``x`` that requires grad: ``x.grad`` is, bit for bit, the sum in ascending channel order of what the K
+    scalar layers give (one x-gradient launch per distinct n_fft and one combine for all channels).  The forward then keeps ``x`` and the
+    fp32 output alive until the backward, which the default layer does not; without it ``x.requires_grad`` raises.
+    Not supported: ``SlotInput``, ``GraphedStep`` and ``LambdAdam(fused_into_backward=...)``."""
 
     MAX_CHANNELS = 8
 
     def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
-                 log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False):
+                 log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False):
         super().__init__()
         lam = init_lambd.detach().clone() if torch.is_tensor(init_lambd) else torch.tensor([float(v) for v in init_lambd])
         if lam.dim() != 1:
@@ -575,6 +605,7 @@ class MultiWindowMelSpectrogram(nn.Module):
         self.normalize_window = normalize_window
         self.n_time = n_points // hop_length + 1
         self.log, self.eps, self.out_dtype, self.lambd_sync = bool(log), float(eps), out_dtype, bool(lambd_sync)
+        self.waveform_grad = bool(waveform_grad)
         self._plans = {}
 
     @property
@@ -625,8 +656,8 @@ class MultiWindowMelSpectrogram(nn.Module):
             raise RuntimeError(f"input has {x.shape[1]} points, the layer was built for n_points={self.n_points}")
         if not x.is_cuda:
             raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
-        if x.requires_grad:
-            raise RuntimeError("MultiWindowMelSpectrogram has no waveform gradient: pass x.detach()")
+        if x.requires_grad and not self.waveform_grad:
+            raise RuntimeError("MultiWindowMelSpectrogram has no waveform gradient by default: pass waveform_grad=True, or x.detach()")
         if self.lambd.device != x.device:
             raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
         xf = x if x.dtype == torch.float32 else _to_f32(x)
@@ -640,7 +671,8 @@ class MultiWindowMelSpectrogram(nn.Module):
 
     def extra_repr(self):
         return (f"channels={self.channels}, n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
-                f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}")
+                f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}, "
+                f"waveform_grad={self.waveform_grad}")
 
 
 class _DspecFunction(torch.autograd.Function):

@@ -452,6 +452,24 @@ dmel_status dmel_plan_lambd_status_channel(dmel_plan* plan, int32_t channel, dme
  * stale_forwards), `count` entries in ascending n_fft, channel_masks[i] bit k = channel k needs n_ffts[i].  Arrays of 3 x channels entries. */
 dmel_status dmel_decide_launch_multi(const float* lambd, const float* rate, int32_t channels, float stale_forwards, int32_t* n_ffts,
                                      uint32_t* channel_masks, int32_t* count);
+/* Gradient w.r.t. the waveform of the multi-window layer: grad_x (batch, n_points) = the sum, in ascending channel order from 0, of what
+ * dmel_backward_x(_dev) gives for each channel, bit for bit.  grad_out and out are (batch, K, M, T) fp32; flags: DMEL_FLAG_LOG only (it
+ * needs out, the saved fp32 log output).  One wave-FFT launch per distinct n_fft <= 2048 for all the channels that need it, per-channel
+ * launches on the LDS path (n_fft 4096 ... 16384, or a shape the wave kernel does not fit), then ONE deterministic combine launch.
+ * dmel_backward_x_multi takes the K values from the host.  dmel_backward_x_multi_dev reads them on the device and takes the launch list
+ * of the forward whose gradient this is, (n_ffts, channel_masks, count) as dmel_plan_last_multi_launch returned it right after that
+ * forward: ascending powers of two in 32 ... 16384, every channel in some mask, no bit at or above `channels`.  Every launch of a channel
+ * returns at once unless lambd[k] asks for its n_fft; a channel that none matches makes grad_x NaN (its forward output is NaN too).
+ * The workspace is plan-owned; an eager call sizes it for every channel's n_fft / 2, n_fft and 2 n_fft, so that a later capture near an
+ * n_fft boundary needs no growth (a capture that would need some: DMEL_ERR_INVALID_ARGUMENT, run once eagerly). */
+dmel_status dmel_backward_x_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels,
+                                  uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream);
+dmel_status dmel_backward_x_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
+                                      const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count, uint32_t flags,
+                                      const float* grad_out, const float* out, float* grad_x, void* stream);
+/* What the most recent dmel_forward_multi(_dev) on this plan issued (host bookkeeping, captured calls included): count entries in
+ * ascending n_fft with their channel masks; arrays of 24 (3 x 8) entries.  count = 0 before the first such call. */
+dmel_status dmel_plan_last_multi_launch(dmel_plan* plan, int32_t* n_ffts, uint32_t* channel_masks, int32_t* count);
 
 /* Introspection for tests / benchmarks */
 typedef struct dmel_plan_info {

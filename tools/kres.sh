@@ -4,7 +4,7 @@
 set -e
 T=$(mktemp -d)
 L=/opt/rocm/lib/llvm/bin
-$L/llvm-objcopy --dump-section .hip_fatbin=$T/fat.bin "$1"
+$L/llvm-objcopy --dump-section .hip_fatbin=$T/fat.bin "$1" $T/copy.o     # (an output file: without one objcopy rewrites its input)
 $L/clang-offload-bundler --type=o --unbundle --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$T/fat.bin --output=$T/k.co
 $L/llvm-readelf --notes $T/k.co | python3 -c "
 import re, sys
