@@ -44,6 +44,7 @@ SYMBOLS = (
     "dmel_mailbox_set_spin_limit", "dmel_mailbox_set_timeout_ms", "dmel_plan_is_live", "dmel_lambd_ring_size", "dmel_spectrogram_ex_dev", "dmel_forward_dev_fixed_spec", "dmel_backward_fb_saved", "dmel_backward_fb_saved_dl", "dmel_backward_x_dev", "dmel_backward_x_spec_dev", "dmel_plan_attach_mailbox", "dmel_backward_x_spec", "dmel_plan_attach_adam",
     "dmel_scratch_bytes_multi", "dmel_forward_multi", "dmel_forward_multi_dev", "dmel_backward_multi", "dmel_plan_lambd_status_channel",
     "dmel_decide_launch_multi", "dmel_backward_x_multi", "dmel_backward_x_multi_dev", "dmel_plan_last_multi_launch",
+    "dmel_forward_lengths", "dmel_forward_dev_lengths",
 )
 TORCH_LIB_PATH = os.path.join(_PKG_DIR, "libdmel_torch.so")
 
@@ -154,6 +155,10 @@ def load():
     L.dmel_forward_scratch.restype = C.c_int
     L.dmel_forward_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
     L.dmel_forward_dev.restype = C.c_int
+    L.dmel_forward_lengths.argtypes = [vp, vp, vp, C.c_int32, C.c_float, C.c_uint32, C.c_double, vp, vp, vp, vp]
+    L.dmel_forward_lengths.restype = C.c_int
+    L.dmel_forward_dev_lengths.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
+    L.dmel_forward_dev_lengths.restype = C.c_int
     L.dmel_forward_dev_fixed.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.c_double, vp, vp, vp, vp]
     L.dmel_forward_dev_fixed.restype = C.c_int
     L.dmel_backward_fb_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, vp, vp, vp, vp]

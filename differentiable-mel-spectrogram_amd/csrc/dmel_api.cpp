@@ -785,11 +785,14 @@ struct MultiLaunch { int ch_out = 0, count = 0; unsigned list = 0, roles = 0; fl
 
 dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dmel::LamArgs lam, unsigned flags, double eps,
                              float* out, float* tangent, int mode, int remove_dc, const Scratch& sc, hipStream_t s, int win_half,
-                             bool* sums_done, float* spec_out = nullptr, const MultiLaunch* ml = nullptr)
+                             bool* sums_done, float* spec_out = nullptr, const MultiLaunch* ml = nullptr, const int32_t* lengths = nullptr)
 {
     if (N < 1) return fail(DMEL_ERR_UNSUPPORTED, "n_fft = " + std::to_string(N));
     const bool pow2 = (N & (N - 1)) == 0;
     const bool big = !pow2 || N > dmel::kMaxNfft;
+    // per-clip lengths (dmel_fwd_len_kernel): the fused kernel's range, the scalar layer's HTK bank
+    if (lengths && (big || N < dmel::kMinFastNfft || spec_out || ml || win_half))
+        return fail(DMEL_ERR_UNSUPPORTED, "per-clip lengths run the fused kernel only: n_fft 32 ... 16384 (n_fft = " + std::to_string(N) + ")");
     if (ml && (big || N < dmel::kMinFastNfft || spec_out))
         return fail(DMEL_ERR_UNSUPPORTED, "the multi-window layer runs n_fft 32 ... 16384 only (n_fft = " + std::to_string(N) + ")");
     if (spec_out && (big || N < dmel::kMinFastNfft || mode != dmel::kTrain))
@@ -897,6 +900,7 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
         pp.B = need_sums ? batch : 0; pp.L = pl->cfg.n_points; pp.nchunks = pl->nchunks; pp.chunk = pl->chunk;
         pp.N = need_window ? N : 0; pp.normalize = pl->cfg.normalize_window; pp.win_half = win_half; pp.center = center;
         pp.lam = lam; pp.lam.role = dmel::kLamQuiet;
+        pp.lengths = need_sums ? lengths : nullptr;
         if (ml && need_window) {
             // the multi-window layer: one window table per channel (win + c kMaxNfft, lambd[c]); the clip sums once for all of them
             for (int i = 0; i < ml->count; ++i) {
@@ -941,7 +945,7 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     fp.B = batch; fp.L = pl->cfg.n_points; fp.T = pl->T; fp.hop = pl->cfg.hop_length; fp.M = pl->cfg.n_mels;
     fp.nchunks = pl->nchunks; fp.groups = tb->groups; fp.xch_groups = tb->xch_groups;
     // DMEL_FLAG_MFMA_BF16X3: the training forward through a caller-supplied (dense) bank contracts on the bf16 matrix pipe
-    const bool hsplit = (flags & DMEL_FLAG_MFMA_BF16X3) && mode == dmel::kTrain && tb->ent_h != nullptr;
+    const bool hsplit = (flags & DMEL_FLAG_MFMA_BF16X3) && mode == dmel::kTrain && tb->ent_h != nullptr && !lengths;
     if (hsplit) mode = dmel::kTrainH;
     // the wave-local contraction where it is built (n_fft 1024, up to 512 mel bands): DMEL_WLC=0 keeps the round-4 kernel, DMEL_WLC=1
     // the 8-wave workgroups, DMEL_WLC=2 the 16-wave ones where they are built (diagnostics).
@@ -951,7 +955,7 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     const bool wl_compact = tb->wl_total4 * 4 <= 320;
     if (mode == dmel::kTrain && tb->wl_b4 != nullptr && wlc_env != 0 && (wl_compact || wlc_env > 0)) {
         const int wide_fpt = dmel::forward_has_wlc_wide(N) ? dmel::forward_frames_per_tile(N, dmel::kTrainWW) : 0;
-        const bool wide = wide_fpt > 0 && wlc_env == 2;      // (16-wave workgroups: measured slower, dmel_kernels.h; built only on request)
+        const bool wide = wide_fpt > 0 && wlc_env == 2 && !lengths;      // (16-wave workgroups: measured slower, dmel_kernels.h; built only on request)
         mode = wide ? dmel::kTrainWW : dmel::kTrainW;
         fp.wl_b4 = tb->wl_b4; fp.wl_lane = tb->wl_lane; fp.wl_phases = tb->wl_phases; fp.wl_total4 = tb->wl_total4;
         for (int i = 0; i < dmel::kWlMaxPhases; ++i) { fp.wl_len4[i] = tb->wl_len4[i]; fp.wl_mg[i] = tb->wl_mg[i]; }
@@ -966,7 +970,7 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     static const int force_tpw = std::getenv("DMEL_TILES_PER_WG") ? std::atoi(std::getenv("DMEL_TILES_PER_WG")) : 0;   // diagnostics
     int tpw = dmel::forward_tiles_per_wg(N, mode, batch, fp.tiles_per_clip);
     if (force_tpw == 1 || (force_tpw == 2 && dmel::forward_two_tiles(N, mode))) tpw = force_tpw;
-    if (hsplit) tpw = 1;
+    if (hsplit || lengths) tpw = 1;                  // (dmel_fwd_len_kernel: one tile per workgroup)
     fp.wgs_per_clip = (fp.tiles_per_clip + tpw - 1) / tpw;
     long long grid = (long long)batch * fp.wgs_per_clip;
     if (ml) {
@@ -976,7 +980,14 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     }
     if (grid > 0x7fffffffLL) return fail(DMEL_ERR_INVALID_ARGUMENT, "too many tiles for one launch");
     if (grid <= dmel::forward_resident_workgroups(N, mode)) fp.flags |= dmel::kFwdEdgeFirst;      // one round: see the kernel's prologue
-    DMEL_HIP(dmel::launch_forward(N, mode, tpw, fp, (int)grid, s));
+    if (lengths) {
+        dmel::FwdLenParams lp{};
+        static_cast<dmel::FwdParams&>(lp) = fp;
+        lp.lengths = lengths;
+        DMEL_HIP(dmel::launch_forward_len(N, mode, tpw, lp, (int)grid, s));
+    } else {
+        DMEL_HIP(dmel::launch_forward(N, mode, tpw, fp, (int)grid, s));
+    }
     prof_span(pl, m1, prof_mark(pl, s), 1);
     pl->info.kernel_path = 0; pl->info.frames_per_tile = fpt; pl->info.grid_fwd = (int)grid;
     pl->info.fb_blocks = tb->n_entries; pl->info.fb_blocks_dense = tb->n_dense;
@@ -1025,7 +1036,8 @@ dmel_status check_forward_args(dmel_plan* pl, const float* x, int batch, const v
 // be given (n_fft_override: the lengths that do not depend on lambd -- optimized=False branches, the spectrogram layer).
 dmel_status run_forward_nolock(dmel_plan* pl, const float* x, int batch, float lambd, unsigned flags, double eps,
                         float* out, float* tangent, int mode, int remove_dc, void* stream,
-                        int n_fft_override = 0, int win_half = 0, void* scratch = nullptr, const float* lambd_dev = nullptr)
+                        int n_fft_override = 0, int win_half = 0, void* scratch = nullptr, const float* lambd_dev = nullptr,
+                        const int32_t* lengths = nullptr)
 {
     dmel_status st = check_forward_args(pl, x, batch, out);
     if (st != DMEL_OK) return st;
@@ -1045,16 +1057,18 @@ dmel_status run_forward_nolock(dmel_plan* pl, const float* x, int batch, float l
     lam.role = dmel::kLamFirst | dmel::kLamLast;
     lam.dot_counter = scratch ? sc.counter : nullptr;            // plan-owned counters are zeroed at allocation and reset themselves
     bool sums_done = false;
-    return launch_forward_n(pl, x, batch, N, lam, flags, eps, out, tangent, mode, remove_dc, sc, s, win_half, &sums_done);
+    return launch_forward_n(pl, x, batch, N, lam, flags, eps, out, tangent, mode, remove_dc, sc, s, win_half, &sums_done, nullptr, nullptr, lengths);
 }
 
 dmel_status run_forward(dmel_plan* pl, const float* x, int batch, float lambd, unsigned flags, double eps,
                         float* out, float* tangent, int mode, int remove_dc, void* stream,
-                        int n_fft_override = 0, int win_half = 0, void* scratch = nullptr, const float* lambd_dev = nullptr)
+                        int n_fft_override = 0, int win_half = 0, void* scratch = nullptr, const float* lambd_dev = nullptr,
+                        const int32_t* lengths = nullptr)
 {
     if (!pl) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
     std::lock_guard<std::mutex> lock(pl->mu);
-    return run_forward_nolock(pl, x, batch, lambd, flags, eps, out, tangent, mode, remove_dc, stream, n_fft_override, win_half, scratch, lambd_dev);
+    return run_forward_nolock(pl, x, batch, lambd, flags, eps, out, tangent, mode, remove_dc, stream, n_fft_override, win_half, scratch, lambd_dev,
+                              lengths);
 }
 
 // ---- device-resident lambd ---------------------------------------------------------------------------------------------
@@ -1256,6 +1270,7 @@ dmel_status dmel_plan_create(const dmel_config* cfg, dmel_plan** plan)
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(DMEL_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", libdmel_hip is built for gfx950 only");
     DMEL_HIP(dmel::forward_prepare_attributes());
+    DMEL_HIP(dmel::forward_len_prepare_attributes());
     DMEL_HIP(dmel::xgrad_prepare_attributes());
     DMEL_HIP(dmel::big_prepare_attributes());
     dmel_plan* pl = new (std::nothrow) dmel_plan();
@@ -1432,8 +1447,9 @@ size_t dmel_scratch_bytes(const dmel_plan* plan, int32_t batch)
     return scratch_bytes(plan, batch);
 }
 
-dmel_status dmel_forward_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, uint32_t flags,
-                             double eps, void* out, float* tangent, void* scratch, void* stream)
+// dmel_forward_dev and dmel_forward_dev_lengths (lengths != nullptr: the launches stay inside the fused kernel's range)
+static dmel_status forward_dev_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, uint32_t flags,
+                                    double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* lengths)
 {
     dmel_status st = check_forward_args(plan, x, batch, out);
     if (st != DMEL_OK) return st;
@@ -1482,6 +1498,12 @@ dmel_status dmel_forward_dev(dmel_plan* plan, const float* x, int32_t batch, con
     }
     int N = 0, guards = 0;
     lam_decide(plan, capturing, &N, &guards);
+    if (lengths) {
+        // clamped to the range the fused kernel serves, as dmel_forward_multi_dev: a forward whose lambd left it is poisoned and reported
+        N = std::min(std::max(N, dmel::kMinFastNfft), dmel::kMaxFastNfft);
+        if (2 * N > dmel::kMaxFastNfft) guards &= ~2;
+        if (N / 2 < dmel::kMinFastNfft) guards &= ~1;
+    }
     // tables of the neighbouring sizes exist before they are needed: building them allocates and copies (not allowed
     // under capture, and a stall at the moment of a crossing otherwise)
     if (!capturing) {
@@ -1513,12 +1535,43 @@ dmel_status dmel_forward_dev(dmel_plan* plan, const float* x, int32_t batch, con
         lam.host_seen = &plan->host_words[0]; lam.host_error = &plan->host_words[dmel::kLamRing];
         lam.dot_counter = scratch ? sc.counter : nullptr;
         st = launch_forward_n(plan, x, batch, cand[i], lam, flags, eps, static_cast<float*>(out), tangent,
-                              tangent ? dmel::kTrain : dmel::kInfer, /*remove_dc=*/1, sc, s, 0, &sums_done);
+                              tangent ? dmel::kTrain : dmel::kInfer, /*remove_dc=*/1, sc, s, 0, &sums_done, nullptr, nullptr, lengths);
         if (st != DMEL_OK) return st;
         if (i == 0) primary_info = plan->info;
     }
     plan->info = primary_info;        // dmel_plan_get_info describes the launch the host expected to do the work
     return DMEL_OK;
+}
+
+dmel_status dmel_forward_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, uint32_t flags,
+                             double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    return forward_dev_impl(plan, x, batch, lambd_dev, flags, eps, out, tangent, scratch, stream, nullptr);
+}
+
+// the flags the per-clip-lengths forwards take
+constexpr uint32_t kLengthsFlags = DMEL_FLAG_LOG | DMEL_FLAG_OUT_BF16 | DMEL_FLAG_X_INDIRECT;
+
+dmel_status dmel_forward_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, float lambd, uint32_t flags,
+                                 double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    if (!plan || !x || !lengths || !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_lengths: plan / x / lengths / out is NULL");
+    if (flags & ~kLengthsFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_lengths: flags other than LOG, OUT_BF16, X_INDIRECT");
+    if (!std::isfinite(lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
+    const int N = dmel_n_fft(lambd);
+    if (N < dmel::kMinFastNfft || N > dmel::kMaxFastNfft)
+        return fail(DMEL_ERR_UNSUPPORTED, "per-clip lengths run n_fft 32 ... 16384; lambd = " + std::to_string(lambd) + " gives n_fft " + std::to_string(N));
+    return run_forward(plan, x, batch, lambd, flags, eps, static_cast<float*>(out), tangent, tangent ? dmel::kTrain : dmel::kInfer,
+                       /*remove_dc=*/1, stream, 0, 0, scratch, nullptr, lengths);
+}
+
+dmel_status dmel_forward_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                     uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    if (!plan || !x || !lengths || !out || !lambd_dev)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_lengths: plan / x / lengths / lambd_dev / out is NULL");
+    if (flags & ~kLengthsFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_lengths: flags other than LOG, OUT_BF16, X_INDIRECT");
+    return forward_dev_impl(plan, x, batch, lambd_dev, flags, eps, out, tangent, scratch, stream, lengths);
 }
 
 dmel_status dmel_forward_dev_fixed(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft,

@@ -32,9 +32,6 @@
 namespace dmel {
 
 
-#ifndef DMEL_TWC
-#define DMEL_TWC 8
-#endif
 #ifndef DMEL_FWD_PART
 #define DMEL_FWD_PART 0
 #endif
@@ -83,6 +80,13 @@ __global__ void __launch_bounds__(kThreads) dmel_prep_kernel(PrepParams p)
     const int b = blockIdx.y, c = blockIdx.x;
     const long long lo = (long long)c * p.chunk;
     long long hi = lo + p.chunk; if (hi > p.L) hi = p.L;
+    if (p.lengths) {
+        // per-clip lengths: the sums stop at the clip's end (a chunk past it adds up nothing)
+        const int lb = p.lengths[b];
+        const long long end = (lb >= 1 && lb <= p.L) ? lb : 1;
+        if (hi > end) hi = end;
+        if (hi < lo) hi = lo;
+    }
     const float* xbase = p.x;
     if (p.x_ind) { typedef const float* cfp; xbase = *(const __attribute__((address_space(4))) cfp*)p.x_ind; }      // the batch by address
     const float* xb = xbase + (size_t)b * p.L;
@@ -131,16 +135,7 @@ hipError_t launch_prep(const PrepParams& p, hipStream_t s)
 
 // ---- fused forward --------------------------------------------------------------------------
 
-// log(me), me = mel + eps, for the fused epilogue (models.py:73).  With the reference's eps (1e-10, any eps >= 1e-30) the argument is a
-// normal number: v_log_f32 (log2, 1 ulp) times ln 2 -- 2 instructions against ~12 of logf(), whose extra work is the scaling of
-// denormal arguments; absolute error <= 3e-6 at |log| = 23 (the 1e-4 bar of the path is absolute in the log domain).  eps below
-// that (or negative): logf().  The choice is uniform over the launch.
-__device__ __attribute__((noinline)) float slow_log(float me) { return logf(me); }   // (a call: the compiler does not fold the two paths into a select)
-__device__ __forceinline__ float fast_log(float me, float eps)
-{
-    if (eps >= 1e-30f) return __builtin_amdgcn_logf(me) * 0.69314718055994530942f;
-    return slow_log(me);
-}
+#include "dmel_fwd_log.h"
 
 #ifdef DMEL_STAMPS
 // Diagnostic build only (tools/stamps.py): s_memtime stamps of every wave at the phase boundaries of the

@@ -1,6 +1,7 @@
 // dmel_fwd_body.inc -- the fused forward kernel, included twice by dmel_fwd.hip: DMEL_FWD_MULTI = 0 makes dmel_fwd_kernel (the scalar layer), 1
-// makes dmel_fwd_multi_kernel (the multi-window layer, FwdParams::ch_out > 0).  The FWD_* names below expand, for the scalar kernel, to exactly
-// the tokens it was written with, so that its code does not change.
+// makes dmel_fwd_multi_kernel (the multi-window layer, FwdParams::ch_out > 0).  dmel_fwd_len.hip includes it a third time with DMEL_FWD_LEN = 1:
+// dmel_fwd_len_kernel, the scalar layer over clips of per-clip lengths (FwdLenParams).  The FWD_* names below expand, for the scalar kernel, to
+// exactly the tokens it was written with, so that its code does not change.
 #if DMEL_FWD_MULTI
 #define FWD_BO bo
 #define FWD_LAM lam_args
@@ -12,10 +13,34 @@
 #define FWD_LAM p.lam
 #define FWD_WIN2 p.win2
 #define FWD_LEADER blockIdx.x == 0
+#if DMEL_FWD_LEN
+#define FWD_KERNEL dmel_fwd_len_kernel
+#else
 #define FWD_KERNEL dmel_fwd_kernel
 #endif
+#endif
+// sample-space bounds of a clip: p.L (also the row stride of x) and fl32(1 / L), or the clip's own length Lc (dmel_fwd_len_kernel); its
+// frames: p.T, or Tc
+// FWD_PAD_MEL(t, v): the mel power v of frame t, or 0 in a pad frame -- the pair modes' epilogue: there a pad frame shares its complex FFT
+// with a frame of the clip and would carry that frame's rounding noise
+#if DMEL_FWD_LEN
+#define FWD_PARAMS FwdLenParams
+#define FWD_LC Lc
+#define FWD_INV_L inv_Lc
+#define FWD_TC Tc
+#define FWD_PAD_MEL(t, v) ((t) < Tc ? (v) : 0.f)
+#else
+#define FWD_PARAMS FwdParams
+#define FWD_LC p.L
+#define FWD_INV_L p.inv_L
+#define FWD_TC p.T
+#define FWD_PAD_MEL(t, v) v
+#endif
+#ifndef DMEL_TWC
+#define DMEL_TWC 8
+#endif
 template <int N, int MODE, int TPW>
-__global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, MODE>().MINW)) FWD_KERNEL(FwdParams p)
+__global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, MODE>().MINW)) FWD_KERNEL(FWD_PARAMS p)
 {
     constexpr FftGeom g = geom_mode<N, MODE>();
     constexpr int R = g.R, C = g.C, G = g.G, FPW = g.FPW, PASSES = g.PASSES, SLOTS = g.SLOTS, MT = g.MT;
@@ -91,6 +116,16 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
 #if DMEL_FWD_MULTI
     const int bo = b * p.ch_out + ch;
 #endif
+#if DMEL_FWD_LEN
+    // the clip is x[b, :Lc] (one scalar load: uniform over the workgroup) with Tc = Lc / hop + 1 frames; the frames past them are pad frames.
+    // A length outside 1 ... L makes the clip's rows NaN (behind the coverage check below); until then it reads as 1, so that every load of the
+    // workgroup stays inside the row
+    const int len_raw = *(const __attribute__((address_space(4))) int*)(p.lengths + b);
+    const bool len_ok = len_raw >= 1 && len_raw <= p.L;
+    const int Lc = __builtin_amdgcn_readfirstlane(len_ok ? len_raw : 1);
+    const int Tc = Lc / p.hop + 1;
+    const float inv_Lc = 1.0f / (float)Lc;
+#endif
     const int tile0 = (wg % p.wgs_per_clip) * TPW;              // first tile of this workgroup inside its clip
     STAMP(0);
     STAMP_PLACE();
@@ -115,7 +150,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
     // new batch by rewriting 8 bytes
     const float* xbase = p.x;
     if (p.x_ind) { typedef const float* cfp; xbase = *(const __attribute__((address_space(4))) cfp*)p.x_ind; }
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(xbase + (size_t)b * p.L, (unsigned)p.L * 4u);
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(xbase + (size_t)b * p.L, (unsigned)FWD_LC * 4u);
     const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.ent_b, (unsigned)p.ent_b_floats * 4u);
 
     // ---- what phase 2 needs from global memory: (ks0, nks, boff, tile) of this wave's mel runs in group 0 and their
@@ -263,7 +298,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
             const int tA = PAIR ? (t0 + 2 * slot) : (t0 + slot);
             const int f0 = tA * p.hop - N / 2;                       // first sample of frame tA
             const int f1 = PAIR ? f0 + p.hop : f0;
-            inside[ti][pass] = __all((f0 >= 0) && (f1 + N <= p.L));
+            inside[ti][pass] = __all((f0 >= 0) && (f1 + N <= FWD_LC));
 #ifdef DMEL_ABLATE
             if (p.flags & 0x2000u) inside[ti][pass] = true;      // timing only: no edge path (edge frames come out wrong)
 #endif
@@ -281,13 +316,36 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
             } else {
                 static_for<0, R>([&](auto aa) {
                     constexpr int a = decltype(aa)::value;
-                    xa[ti][pass][a] = buf_f32(rx, clampi(sA + G * a, p.L - 1) * 4);
-                    if constexpr (PAIR) xb2[ti][pass][a] = buf_f32(rx, clampi(sA + p.hop + G * a, p.L - 1) * 4);
+                    xa[ti][pass][a] = buf_f32(rx, clampi(sA + G * a, FWD_LC - 1) * 4);
+                    if constexpr (PAIR) xb2[ti][pass][a] = buf_f32(rx, clampi(sA + p.hop + G * a, FWD_LC - 1) * 4);
                 });
             }
         });
     };
 
+#if DMEL_FWD_LEN
+    // rows of frames [t_first, t_end) of this clip without a transform: pad frames (zero mel power -- 0, or the epilogue's own log(0 + eps) --
+    // and a zero tangent) or, for an invalid length, NaN
+    auto fill_rows = [&](int t_first, int t_end, bool pad) {
+        const bool do_log = (p.flags & 1u) != 0;
+        const bool out_bf16 = (p.flags & 4u) != 0;
+        float v = __builtin_nanf(""), tv = v;
+        if (pad) {
+            const float me = 0.f + p.eps;
+            v = do_log ? (WLC ? fast_log(me, p.eps) : logf(me)) : 0.f;
+            tv = 0.f;
+        }
+        if (t_end > p.T) t_end = p.T;
+        const int nf = t_end - t_first;
+        if (nf <= 0) return;
+        for (int idx = tid; idx < p.M * nf; idx += THREADS) {
+            const int m = idx / nf, t = t_first + idx % nf;
+            const size_t o = ((size_t)b * p.M + m) * p.T + t;
+            if (out_bf16) reinterpret_cast<unsigned short*>(p.out)[o] = bf16_bits(v); else p.out[o] = v;
+            if (p.tangent) p.tangent[o] = tv;
+        }
+    };
+#endif
     // ================= prologue, once per workgroup ============================================
     constexpr bool TW1_LDS = g.TW1_OFF != 0;                    // first-stage twiddles from a table in LDS (kTrainW where it fits)
     constexpr bool TW1_POW = (R >= 16) && !TW1_LDS;             // first-stage twiddles by powers: see phase 1
@@ -337,6 +395,14 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
             }
             return;
         }
+#if DMEL_FWD_LEN
+        // a workgroup whose first frame lies past the clip transforms nothing: it writes its pad rows (or NaN rows for an invalid length) and is
+        // done.  (Behind the coverage check: only the launch whose n_fft the device lambd selects writes.)
+        if (!len_ok || tile0 * FPT >= Tc) {
+            fill_rows(tile0 * FPT, (tile0 + TPW) * FPT, len_ok);
+            return;
+        }
+#endif
         if constexpr (WPF > 1) {
             if (tid < 4) fctr[tid] = 0u;                                  // the frames' meeting counters (sync_frame)
             __syncthreads();
@@ -449,7 +515,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                 constexpr int st = 1 << decltype(ll)::value;
                 static_for<0, WAVES / (2 * st)>([&](auto ii) { constexpr int i = decltype(ii)::value * 2 * st; t[i] += t[i + st]; });
             });
-            return mean_quotient(t[0], p.L, p.inv_L);
+            return mean_quotient(t[0], FWD_LC, FWD_INV_L);
         };
 #ifdef DMEL_ABLATE
         const bool dbg_no_mean = (p.flags & 0x1000u) != 0;      // timing ablation: no clip sum (mean = 0)
@@ -473,8 +539,8 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                     const int n = lg + G * a;                                // >= N/2: inside the frame's second half
                     const bool seg = n < N / 2 + p.hop;
                     const int ia = tA * p.hop - N / 2 + n;
-                    ps += (seg && tA < p.T && ia < p.L) ? xa[0][pass][a] : 0.f;
-                    if constexpr (PAIR) ps += (seg && tA + 1 < p.T && ia + p.hop < p.L) ? xb2[0][pass][a] : 0.f;
+                    ps += (seg && tA < FWD_TC && ia < FWD_LC) ? xa[0][pass][a] : 0.f;
+                    if constexpr (PAIR) ps += (seg && tA + 1 < FWD_TC && ia + p.hop < FWD_LC) ? xb2[0][pass][a] : 0.f;
                 });
             });
             mean = mean_of(wave_sum(ps));
@@ -492,7 +558,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
 #ifdef DMEL_ABLATE
                 const int n4 = (p.flags & 0x40000u) ? p.L / 8 : ((p.flags & 0x80000u) ? p.L / 16 : p.L / 4);   // timing only: part of the clip
 #else
-                const int n4 = p.L / 4;
+                const int n4 = FWD_LC / 4;
 #endif
                 for (int base = 0; base < n4; base += THREADS * KB) {
                     float4 v[KB];
@@ -513,7 +579,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
             }
             // what is left (the last L % 4 samples, or everything for a clip that is not 16-byte aligned): dword buffer
             // loads, out-of-range offsets return 0
-            for (int base = i; base < p.L; base += THREADS * KB) {
+            for (int base = i; base < FWD_LC; base += THREADS * KB) {
                 float v[KB];
                 static_for<0, KB>([&](auto jj) { v[decltype(jj)::value] = buf_f32(rx, (base + tid + THREADS * decltype(jj)::value) * 4); });
                 static_for<0, KB>([&](auto jj) { a0 += v[decltype(jj)::value]; });
@@ -524,7 +590,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
             if (p.remove_dc) {
                 // long clips: the <= 64 partial sums of the prep kernel, one per lane, one round trip, added
                 // in a fixed butterfly order (deterministic)
-                mean = mean_quotient(wave_sum(ps_early), p.L, p.inv_L);
+                mean = mean_quotient(wave_sum(ps_early), FWD_LC, FWD_INV_L);
             }
         }
         STAMP(2);   // window table + clip mean done
@@ -549,6 +615,9 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
         constexpr int ti = decltype(tt)::value;
         if (ti > 0 && tile0 + ti >= p.tiles_per_clip) return;          // the clip has no such tile (same answer in every wave)
         const int t0 = (tile0 + ti) * FPT;
+#if DMEL_FWD_LEN
+        if (ti > 0 && t0 >= Tc) { fill_rows(t0, t0 + FPT, true); return; }      // a later tile past the clip: its pad rows only
+#endif
         if constexpr (ti > 0) STAMP(16 * ti + 2);   // previous tile's epilogue issued, this tile begins
         if constexpr (ti > 0) {
             // the FFT slots (every wave has read the previous tile's spectra before the barriers of its phase 2 or the one
@@ -637,16 +706,28 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                         else z[a] = v2f{va, xb2[ti][pass][a] - mean_i} * wd.xx;
                     });
                 } else {
+#if DMEL_FWD_LEN
+                    // samples of the clip only; a pad frame (Tc <= t < T) is all zero: its spectrum, mel power and tangent are exactly 0.  Frames
+                    // past the output (t >= T, never written) keep the default path's samples: the pair modes' two frames of a complex FFT share
+                    // its rounding, and with Lc = L every frame must come out as dmel_fwd_kernel's
+                    const int lim_a = (tA < Tc || tA >= p.T) ? Lc : 0;
+                    [[maybe_unused]] const int lim_b = (tA + 1 < Tc || tA + 1 >= p.T) ? Lc : 0;
+#define FWD_LIM_A lim_a
+#define FWD_LIM_B lim_b
+#else
+#define FWD_LIM_A p.L
+#define FWD_LIM_B p.L
+#endif
                     static_for<0, R>([&](auto aa) {
                         constexpr int a = decltype(aa)::value;
                         const int n = lg + G * a;
                         const v2f wd = wload(aa);
                         const int ia = f0 + n;
-                        const float va = ((ia >= 0) && (ia < p.L)) ? xa[ti][pass][a] - mean : 0.f;
+                        const float va = ((ia >= 0) && (ia < FWD_LIM_A)) ? xa[ti][pass][a] - mean : 0.f;
                         if constexpr (!PAIR) z[a] = splat(va) * wd;
                         else {
                             const int ib = f1 + n;
-                            const float vb = ((ib >= 0) && (ib < p.L)) ? xb2[ti][pass][a] - mean : 0.f;
+                            const float vb = ((ib >= 0) && (ib < FWD_LIM_B)) ? xb2[ti][pass][a] - mean : 0.f;
                             z[a] = v2f{va, vb} * wd.xx;
                             // (the frames at a clip's edge, pair modes: four entries at a time.  Interleaved freely, the index arithmetic of all R entries
                             // raised this RARE path's register demand past the budget, and what it spilled -- z[0 .. 4] -- was spilled on the interior path too)
@@ -654,6 +735,15 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                         }
                     });
                 }
+#if DMEL_FWD_LEN
+                // (radix-8 and radix-4 plans, n_fft 32 ... 128: the windowed samples are materialised before the transform.  Without this the
+                // backend fused two window products into the first butterflies (two v_pk_mul_f32 + v_pk_add_f32 became v_pk_fma_f32), which
+                // dmel_fwd_kernel does not: full-length clips came out 1 - 2 ulp off the default path.  With it both round alike.)
+                if constexpr (R <= 8) {
+#pragma unroll
+                    for (int a = 0; a < R; ++a) asm volatile("" : "+v"(z[a]));
+                }
+#endif
                 STAMP(16 * ti + 3);   // samples arrived, windowed
                 if constexpr (USE_DIT) fft_reg_dit<R>(z); else fft_reg<R>(z);
                 STAMP(16 * ti + 4);   // radix-R #1
@@ -1289,7 +1379,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                                 const int slot = mt * 8 + 2 * cg + (i & 1);
                                 const int t = t0 + 2 * slot + (i >> 1);
                                 if (slot < SLOTS && t < p.T) {
-                                    const float mel = 0.25f * a[i];
+                                    const float mel = FWD_PAD_MEL(t, 0.25f * a[i]);
                                     put(t, do_log ? logf(mel + p.eps) : mel);
                                 }
                             });
@@ -1504,3 +1594,10 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
 #undef FWD_WIN2
 #undef FWD_LEADER
 #undef FWD_KERNEL
+#undef FWD_PARAMS
+#undef FWD_LC
+#undef FWD_INV_L
+#undef FWD_TC
+#undef FWD_PAD_MEL
+#undef FWD_LIM_A
+#undef FWD_LIM_B

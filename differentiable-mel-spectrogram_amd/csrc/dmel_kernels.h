@@ -411,6 +411,12 @@ struct FwdParams {
     float ch_val[kMaxChannels];
 };
 
+// dmel_fwd_len_kernel (csrc/dmel_fwd_len.hip): the scalar layer's launch over clips of per-clip lengths.  Clip b is x[b, :lengths[b]] (x keeps
+// its row stride L); its frames t >= lengths[b] / hop + 1 are pad frames; a length outside 1 ... L makes the clip's rows NaN.
+struct FwdLenParams : FwdParams {
+    const int* lengths;         // (B) device, read by the kernel when it runs
+};
+
 struct PrepParams {
     const float* x; float* psum; float2* win2;
     const float* const* x_ind;      // DMEL_FLAG_X_INDIRECT: the address of x is read from here (then x is nullptr), as in FwdParams
@@ -419,10 +425,13 @@ struct PrepParams {
     int win_half;
     float center;     // the window's centre in table coordinates: N/2, or (L/2 as an integer) + L/2 for the whole-clip window of an
                       // odd clip length L placed in an n_fft = 2L frame (time_frequency.py:24 centres at L/2 as a real number)
+    const int* lengths;   // (B) per-clip lengths or nullptr: the partial sums then stop at lengths[b] (a length outside 1 ... L counts as 1)
 };
 
 hipError_t launch_prep(const PrepParams& p, hipStream_t s);
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdParams& p, int grid, hipStream_t s);
+hipError_t launch_forward_len(int n_fft, int mode, int tiles_per_wg, const FwdLenParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
+hipError_t forward_len_prepare_attributes();   // ... and the dynamic-LDS limit of its instantiations
 int forward_tiles_per_wg(int n_fft, int mode, int batch, int tiles_per_clip);          // 1 or 2: what launch_forward should be given
 bool forward_two_tiles(int n_fft, int mode);          // the two-tiles-per-workgroup instantiation exists for this size and mode
 int forward_lds_bytes(int n_fft, int mode);

@@ -5,6 +5,7 @@
 //     dmel::forward(x, lambd, plan, flags, eps, want_tangent, lambd_sync, out_bf16) -> (out, tangent_buf)
 //     dmel::backward(grad_out, tangent_buf, plan)                                      -> d lambd
 //     dmel::mel_spectrogram(x, lambd, plan, flags, eps, lambd_sync, out_bf16)          -> out      (differentiable in lambd)
+//     dmel::mel_spectrogram_lengths(x, lengths, lambd, plan, flags, eps, lambd_sync, out_bf16) -> out   (clips x[b, :lengths[b]])
 //     dmel::mel_fbanks(n_freqs, f_min, f_max, n_mels, sample_rate)                     -> (n_freqs, n_mels) fp32
 // This file holds no arithmetic: it allocates outputs with at::empty on x's device, takes the current HIP stream
 // (forward on the caller's thread, backward on the autograd engine's thread: models.py:33, train.py:47) and calls
@@ -48,8 +49,9 @@ constexpr int64_t kAlign = 256;     // the scratch block sits behind the tangent
 // (out, tangent_buf): tangent_buf is a flat fp32 tensor holding the tangent (out.numel() values, empty when no tangent is
 // wanted) followed, 256-byte aligned, by the scratch block of this call (dmel_scratch_bytes): the ticket and partials of
 // the reduction in dmel::backward live there, so nothing plan-owned is shared between steps on different streams.
-std::tuple<at::Tensor, at::Tensor> dmel_forward_op(const at::Tensor& x, const at::Tensor& lambd, int64_t plan_h, int64_t flags,
-                                                   double eps, bool want_tangent, bool lambd_sync, bool out_bf16)
+// lengths != nullptr: clips of per-clip lengths (dmel_forward_lengths / dmel_forward_dev_lengths), an int32 (batch,) tensor on x's device
+std::tuple<at::Tensor, at::Tensor> forward_impl(const at::Tensor& x, const at::Tensor* lengths, const at::Tensor& lambd, int64_t plan_h,
+                                                int64_t flags, double eps, bool want_tangent, bool lambd_sync, bool out_bf16)
 {
     TORCH_CHECK(x.is_cuda(), "dmel::forward: x must be on the GPU (no CPU fallback)");
     // DMEL_FLAG_X_INDIRECT (dmel_amd.SlotInput): x is a (batch, n_points) VIEW with zero strides over a pointer cell -- its shape is the
@@ -78,7 +80,25 @@ std::tuple<at::Tensor, at::Tensor> dmel_forward_op(const at::Tensor& x, const at
     float* tangent = want_tangent ? reinterpret_cast<float*>(base) : nullptr;
     void* scratch = base + tan_bytes;
     const uint32_t f = (uint32_t)flags | (out_bf16 ? DMEL_FLAG_OUT_BF16 : 0u);
-    if (B > 0) {
+    if (lengths) {
+        // the values are the kernels' to read: shape, dtype and device only
+        TORCH_CHECK(lengths->dim() == 1 && lengths->size(0) == B && lengths->scalar_type() == at::kInt && lengths->is_contiguous(),
+                    "dmel::mel_spectrogram_lengths: lengths must be a contiguous int32 tensor of shape (", B, ",)");
+        TORCH_CHECK(lengths->device() == x.device(), "dmel::mel_spectrogram_lengths: lengths is on ", lengths->device(), " but x is on ", x.device());
+        TORCH_CHECK(!(f & DMEL_FLAG_FULL_WINDOW), "dmel::mel_spectrogram_lengths: per-clip lengths need optimized=True");
+    }
+    if (B > 0 && lengths) {
+        const int32_t* lp = lengths->data_ptr<int32_t>();
+        if (lambd_sync) {
+            TORCH_CHECK(lambd.is_cuda() || lambd.is_cpu(), "dmel::forward: lambd on an unsupported device");
+            const float lam = lambd.item<float>();
+            check(dmel_forward_lengths(plan, x.data_ptr<float>(), lp, (int32_t)B, lam, f, eps, out.data_ptr(), tangent, scratch, stream_of(x)));
+        } else {
+            TORCH_CHECK(lambd.device() == x.device(), "dmel::forward: lambd is on ", lambd.device(), " but x is on ", x.device());
+            check(dmel_forward_dev_lengths(plan, x.data_ptr<float>(), lp, (int32_t)B, lambd.data_ptr<float>(), f, eps, out.data_ptr(), tangent,
+                                           scratch, stream_of(x)));
+        }
+    } else if (B > 0) {
         if (lambd_sync) {
             TORCH_CHECK(lambd.is_cuda() || lambd.is_cpu(), "dmel::forward: lambd on an unsupported device");
             const float lam = lambd.item<float>();                       // the one host read (time_frequency.py:39)
@@ -96,6 +116,12 @@ std::tuple<at::Tensor, at::Tensor> dmel_forward_op(const at::Tensor& x, const at
     }
     (void)info;
     return {out, buf};
+}
+
+std::tuple<at::Tensor, at::Tensor> dmel_forward_op(const at::Tensor& x, const at::Tensor& lambd, int64_t plan_h, int64_t flags,
+                                                   double eps, bool want_tangent, bool lambd_sync, bool out_bf16)
+{
+    return forward_impl(x, nullptr, lambd, plan_h, flags, eps, want_tangent, lambd_sync, out_bf16);
 }
 
 at::Tensor dmel_backward_impl(const at::Tensor& grad_out, const at::Tensor& tangent_buf, int64_t plan_h, bool scalar_shape)
@@ -144,28 +170,54 @@ at::Tensor plan_reference(dmel_plan* plan)
 }
 
 // forward carries d out / d lambd (one trainable scalar: forward mode), backward is one dot product (train.py:47)
+at::Tensor save_forward(torch::autograd::AutogradContext* ctx, const std::tuple<at::Tensor, at::Tensor>& r, const at::Tensor& lambd, int64_t plan_h,
+                        bool want_tangent)
+{
+    ctx->saved_data["plan"] = plan_h;
+    if (want_tangent) ctx->saved_data["plan_ref"] = plan_reference(as_plan(plan_h));      // backward dereferences the plan
+    ctx->saved_data["want"] = want_tangent;
+    ctx->saved_data["lam_dim"] = (int64_t)lambd.dim();
+    ctx->saved_data["lam_dtype"] = (int64_t)lambd.scalar_type();
+    if (want_tangent) ctx->save_for_backward({std::get<1>(r)});
+    return std::get<0>(r);
+}
+
+at::Tensor lambd_grad(torch::autograd::AutogradContext* ctx, const torch::autograd::variable_list& grads)
+{
+    at::Tensor dl;
+    if (ctx->saved_data["want"].toBool() && grads[0].defined()) {
+        const auto saved = ctx->get_saved_variables();
+        dl = dmel_backward_impl(grads[0], saved[0], ctx->saved_data["plan"].toInt(), ctx->saved_data["lam_dim"].toInt() == 0);
+    }
+    return dl;
+}
+
 struct DmelFn : public torch::autograd::Function<DmelFn> {
     static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& x, const at::Tensor& lambd, int64_t plan_h,
                               int64_t flags, double eps, bool want_tangent, bool lambd_sync, bool out_bf16)
     {
-        auto r = dmel_forward_op(x, lambd, plan_h, flags, eps, want_tangent, lambd_sync, out_bf16);
-        ctx->saved_data["plan"] = plan_h;
-        if (want_tangent) ctx->saved_data["plan_ref"] = plan_reference(as_plan(plan_h));      // backward dereferences the plan
-        ctx->saved_data["want"] = want_tangent;
-        ctx->saved_data["lam_dim"] = (int64_t)lambd.dim();
-        ctx->saved_data["lam_dtype"] = (int64_t)lambd.scalar_type();
-        if (want_tangent) ctx->save_for_backward({std::get<1>(r)});
-        return std::get<0>(r);
+        return save_forward(ctx, dmel_forward_op(x, lambd, plan_h, flags, eps, want_tangent, lambd_sync, out_bf16), lambd, plan_h, want_tangent);
     }
 
     static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads)
     {
-        at::Tensor dl;
-        if (ctx->saved_data["want"].toBool() && grads[0].defined()) {
-            const auto saved = ctx->get_saved_variables();
-            dl = dmel_backward_impl(grads[0], saved[0], ctx->saved_data["plan"].toInt(), ctx->saved_data["lam_dim"].toInt() == 0);
-        }
-        return {at::Tensor(), dl, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+        return {at::Tensor(), lambd_grad(ctx, grads), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+    }
+};
+
+// per-clip lengths: the same node; pad frames carry a zero tangent, so the backward is the same dot product
+struct DmelLenFn : public torch::autograd::Function<DmelLenFn> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& x, const at::Tensor& lengths, const at::Tensor& lambd,
+                              int64_t plan_h, int64_t flags, double eps, bool want_tangent, bool lambd_sync, bool out_bf16)
+    {
+        return save_forward(ctx, forward_impl(x, &lengths, lambd, plan_h, flags, eps, want_tangent, lambd_sync, out_bf16), lambd, plan_h,
+                            want_tangent);
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grads)
+    {
+        return {at::Tensor(), at::Tensor(), lambd_grad(ctx, grads), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(),
+                at::Tensor()};
     }
 };
 
@@ -176,6 +228,13 @@ at::Tensor dmel_mel_spectrogram_op(const at::Tensor& x, const at::Tensor& lambd,
     return DmelFn::apply(x, lambd, plan_h, flags, eps, want, lambd_sync, out_bf16);
 }
 
+at::Tensor dmel_mel_spectrogram_lengths_op(const at::Tensor& x, const at::Tensor& lengths, const at::Tensor& lambd, int64_t plan_h, int64_t flags,
+                                           double eps, bool lambd_sync, bool out_bf16)
+{
+    const bool want = at::GradMode::is_enabled() && lambd.requires_grad();
+    return DmelLenFn::apply(x, lengths, lambd, plan_h, flags, eps, want, lambd_sync, out_bf16);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(dmel, m)
@@ -184,6 +243,7 @@ TORCH_LIBRARY(dmel, m)
     m.def("backward(Tensor grad_out, Tensor tangent_buf, int plan) -> Tensor");
     m.def("mel_spectrogram(Tensor x, Tensor lambd, int plan, int flags, float eps, bool lambd_sync, bool out_bf16) -> Tensor");
     m.def("mel_fbanks(int n_freqs, float f_min, float f_max, int n_mels, int sample_rate) -> Tensor");
+    m.def("mel_spectrogram_lengths(Tensor x, Tensor lengths, Tensor lambd, int plan, int flags, float eps, bool lambd_sync, bool out_bf16) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(dmel, CUDA, m)
@@ -195,5 +255,6 @@ TORCH_LIBRARY_IMPL(dmel, CUDA, m)
 TORCH_LIBRARY_IMPL(dmel, CompositeImplicitAutograd, m)
 {
     m.impl("mel_spectrogram", dmel_mel_spectrogram_op);
+    m.impl("mel_spectrogram_lengths", dmel_mel_spectrogram_lengths_op);
     m.impl("mel_fbanks", dmel_mel_fbanks_op);
 }

@@ -278,6 +278,17 @@ def _mel_op():
     return _MEL_OP
 
 
+_LEN_OP = None
+
+
+def _len_op():
+    """torch.ops.dmel.mel_spectrogram_lengths.default, resolved once."""
+    global _LEN_OP
+    if _LEN_OP is None:
+        _LEN_OP = capi.torch_ops().mel_spectrogram_lengths.default
+    return _LEN_OP
+
+
 def _to_f32(x: torch.Tensor) -> torch.Tensor:
     """The kernels compute in fp32.  The reference removes the clip mean in the INPUT dtype (models.py:38: ``x[idx] - torch.mean(x[idx])``):
     for fp64 clips (GaussPulse, datasets.py:33) that subtraction happens here, in fp64, BEFORE the cast -- a DC offset far above the
@@ -313,6 +324,14 @@ class MelSpectrogramLayer(nn.Module):
     spectrogram for the filterbank gradient instead of recomputing it in the backward.
 
     forward(x: (B, n_points)) -> (B, 1, n_mels, n_points // hop_length + 1) float32.
+
+    forward(x, lengths): zero-padded batches.  ``lengths`` is a (B,) integer tensor, ``1 <= lengths[b] <= n_points``; clip b is
+    ``x[b, :lengths[b]]``.  Its first ``frame_lengths(lengths)[b]`` frames are what the reference layer returns for that clip alone at
+    ``n_points = lengths[b]`` (the mean over the clip's own samples, the centred frames zero-padded past its end); the frames after
+    them are pad frames with the value of a frame of zero mel power (0, or ``log(0 + eps)`` with ``log=True``) and no gradient, and
+    their tiles cost no transform.  ``x[b, lengths[b]:]`` is never read.  The values are read by the kernels only (never by the host;
+    a captured step sees what the tensor holds when it replays): a length outside ``1 ... n_points`` makes that clip's rows NaN.
+    HTK bank with ``optimized=True`` only, no waveform gradient, clips that start at sample 0.
     """
 
     def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1,
@@ -409,8 +428,60 @@ class MelSpectrogramLayer(nn.Module):
         state["_fb_synced"] = {}
         return state
 
+    def frame_lengths(self, lengths: torch.Tensor) -> torch.Tensor:
+        """Valid frames per clip of ``forward(x, lengths)``: ``lengths // hop_length + 1`` (models.py:30 at ``n_points = lengths[b]``),
+        on the tensor's own device."""
+        return lengths // self.hop_length + 1
+
     # -- forward ------------------------------------------------------------------------------
-    def forward(self, x):
+    def _forward_lengths(self, x, lengths):
+        """forward(x, lengths): torch.ops.dmel.mel_spectrogram_lengths (the hot path's C++ autograd node over dmel_forward_dev_lengths, or
+        dmel_forward_lengths with lambd_sync).  Shape, dtype and device of ``lengths`` are checked here; its values never leave the device."""
+        if self.mel_fb is not None:
+            raise RuntimeError("per-clip lengths run the HTK bank only: learnable_fb=True does not take lengths")
+        if not self.optimized:
+            raise RuntimeError("per-clip lengths need optimized=True (the optimized=False branch's n_fft = 2 n_points depends on the clip length)")
+        if not torch.is_tensor(lengths):
+            raise TypeError(f"lengths must be a 1-D integer tensor, got {type(lengths).__name__}")
+        if lengths.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"lengths must hold int32 or int64 values, got {lengths.dtype}")
+        if lengths.dim() != 1 or lengths.shape[0] != x.shape[0]:
+            raise ValueError(f"lengths must have shape ({x.shape[0]},), got {tuple(lengths.shape)}")
+        if lengths.device.type == "cpu":
+            lengths = lengths.to(x.device)
+        elif lengths.device != x.device:
+            raise RuntimeError(f"lengths is on {lengths.device} but x is on {x.device}")
+        if lengths.dtype != torch.int32:
+            lengths = lengths.to(torch.int32)
+        if not lengths.is_contiguous():
+            lengths = lengths.contiguous()
+        flags = capi.DMEL_FLAG_LOG if self.log else 0
+        lam = self.lambd if self.lambd.dtype == torch.float32 else self.lambd.to(torch.float32)
+        bf16 = self.out_dtype == torch.bfloat16
+        if isinstance(x, SlotInput):
+            if self.lambd_sync:
+                raise RuntimeError("a SlotInput needs the default layer: HTK bank, optimized=True, lambd_sync=False")
+            if self.lambd.device != x.device:
+                raise RuntimeError(f"lambd is on {self.lambd.device} but the slot is on {x.device}; call layer.to(device)")
+            return _len_op()(x.view(), lengths, lam, self._plan_for(x.device).handle, flags | capi.DMEL_FLAG_X_INDIRECT, self.eps, False, bf16)
+        if not x.is_cuda:
+            raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
+        if x.requires_grad:
+            raise RuntimeError("per-clip lengths have no waveform gradient: pass x.detach()")
+        if self.lambd.device != x.device:
+            raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
+        xf = x if x.dtype == torch.float32 else x.to(torch.float32)      # (no fp64 pre-centring: the mean is the clip's own, taken by the kernel)
+        if not xf.is_contiguous():
+            xf = xf.contiguous()
+        return _len_op()(xf, lengths, lam, self._plan_for(x.device).handle, flags, self.eps, self.lambd_sync, bf16)
+
+    def forward(self, x, lengths=None):
+        if lengths is not None:
+            if x.dim() != 2:
+                raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
+            if x.shape[1] != self.n_points:
+                raise RuntimeError(f"input has {x.shape[1]} points, the layer was built for n_points={self.n_points}")
+            return self._forward_lengths(x, lengths)
         if x.dim() != 2:
             raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
         batch_size, n_points = x.shape
@@ -647,7 +718,9 @@ class MultiWindowMelSpectrogram(nn.Module):
         state["_plans"] = {}
         return state
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        if lengths is not None:
+            raise RuntimeError("MultiWindowMelSpectrogram does not take per-clip lengths (MelSpectrogramLayer does)")
         if isinstance(x, SlotInput):
             raise RuntimeError("MultiWindowMelSpectrogram does not take a SlotInput")
         if x.dim() != 2:
@@ -759,7 +832,9 @@ class SpectrogramLayer(nn.Module):
         state["_plans"] = {}
         return state
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        if lengths is not None:
+            raise RuntimeError("SpectrogramLayer does not take per-clip lengths (MelSpectrogramLayer does)")
         if x.dim() != 2:
             raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
         if not x.is_cuda:
@@ -793,8 +868,10 @@ DifferentiableMelSpectrogram = MelSpectrogramLayer
 
 
 def dmel_log_mel(x, lambd, n_mels, sample_rate, hop_length, f_min=0.0, f_max=None, normalize_window=False,
-                 log=True, eps=1e-10, _plan_cache={}):
+                 log=True, eps=1e-10, _plan_cache={}, *, lengths=None):
     """Functional form: log-mel (or mel) of x with window width ``lambd`` (a tensor that may require grad)."""
+    if lengths is not None:
+        raise RuntimeError("dmel_log_mel does not take per-clip lengths (MelSpectrogramLayer does)")
     key = (x.device.index, x.shape[1], hop_length, n_mels, sample_rate, float(f_min), f_max, bool(normalize_window))
     plan = _plan_cache.get(key)
     if plan is None:

@@ -199,6 +199,21 @@ dmel_status dmel_forward_dev_fixed(dmel_plan* plan, const float* x, int32_t batc
  * from 32 to 16384, not with DMEL_FLAG_FULL_WINDOW; spec = NULL is plain dmel_forward_dev_fixed. */
 dmel_status dmel_forward_dev_fixed_spec(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft,
                                         uint32_t flags, double eps, void* out, float* tangent, float* spec, void* scratch, void* stream);
+/* Per-clip lengths (zero-padded batches): dmel_forward_scratch / dmel_forward_dev over clips x[b, :lengths[b]].  lengths: device, `batch`
+ * int32 values, read by the kernels when they run (never by the host: a captured forward sees what the buffer holds at replay).  Clip b
+ * is computed as a plan with n_points = lengths[b] would compute it (its own mean; the centred frames zero-padded past lengths[b]) for
+ * its frames t < lengths[b] / hop_length + 1; the frames after them are pad frames -- the value of a frame of zero mel power (0, or the
+ * kernel's log(0 + eps) with DMEL_FLAG_LOG) and a zero tangent -- and tiles of pad frames are not transformed.  x[b, lengths[b]:] is
+ * never read.  A length outside 1 ... n_points makes that clip's rows (and its tangent) NaN; the other clips are unaffected.
+ * The tangent carries the usual meaning, so dmel_backward_scratch on it gives d loss / d lambd.  Flags: DMEL_FLAG_LOG, DMEL_FLAG_OUT_BF16,
+ * DMEL_FLAG_X_INDIRECT.  The HTK bank and n_fft 32 ... 16384 only: dmel_forward_lengths refuses a lambd outside that range
+ * (DMEL_ERR_UNSUPPORTED); dmel_forward_dev_lengths clamps its launches to it (a forward no launch covered is NaN and the next call
+ * returns DMEL_ERR_LAMBD_TRACKING, as dmel_forward_dev).  Scratch as dmel_forward_scratch / dmel_forward_dev.  NULL handles and pointers:
+ * DMEL_ERR_INVALID_ARGUMENT before any device call. */
+dmel_status dmel_forward_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, float lambd, uint32_t flags,
+                                 double eps, void* out, float* tangent, void* scratch, void* stream);
+dmel_status dmel_forward_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                     uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream);
 
 /* Every forward that EXECUTES on a plan (an eager dmel_forward_dev, or one replay of a captured one) draws the next
  * EXECUTION NUMBER from a device counter and reports (number, lambd as it read it) into a pinned ring of 64 entries. */
