@@ -299,6 +299,17 @@ def _to_f32(x: torch.Tensor) -> torch.Tensor:
     return x.to(torch.float32)
 
 
+def _to_f32_lengths(x: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+    """_to_f32 for forward(x, lengths): an fp64 clip loses its own mean, over ``x[b, :lengths[b]]``, in fp64 before the cast (a masked sum
+    divided by the length, on the device: no host read, so a captured step stays capturable).  Samples past a clip are masked out of the
+    sum (NaN or inf there reaches no output); an invalid length changes only its own clip, which the kernel makes NaN."""
+    if x.dtype == torch.float64:
+        inside = torch.arange(x.shape[1], device=x.device)[None, :] < lengths[:, None]
+        mean = torch.where(inside, x, 0.0).sum(dim=1, keepdim=True) / lengths.clamp(min=1)[:, None].to(torch.float64)
+        x = x - mean
+    return x.to(torch.float32)
+
+
 class MelSpectrogramLayer(nn.Module):
     """Differentiable (log-)Mel spectrogram with a trainable Gaussian window width.
 
@@ -330,7 +341,9 @@ class MelSpectrogramLayer(nn.Module):
     ``n_points = lengths[b]`` (the mean over the clip's own samples, the centred frames zero-padded past its end); the frames after
     them are pad frames with the value of a frame of zero mel power (0, or ``log(0 + eps)`` with ``log=True``) and no gradient, and
     their tiles cost no transform.  ``x[b, lengths[b]:]`` is never read.  The values are read by the kernels only (never by the host;
-    a captured step sees what the tensor holds when it replays): a length outside ``1 ... n_points`` makes that clip's rows NaN.
+    a captured step sees what the tensor holds when it replays): a length outside ``1 ... n_points`` makes that clip's rows NaN (int64
+    lengths are clamped on the device before they are narrowed to int32, so no value wraps into the valid range).  fp64 clips lose their
+    own mean in fp64 before the cast to fp32, as ``forward(x)`` does.
     HTK bank with ``optimized=True`` only, no waveform gradient, clips that start at sample 0.
     """
 
@@ -452,7 +465,8 @@ class MelSpectrogramLayer(nn.Module):
         elif lengths.device != x.device:
             raise RuntimeError(f"lengths is on {lengths.device} but x is on {x.device}")
         if lengths.dtype != torch.int32:
-            lengths = lengths.to(torch.int32)
+            # int64 values clamped on the device before the narrowing: a length such as 2**32 + 4000 must stay invalid (NaN), not wrap to 4000
+            lengths = lengths.clamp(0, self.n_points + 1).to(torch.int32)
         if not lengths.is_contiguous():
             lengths = lengths.contiguous()
         flags = capi.DMEL_FLAG_LOG if self.log else 0
@@ -470,7 +484,7 @@ class MelSpectrogramLayer(nn.Module):
             raise RuntimeError("per-clip lengths have no waveform gradient: pass x.detach()")
         if self.lambd.device != x.device:
             raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
-        xf = x if x.dtype == torch.float32 else x.to(torch.float32)      # (no fp64 pre-centring: the mean is the clip's own, taken by the kernel)
+        xf = x if x.dtype == torch.float32 else _to_f32_lengths(x, lengths)
         if not xf.is_contiguous():
             xf = xf.contiguous()
         return _len_op()(xf, lengths, lam, self._plan_for(x.device).handle, flags, self.eps, self.lambd_sync, bf16)

@@ -115,6 +115,7 @@ ORACLE = [
 @pytest.mark.parametrize("case", range(len(ORACLE) + 1), ids=["nfft512", "hop_gt_half", "nfft1024_many_tiles", "audio_mnist"])
 def test_against_the_oracle_clip_by_clip(case):
     from oracle import dmel_oracle as O
+    from test_hip_parity import assert_parity
     if case < len(ORACLE):
         lam, L, hop, M, sr, lens = ORACLE[case]
     else:
@@ -134,6 +135,7 @@ def test_against_the_oracle_clip_by_clip(case):
         tb = lb // hop + 1
         yr, tr = O.forward(x_np[b:b + 1, :lb], lam, hop, M, sr)
         worst = max(worst, _rel_err(y[b:b + 1, :, :, :tb], yr))
+        assert_parity(f"lengths_oracle/case{case}/b{b}_L{lb}/mel", y[b:b + 1, :, :, :tb], yr, allow_floor=False)     # every element, no floor
         d_ref += O.backward(g_np[b:b + 1, :, :, :tb], tr)
     assert worst <= 1e-4, worst
     assert abs(float(d) - d_ref) <= 1e-4 * abs(d_ref), (float(d), d_ref)
