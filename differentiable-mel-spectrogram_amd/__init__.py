@@ -11,12 +11,13 @@ from __future__ import annotations
 
 import importlib
 
-__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "capi", "synth", "dist",
+__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "capi", "synth", "dist",
            "nets", "panns", "graph", "optim"]
 
 _LAZY = {
     "MelSpectrogramLayer": ("layer", "MelSpectrogramLayer"),
     "MultiWindowMelSpectrogram": ("layer", "MultiWindowMelSpectrogram"),
+    "BandSplitMelSpectrogram": ("layer", "BandSplitMelSpectrogram"),
     "DifferentiableMelSpectrogram": ("layer", "DifferentiableMelSpectrogram"),
     "dmel_log_mel": ("layer", "dmel_log_mel"),
     "SpectrogramLayer": ("layer", "SpectrogramLayer"),

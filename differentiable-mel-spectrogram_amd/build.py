@@ -15,7 +15,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdmel_hip.so")
 TORCH_LIB_PATH = os.path.join(PKG_DIR, "libdmel_torch.so")
 OBJ_DIR = os.path.join(PKG_DIR, "build")
-SOURCES = ["dmel_fwd.hip", "dmel_fwd_len.hip", "dmel_aux.hip", "dmel_big.hip", "dmel_xgrad.hip", "dmel_api.cpp", "dmel_comm.cpp"]
+SOURCES = ["dmel_fwd.hip", "dmel_fwd_len.hip", "dmel_fwd_band.hip", "dmel_aux.hip", "dmel_big.hip", "dmel_xgrad.hip", "dmel_api.cpp", "dmel_comm.cpp"]
 HEADERS = [os.path.join(CSRC, "dmel_kernels.h"), os.path.join(CSRC, "dmel_fwd_body.inc"), os.path.join(CSRC, "dmel_fwd_log.h"),os.path.join(CSRC, "dmel_xgrad_wave_body.inc"), os.path.join(CSRC, "dmel_ldsfft.h"), os.path.join(CSRC, "dmel_wavefft.h"), os.path.join(os.path.dirname(PKG_DIR), "include", "dmel.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
@@ -34,7 +34,7 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-# csrc/dmel_fwd.hip and csrc/dmel_fwd_len.hip are compiled FWD_PARTS times each (-DDMEL_FWD_SPLIT -DDMEL_FWD_PART=k): their large
+# csrc/dmel_fwd.hip, csrc/dmel_fwd_len.hip and csrc/dmel_fwd_band.hip are compiled FWD_PARTS times each (-DDMEL_FWD_SPLIT -DDMEL_FWD_PART=k): their large
 # instantiations in parallel
 FWD_PARTS = 4
 
@@ -44,7 +44,7 @@ def _units():
     for src in SOURCES:
         sp = os.path.join(CSRC, src)
         stem = os.path.splitext(src)[0]
-        if src in ("dmel_fwd.hip", "dmel_fwd_len.hip"):
+        if src in ("dmel_fwd.hip", "dmel_fwd_len.hip", "dmel_fwd_band.hip"):
             for k in range(FWD_PARTS):
                 yield sp, os.path.join(OBJ_DIR, f"{stem}_part{k}.o"), ["-DDMEL_FWD_SPLIT", f"-DDMEL_FWD_PART={k}"]
         else:

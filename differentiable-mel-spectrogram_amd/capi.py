@@ -44,6 +44,7 @@ SYMBOLS = (
     "dmel_mailbox_set_spin_limit", "dmel_mailbox_set_timeout_ms", "dmel_plan_is_live", "dmel_lambd_ring_size", "dmel_spectrogram_ex_dev", "dmel_forward_dev_fixed_spec", "dmel_backward_fb_saved", "dmel_backward_fb_saved_dl", "dmel_backward_x_dev", "dmel_backward_x_spec_dev", "dmel_plan_attach_mailbox", "dmel_backward_x_spec", "dmel_plan_attach_adam",
     "dmel_scratch_bytes_multi", "dmel_forward_multi", "dmel_forward_multi_dev", "dmel_backward_multi", "dmel_plan_lambd_status_channel",
     "dmel_decide_launch_multi", "dmel_backward_x_multi", "dmel_backward_x_multi_dev", "dmel_plan_last_multi_launch",
+    "dmel_forward_band", "dmel_forward_band_dev", "dmel_backward_band",
     "dmel_forward_lengths", "dmel_forward_dev_lengths",
 )
 TORCH_LIB_PATH = os.path.join(_PKG_DIR, "libdmel_torch.so")
@@ -202,6 +203,12 @@ def load():
     L.dmel_backward_x_multi_dev.restype = C.c_int
     L.dmel_plan_last_multi_launch.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
     L.dmel_plan_last_multi_launch.restype = C.c_int
+    L.dmel_forward_band.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
+    L.dmel_forward_band.restype = C.c_int
+    L.dmel_forward_band_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
+    L.dmel_forward_band_dev.restype = C.c_int
+    L.dmel_backward_band.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp]
+    L.dmel_backward_band.restype = C.c_int
     L.dmel_mailbox_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(vp), C.c_char_p]
     L.dmel_mailbox_create.restype = C.c_int
     L.dmel_mailbox_connect.argtypes = [vp, C.c_char_p]
@@ -480,6 +487,28 @@ class Plan:
                        accumulate: bool = False, grad_bf16: bool = False):
         _check(load().dmel_backward_multi(self._h, grad_ptr, DMEL_DTYPE_BF16 if grad_bf16 else DMEL_DTYPE_F32, tangent_ptr, int(batch),
                                           int(channels), int(accumulate), dlambd_ptr, scratch_ptr, stream))
+
+    # -- the band-split layer (dmel_forward_band*, dmel_backward_band): one (B, 1, M, T) image, channel k owns rows edges[k] ... edges[k + 1] - 1 --
+    def forward_band(self, x_ptr: int, batch: int, lambd, edges, out_ptr: int, tangent_ptr: int | None, log: bool, eps: float, stream: int,
+                     scratch_ptr: int, out_bf16: bool = False):
+        """lambd: the K host values; edges: K + 1 host integers"""
+        lam = (C.c_float * len(lambd))(*[float(v) for v in lambd])
+        ed = (C.c_int32 * len(edges))(*[int(v) for v in edges])
+        flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
+        _check(load().dmel_forward_band(self._h, x_ptr, batch, lam, len(lambd), ed, flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream))
+
+    def forward_band_dev(self, x_ptr: int, batch: int, lambd_ptr: int, edges, out_ptr: int, tangent_ptr: int | None, log: bool,
+                         eps: float, stream: int, scratch_ptr: int, out_bf16: bool = False):
+        ed = (C.c_int32 * len(edges))(*[int(v) for v in edges])
+        flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
+        _check(load().dmel_forward_band_dev(self._h, x_ptr, batch, lambd_ptr, len(edges) - 1, ed, flags, float(eps), out_ptr, tangent_ptr,
+                                            scratch_ptr, stream))
+
+    def backward_band(self, grad_ptr: int, tangent_ptr: int, batch: int, edges, dlambd_ptr: int, stream: int, scratch_ptr: int,
+                      accumulate: bool = False, grad_bf16: bool = False):
+        ed = (C.c_int32 * len(edges))(*[int(v) for v in edges])
+        _check(load().dmel_backward_band(self._h, grad_ptr, DMEL_DTYPE_BF16 if grad_bf16 else DMEL_DTYPE_F32, tangent_ptr, int(batch),
+                                         len(edges) - 1, ed, int(accumulate), dlambd_ptr, scratch_ptr, stream))
 
     def backward_x_multi(self, x_ptr: int, batch: int, lambd, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int, log: bool, stream: int):
         """dmel_backward_x_multi: grad_x = sum over channels (ascending) of the scalar layer's waveform gradient; lambd: the K host values;

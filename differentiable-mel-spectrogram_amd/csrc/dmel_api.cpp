@@ -781,7 +781,8 @@ dmel_status big_tables_for(dmel_plan* pl, int N, dmel_plan::BigTab* out, const f
 // `lam` says where lambd comes from and whether the kernels check it against N (dmel_kernels.h); `sc` is the scratch of
 // this call.  Shared by every entry point; the plan mutex is held by the caller.
 // one launch of the multi-window layer: `count` channels (nibbles of `list`, with their lambd roles in `roles`) of an output with `ch_out` channels
-struct MultiLaunch { int ch_out = 0, count = 0; unsigned list = 0, roles = 0; float vals[dmel::kMaxChannels] = {}; };
+// (edges != nullptr: the band-split layer -- ch_out = 1, channel c writes rows [edges[c], edges[c + 1]) of the one image: dmel_fwd_band_kernel)
+struct MultiLaunch { int ch_out = 0, count = 0; unsigned list = 0, roles = 0; float vals[dmel::kMaxChannels] = {}; const int32_t* edges = nullptr; int channels = 0; };
 
 dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dmel::LamArgs lam, unsigned flags, double eps,
                              float* out, float* tangent, int mode, int remove_dc, const Scratch& sc, hipStream_t s, int win_half,
@@ -970,7 +971,7 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     static const int force_tpw = std::getenv("DMEL_TILES_PER_WG") ? std::atoi(std::getenv("DMEL_TILES_PER_WG")) : 0;   // diagnostics
     int tpw = dmel::forward_tiles_per_wg(N, mode, batch, fp.tiles_per_clip);
     if (force_tpw == 1 || (force_tpw == 2 && dmel::forward_two_tiles(N, mode))) tpw = force_tpw;
-    if (hsplit || lengths) tpw = 1;                  // (dmel_fwd_len_kernel: one tile per workgroup)
+    if (hsplit || lengths || (ml && ml->edges)) tpw = 1;                  // (dmel_fwd_len_kernel, dmel_fwd_band_kernel: one tile per workgroup)
     fp.wgs_per_clip = (fp.tiles_per_clip + tpw - 1) / tpw;
     long long grid = (long long)batch * fp.wgs_per_clip;
     if (ml) {
@@ -985,6 +986,11 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
         static_cast<dmel::FwdParams&>(lp) = fp;
         lp.lengths = lengths;
         DMEL_HIP(dmel::launch_forward_len(N, mode, tpw, lp, (int)grid, s));
+    } else if (ml && ml->edges) {
+        dmel::FwdBandParams bp{};
+        static_cast<dmel::FwdParams&>(bp) = fp;
+        for (int c = 0; c <= dmel::kMaxChannels; ++c) bp.band_edges[c] = ml->edges[std::min(c, ml->channels)];
+        DMEL_HIP(dmel::launch_forward_band(N, mode, tpw, bp, (int)grid, s));
     } else {
         DMEL_HIP(dmel::launch_forward(N, mode, tpw, fp, (int)grid, s));
     }
@@ -1271,6 +1277,7 @@ dmel_status dmel_plan_create(const dmel_config* cfg, dmel_plan** plan)
         return fail(DMEL_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", libdmel_hip is built for gfx950 only");
     DMEL_HIP(dmel::forward_prepare_attributes());
     DMEL_HIP(dmel::forward_len_prepare_attributes());
+    DMEL_HIP(dmel::forward_band_prepare_attributes());
     DMEL_HIP(dmel::xgrad_prepare_attributes());
     DMEL_HIP(dmel::big_prepare_attributes());
     dmel_plan* pl = new (std::nothrow) dmel_plan();
@@ -1779,7 +1786,7 @@ bool multi_in_range(int n) { return n >= dmel::kMinFastNfft && n <= dmel::kMaxFa
 // among the launches that carry it
 dmel_status issue_multi(dmel_plan* pl, const float* x, int batch, int channels, const int* ns, const uint32_t* mask, int nl,
                         const dmel::LamArgs& base, const float* vals, uint32_t flags, double eps, void* out, float* tangent,
-                        const Scratch& sc, hipStream_t s)
+                        const Scratch& sc, hipStream_t s, const int32_t* edges = nullptr)
 {
     int first[dmel::kMaxChannels], last[dmel::kMaxChannels];
     for (int c = 0; c < channels; ++c) { first[c] = -1; last[c] = -1; }
@@ -1792,7 +1799,7 @@ dmel_status issue_multi(dmel_plan* pl, const float* x, int batch, int channels, 
     dmel_plan_info primary_info = pl->info;
     for (int i = 0; i < nl; ++i) {
         MultiLaunch ml;
-        ml.ch_out = channels;
+        ml.ch_out = edges ? 1 : channels; ml.edges = edges; ml.channels = channels;
         for (int c = 0; c < dmel::kMaxChannels; ++c) ml.vals[c] = c < channels && vals ? vals[c] : 0.f;
         for (int c = 0; c < channels; ++c) {
             if (!(mask[i] >> c & 1u)) continue;
@@ -1813,10 +1820,29 @@ dmel_status issue_multi(dmel_plan* pl, const float* x, int batch, int channels, 
     return DMEL_OK;
 }
 
-}  // namespace
+// 0 = e_0 < e_1 < ... < e_K (every group non-empty); e_K = n_mels is checked against the plan by the caller
+dmel_status check_band_edges(const int32_t* edges, int channels, const char* who)
+{
+    if (channels < 1 || channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": channels must be 1 ... 8");
+    if (!edges) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges is NULL");
+    if (edges[0] != 0) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges must start at 0");
+    for (int c = 0; c < channels; ++c)
+        if (edges[c + 1] <= edges[c])
+            return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges must be strictly ascending (group " + std::to_string(c) + " is empty)");
+    return DMEL_OK;
+}
 
-dmel_status dmel_forward_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, uint32_t flags,
-                               double eps, void* out, float* tangent, void* scratch, void* stream)
+dmel_status check_band_plan(const dmel_plan* pl, const int32_t* edges, int channels, const char* who)
+{
+    if (!pl) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
+    if (edges[channels] != pl->cfg.n_mels)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges must end at n_mels = " + std::to_string(pl->cfg.n_mels) + " (got " +
+                    std::to_string(edges[channels]) + ")");
+    return DMEL_OK;
+}
+
+dmel_status forward_multi_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, uint32_t flags,
+                               double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges)
 {
     dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, scratch);
     if (st != DMEL_OK) return st;
@@ -1839,11 +1865,11 @@ dmel_status dmel_forward_multi(dmel_plan* plan, const float* x, int32_t batch, c
     base.n_expected = 0;                          // every n_fft was derived from these very values
     base.dot_counter = sc.counter;
     return issue_multi(plan, x, batch, channels, ns, mask, nl, base, lambd_host, flags, eps, out, tangent, sc,
-                       reinterpret_cast<hipStream_t>(stream));
+                       reinterpret_cast<hipStream_t>(stream), edges);
 }
 
-dmel_status dmel_forward_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
-                                   double eps, void* out, float* tangent, void* scratch, void* stream)
+dmel_status forward_multi_dev_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
+                                   double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges)
 {
     dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, scratch);
     if (st != DMEL_OK) return st;
@@ -1938,7 +1964,76 @@ dmel_status dmel_forward_multi_dev(dmel_plan* plan, const float* x, int32_t batc
     base.exec_counter = plan->multi_exec; base.handled = sc.handled;
     base.host_seen = plan->multi_words; base.host_error = plan->multi_words + dmel::kLamRing;
     base.dot_counter = sc.counter;
-    return issue_multi(plan, x, batch, channels, ns, mask, nl, base, nullptr, flags, eps, out, tangent, sc, s);
+    return issue_multi(plan, x, batch, channels, ns, mask, nl, base, nullptr, flags, eps, out, tangent, sc, s, edges);
+}
+
+}  // namespace
+
+dmel_status dmel_forward_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, uint32_t flags,
+                               double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    return forward_multi_impl(plan, x, batch, lambd_host, channels, flags, eps, out, tangent, scratch, stream, nullptr);
+}
+
+dmel_status dmel_forward_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
+                                   double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    return forward_multi_dev_impl(plan, x, batch, lambd_dev, channels, flags, eps, out, tangent, scratch, stream, nullptr);
+}
+
+// ---- the band-split layer: K window widths inside ONE image, a width per group of mel bands -----------------------------------------
+// The multi-window layer's launches (one per distinct n_fft, the same per-channel lambd words, guards and scratch) through dmel_fwd_band_kernel.
+// band_edges are host integers, validated and taken by value (they travel in the kernel arguments).
+dmel_status dmel_forward_band(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, const int32_t* band_edges,
+                              uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    dmel_status st = check_band_edges(band_edges, channels, "dmel_forward_band");
+    if (st != DMEL_OK) return st;
+    if ((st = check_band_plan(plan, band_edges, channels, "dmel_forward_band")) != DMEL_OK) return st;
+    int32_t edges[dmel::kMaxChannels + 1];
+    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
+    return forward_multi_impl(plan, x, batch, lambd_host, channels, flags, eps, out, tangent, scratch, stream, edges);
+}
+
+dmel_status dmel_forward_band_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, const int32_t* band_edges,
+                                  uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    dmel_status st = check_band_edges(band_edges, channels, "dmel_forward_band_dev");
+    if (st != DMEL_OK) return st;
+    if ((st = check_band_plan(plan, band_edges, channels, "dmel_forward_band_dev")) != DMEL_OK) return st;
+    int32_t edges[dmel::kMaxChannels + 1];
+    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
+    return forward_multi_dev_impl(plan, x, batch, lambd_dev, channels, flags, eps, out, tangent, scratch, stream, edges);
+}
+
+dmel_status dmel_backward_band(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int32_t batch, int32_t channels,
+                               const int32_t* band_edges, int32_t accumulate, float* dlambd, void* scratch, void* stream)
+{
+    dmel_status st = check_band_edges(band_edges, channels, "dmel_backward_band");
+    if (st != DMEL_OK) return st;
+    if ((st = check_band_plan(plan, band_edges, channels, "dmel_backward_band")) != DMEL_OK) return st;
+    if (batch < 0 || !dlambd || !scratch || (batch > 0 && (!grad_out || !tangent)))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: bad arguments");
+    if (grad_dtype != DMEL_DTYPE_F32 && grad_dtype != DMEL_DTYPE_BF16)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
+    if (plan->mailbox || plan->fused_adam.param)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: a plan with an attached mailbox or fused Adam serves the scalar layer only");
+    { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
+    if ((long long)batch * plan->cfg.n_mels * plan->T >= (1LL << 31)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: more than 2^31 elements");
+    std::lock_guard<std::mutex> lock(plan->mu);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const Scratch sc = carve(scratch, channels);
+    dmel::DotBandParams dp{};
+    dp.g = grad_out; dp.t = tangent; dp.partials = sc.partials; dp.counter = sc.counter; dp.result = dlambd;
+    dp.g_bf16 = grad_dtype == DMEL_DTYPE_BF16; dp.batch = batch; dp.channels = channels; dp.M = plan->cfg.n_mels; dp.T = plan->T;
+    dp.accumulate = accumulate;
+    for (int c = 0; c <= dmel::kMaxChannels; ++c) dp.edges[c] = band_edges[std::min(c, channels)];
+    // at most kDotMaxBlocks partials in all (the ticket tree's layout), dealt to the groups in proportion to their rows
+    dmel::dot_band_deal(dp.edges, channels, batch, plan->T, dp.blocks);
+    const size_t m0 = prof_mark(plan, s);
+    DMEL_HIP(dmel::launch_dot_band(dp, s));
+    prof_span(plan, m0, prof_mark(plan, s), 2);
+    return DMEL_OK;
 }
 
 dmel_status dmel_backward_multi(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int32_t batch, int32_t channels,

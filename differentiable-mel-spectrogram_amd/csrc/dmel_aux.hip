@@ -317,6 +317,99 @@ hipError_t launch_dot_multi(const void* g, int g_bf16, const float* t, int batch
     return hipGetLastError();
 }
 
+// ---- the band-split layer's backward: K gradients in one launch over ONE (B, 1, M, T) image -----------------------------------
+// dmel_dot_multi_kernel with rows instead of channels: group c is rows [edges[c], edges[c + 1]) of every clip -- (e_c+1 - e_c) T contiguous
+// elements per clip, taken 4 at a time when T is a multiple of 4 --, its workgroups are blocks[c] consecutive ones of the grid (dealt by the
+// host in proportion to the row counts), each publishes one fp64 partial and goes through the same two-level ticket tree; the last one adds
+// each group's partials in index order (the same bits every run) and writes all K results.
+template <bool GBF16>
+__global__ void __launch_bounds__(kDotThreads) dmel_dot_band_kernel(DotBandParams p)
+{
+    __shared__ double red4[kDotThreads / 16];
+    __shared__ int is_last;
+    const int tid = threadIdx.x;
+    // this workgroup's group and its index inside it (uniform: scalar compares over at most kMaxChannels prefix sums)
+    int c = 0, first = 0;
+    while (c + 1 < p.channels && (int)blockIdx.x >= first + p.blocks[c]) { first += p.blocks[c]; ++c; }
+    const int j = blockIdx.x - first, bpc = p.blocks[c];
+    const unsigned span = (unsigned)(p.edges[c + 1] - p.edges[c]) * (unsigned)p.T;      // elements of this group per clip
+    const long long clip = (long long)p.M * p.T, off = (long long)p.edges[c] * p.T;
+    const unsigned stride = (unsigned)bpc * kDotThreads;
+    double acc = 0.0;
+    const uintptr_t galign = GBF16 ? 7 : 15;
+    const bool vec = (p.T & 3) == 0 && ((reinterpret_cast<uintptr_t>(p.g) & galign) | (reinterpret_cast<uintptr_t>(p.t) & 15)) == 0;
+    if (vec) {
+        const unsigned span4 = span / 4, n4 = (unsigned)p.batch * span4;          // (host: batch M T < 2^31)
+        const float4* t4 = reinterpret_cast<const float4*>(p.t);
+        for (unsigned i = (unsigned)j * kDotThreads + tid; i < n4; i += stride) {
+            const unsigned b = i / span4, r = i - b * span4;
+            const long long e = ((long long)b * clip + off) / 4 + r;
+            const float4 a = load_g4<GBF16>(p.g, e), v = t4[e];
+            acc += ((double)a.x * (double)v.x + (double)a.y * (double)v.y) + ((double)a.z * (double)v.z + (double)a.w * (double)v.w);
+        }
+    } else {
+        const unsigned n1 = (unsigned)p.batch * span;
+        for (unsigned i = (unsigned)j * kDotThreads + tid; i < n1; i += stride) {
+            const unsigned b = i / span, r = i - b * span;
+            const long long e = (long long)b * clip + off + r;
+            acc += (double)load_g1<GBF16>(p.g, e) * (double)p.t[e];
+        }
+    }
+    const double bsum = block_sum(acc, red4);
+    if (tid == 0) {
+        __hip_atomic_store(&p.partials[blockIdx.x], bsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // the ticket tree of dmel_dot_kernel, over the whole grid
+        const unsigned grp = blockIdx.x / kDotGroup, ngroups = (gridDim.x + kDotGroup - 1) / kDotGroup;
+        const unsigned gsize = grp + 1 < ngroups ? (unsigned)kDotGroup : gridDim.x - grp * kDotGroup;
+        unsigned* gc = dot_group_counters(p.counter) + 16 * grp;
+        bool last = false;
+        if (__hip_atomic_fetch_add(gc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1u) {
+            __hip_atomic_store(gc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = __hip_atomic_fetch_add(p.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ngroups - 1u;
+        }
+        is_last = last;
+    }
+    __syncthreads();
+    if (!is_last) return;
+    int q0 = 0;
+    for (int k = 0; k < p.channels; ++k) {
+        double sum = 0.0;
+        for (int q = tid; q < p.blocks[k]; q += kDotThreads)
+            sum += __hip_atomic_load(&p.partials[q0 + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        q0 += p.blocks[k];
+        const double total = block_sum(sum, red4);
+        if (tid == 0) p.result[k] = p.accumulate ? (float)((double)p.result[k] + total) : (float)total;
+        __syncthreads();                                   // red4 is reused by the next group
+    }
+    if (tid == 0) __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// workgroups per group: 4096 elements per workgroup and tensor as dot_blocks_for, at most kDotMaxBlocks in all, dealt in proportion to the
+// groups' row counts (rounded down, at least one each: the sum stays inside the budget)
+void dot_band_deal(const int* edges, int channels, int batch, int T, int* blocks)
+{
+    const int M = edges[channels];
+    const long long count = (long long)batch * M * T;
+    long long total = (count + 4095) / 4096;
+    if (total > kDotMaxBlocks) total = kDotMaxBlocks;
+    if (total < channels) total = channels;
+    const long long spare = total - channels;
+    for (int c = 0; c < channels; ++c) blocks[c] = 1 + (int)(spare * (edges[c + 1] - edges[c]) / (M > 0 ? M : 1));
+}
+
+hipError_t launch_dot_band(const DotBandParams& p, hipStream_t s)
+{
+    if (p.channels < 1 || p.channels > kMaxChannels) return hipErrorInvalidValue;
+    int total = 0;
+    for (int c = 0; c < p.channels; ++c) { if (p.blocks[c] < 1) return hipErrorInvalidValue; total += p.blocks[c]; }
+    if (total > kDotMaxBlocks) return hipErrorInvalidValue;
+    const dim3 gr(total), bl(kDotThreads);
+    if (p.g_bf16) hipLaunchKernelGGL((dmel_dot_band_kernel<true>), gr, bl, 0, s, p);
+    else hipLaunchKernelGGL((dmel_dot_band_kernel<false>), gr, bl, 0, s, p);
+    return hipGetLastError();
+}
+
 // ---- filterbank tables from a device matrix -----------------------------------------------------------------
 // grid.x = runs (one (group, wave, run) entry of tile_ranges each) + the workgroups that copy / transpose the matrix (one
 // workgroup doing all of it took 64 us for 513 x 128 entries: the longest kernel of a trainable-filterbank step)

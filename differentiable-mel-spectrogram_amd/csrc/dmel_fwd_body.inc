@@ -2,12 +2,19 @@
 // makes dmel_fwd_multi_kernel (the multi-window layer, FwdParams::ch_out > 0).  dmel_fwd_len.hip includes it a third time with DMEL_FWD_LEN = 1:
 // dmel_fwd_len_kernel, the scalar layer over clips of per-clip lengths (FwdLenParams).  The FWD_* names below expand, for the scalar kernel, to
 // exactly the tokens it was written with, so that its code does not change.
+// dmel_fwd_band.hip includes it with DMEL_FWD_MULTI = 1 and DMEL_FWD_BAND = 1: dmel_fwd_band_kernel (BandSplitMelSpectrogram, FwdBandParams) -- the
+// multi-window kernel's channel addressing, but all channels write ONE (B, 1, M, T) image and channel c only its rows [e_c, e_c+1): the
+// contraction work of the other rows is skipped where a whole tile / phase lies outside them and every store site is confined to them.
 #if DMEL_FWD_MULTI
 #define FWD_BO bo
 #define FWD_LAM lam_args
 #define FWD_WIN2 win2
 #define FWD_LEADER grid_leader
+#if DMEL_FWD_BAND
+#define FWD_KERNEL dmel_fwd_band_kernel
+#else
 #define FWD_KERNEL dmel_fwd_multi_kernel
+#endif
 #else
 #define FWD_BO b
 #define FWD_LAM p.lam
@@ -30,7 +37,11 @@
 #define FWD_TC Tc
 #define FWD_PAD_MEL(t, v) ((t) < Tc ? (v) : 0.f)
 #else
+#if DMEL_FWD_BAND
+#define FWD_PARAMS FwdBandParams
+#else
 #define FWD_PARAMS FwdParams
+#endif
 #define FWD_LC p.L
 #define FWD_INV_L p.inv_L
 #define FWD_TC p.T
@@ -38,6 +49,11 @@
 #endif
 #ifndef DMEL_TWC
 #define DMEL_TWC 8
+#endif
+// dmel_fwd_band_kernel: 1 = tiles / phases that hold none of the channel's rows are not contracted; 0 = every row is contracted and the stores
+// alone are masked (diagnostic builds: the comparison of NOTEBOOK R8.1)
+#ifndef DMEL_BAND_SKIP
+#define DMEL_BAND_SKIP 1
 #endif
 template <int N, int MODE, int TPW>
 __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, MODE>().MINW)) FWD_KERNEL(FWD_PARAMS p)
@@ -114,7 +130,13 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
 #endif
     const int b = wg / p.wgs_per_clip;
 #if DMEL_FWD_MULTI
+#if DMEL_FWD_BAND
+    // one image for all channels; this channel's rows [e_lo, e_hi): two scalar loads from the kernel arguments, uniform over the workgroup
+    const int bo = b;
+    const int e_lo = __builtin_amdgcn_readfirstlane(p.band_edges[ch]), e_hi = __builtin_amdgcn_readfirstlane(p.band_edges[ch + 1]);
+#else
     const int bo = b * p.ch_out + ch;
+#endif
 #endif
 #if DMEL_FWD_LEN
     // the clip is x[b, :Lc] (one scalar load: uniform over the workgroup) with Tc = Lc / hop + 1 frames; the frames past them are pad frames.
@@ -373,10 +395,15 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
         if (ls.action != kLamRun) {
             if (ls.action == kLamPoison) {
                 // no launch of this forward matched the device lambd: NaN instead of stale memory (the host raises too)
-                const int rows = IS_SPEC ? F : p.M;
+#if DMEL_FWD_BAND
+                const int rows = p.M, nrows = e_hi - e_lo, row0 = e_lo;              // this channel's rows only: the other groups' stay as they are
+#else
+                const int rows = IS_SPEC ? F : p.M, nrows = rows;
+                constexpr int row0 = 0;
+#endif
                 const float qn = __builtin_nanf("");
-                for (int idx = tid; idx < rows * FPT * TPW; idx += THREADS) {
-                    const int rr = idx / (FPT * TPW), t = tile0 * FPT + idx % (FPT * TPW);
+                for (int idx = tid; idx < nrows * FPT * TPW; idx += THREADS) {
+                    const int rr = row0 + idx / (FPT * TPW), t = tile0 * FPT + idx % (FPT * TPW);
                     if (t >= p.T) continue;
                     const size_t o = ((size_t)FWD_BO * rows + rr) * p.T + t;
                     if (p.flags & 4u) reinterpret_cast<unsigned short*>(p.out)[o] = 0x7fc0u; else p.out[o] = qn;
@@ -1146,6 +1173,14 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
             for (int ph = 0; ph < p.wl_phases; ++ph) {
                 const int n4 = p.wl_len4[ph];
                 const int2 li = li_pref;
+#if DMEL_FWD_BAND
+                // a lane keeps its column only if the mel band is one of this channel's rows; a phase none of whose quads holds such a
+                // band (the quads are sorted by width: the narrow low bands and the wide high ones sit in different phases) runs no steps
+                const bool row_mine = li.y >= e_lo && li.y < e_hi;
+                const int n4r = (!DMEL_BAND_SKIP || __any(row_mine)) ? n4 : 0;
+#else
+                const int n4r = n4;
+#endif
                 const int mi = mi_pref;
                 if (ph + 1 < p.wl_phases) {
                     li_pref = p.wl_lane[(ph + 1) * 64 + lane];
@@ -1175,7 +1210,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                 };
                 int s4 = 0;
                 const int ring_n4 = DMEL_WL_UNCOND ? wl_last(n4, off4 - n4) : n4;
-                for (; s4 + WL_DEPTH <= n4; s4 += WL_DEPTH) {
+                for (; s4 + WL_DEPTH <= n4r; s4 += WL_DEPTH) {
                     static_for<0, WL_DEPTH>([&](auto dd) {
                         constexpr int d = decltype(dd)::value;
                         group(dd);
@@ -1189,7 +1224,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                     });
                     aaddr += WL_DEPTH * 32;
                 }
-                static_for<0, WL_DEPTH - 1>([&](auto dd) { if (s4 + decltype(dd)::value < n4) group(dd); });
+                static_for<0, WL_DEPTH - 1>([&](auto dd) { if (s4 + decltype(dd)::value < n4r) group(dd); });
                 // the next phase's first groups: in flight under this phase's epilogue
                 if (DMEL_WL_NEXT && ph + 1 < p.wl_phases) wl_ring_init(p.wl_len4[ph + 1], off4);
                 floatx4 tot = acc0 + acc1;
@@ -1219,6 +1254,9 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                 // ---- epilogue: column j of block b = mel band li.y, rows = (frame, P | D) ----------------
                 const int m = li.y;
                 if (m < 0) continue;
+#if DMEL_FWD_BAND
+                if (!row_mine) continue;
+#endif
 #ifdef DMEL_ABLATE
                 if (p.flags & 0x400u) { if (tot[0] == 12345.678f) out_clip[0] = tot[1] + tot[2] + tot[3]; continue; }   // timing only: no epilogue
                 if (p.flags & 0x20000u) {
@@ -1292,10 +1330,16 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                 __syncthreads();
                 STAMP(16 * ti + 10);
                 constexpr int QPR = SLOTS / 4;                               // 16-byte pieces per row of the tile
-                const int total = 2 * p.M * QPR;
+#if DMEL_FWD_BAND
+                const int srows = e_hi - e_lo, srow0 = e_lo;                 // only this channel's rows were staged
+#else
+                const int srows = p.M;
+                constexpr int srow0 = 0;
+#endif
+                const int total = 2 * srows * QPR;
                 for (int idx = tid; idx < total; idx += THREADS) {
                     const int rw = idx / QPR, c = idx % QPR;
-                    const int pl = rw >= p.M ? 1 : 0, mm = rw - pl * p.M;
+                    const int pl = rw >= srows ? 1 : 0, mm = srow0 + rw - pl * srows;
                     float4 v;
                     if constexpr (FPW == 2) {
                         const float2 lo = *reinterpret_cast<const float2*>(smem_raw + (2 * c) * FPW * (SS * 8) + ((pl * p.M + mm) * FPW) * 4);
@@ -1329,6 +1373,9 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                     if (nt < 0) return;
                     const int m = 16 * nt + col;
                     if (m >= p.M) return;
+#if DMEL_FWD_BAND
+                    if (m < e_lo || m >= e_hi) return;
+#endif
                     const size_t rbase = ((size_t)FWD_BO * p.M + m) * p.T;
                     float* orow = p.out + rbase;
                     unsigned short* orow_h = reinterpret_cast<unsigned short*>(p.out) + rbase;     // DMEL_FLAG_OUT_BF16: out is bf16
@@ -1470,6 +1517,11 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                     if (p.flags & 0x800u) return;                       // timing ablation: skip the MFMA loop
 #endif
                     if (nks <= 0) return;
+#if DMEL_FWD_BAND
+                    // a mel tile (or a piece of one) none of whose 16 bands is this channel's: nothing of it is stored, so nothing is contracted
+                    // (uniform: the tile word is in scalar registers; the exchange below still runs, on zeros)
+                    if (DMEL_BAND_SKIP && tile_of[loc] >= 0 && (16 * tile_of[loc] + 16 <= e_lo || 16 * tile_of[loc] >= e_hi)) return;
+#endif
                     const int bbase = (boff + lane) * 4;
                     // One group = 4 consecutive k-steps = 16 consecutive bins starting at a multiple of 16 (the host
                     // aligns every run to 4 k-steps), so the 4 reads of Z[k] share one base address and, except at one

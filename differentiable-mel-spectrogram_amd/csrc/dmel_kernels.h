@@ -417,6 +417,12 @@ struct FwdLenParams : FwdParams {
     const int* lengths;         // (B) device, read by the kernel when it runs
 };
 
+// dmel_fwd_band_kernel (csrc/dmel_fwd_band.hip): the multi-window launch (ch_out = 1, channel slots, per-channel lambd words and window tables) whose
+// channels all write ONE (B, 1, M, T) image: channel c produces rows [band_edges[c], band_edges[c + 1]) and nothing else.
+struct FwdBandParams : FwdParams {
+    int band_edges[kMaxChannels + 1];   // 0 = e_0 < e_1 < ... < e_K = M (validated by the host)
+};
+
 struct PrepParams {
     const float* x; float* psum; float2* win2;
     const float* const* x_ind;      // DMEL_FLAG_X_INDIRECT: the address of x is read from here (then x is nullptr), as in FwdParams
@@ -432,6 +438,8 @@ hipError_t launch_prep(const PrepParams& p, hipStream_t s);
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdParams& p, int grid, hipStream_t s);
 hipError_t launch_forward_len(int n_fft, int mode, int tiles_per_wg, const FwdLenParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
 hipError_t forward_len_prepare_attributes();   // ... and the dynamic-LDS limit of its instantiations
+hipError_t launch_forward_band(int n_fft, int mode, int tiles_per_wg, const FwdBandParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
+hipError_t forward_band_prepare_attributes();
 int forward_tiles_per_wg(int n_fft, int mode, int batch, int tiles_per_clip);          // 1 or 2: what launch_forward should be given
 bool forward_two_tiles(int n_fft, int mode);          // the two-tiles-per-workgroup instantiation exists for this size and mode
 int forward_lds_bytes(int n_fft, int mode);
@@ -640,6 +648,17 @@ hipError_t launch_dot(const void* g, int g_bf16, const float* t, long long count
 int dot_multi_blocks_per_channel(long long per_channel, int channels);
 hipError_t launch_dot_multi(const void* g, int g_bf16, const float* t, int batch, int channels, long long per_row, int blocks_per_channel,
                             int accumulate, double* partials, unsigned* counter, float* result, hipStream_t s);
+// the band-split layer's backward: dlambd[c] = sum over clips and rows [edges[c], edges[c + 1]) of grad_out . tangent for (batch, 1, M, T) tensors
+// (`per_row` = T elements per row), in ONE launch: the workgroups are dealt to the groups in proportion to their row counts (blocks[c], their
+// sum <= kDotMaxBlocks); same scratch, fp64 accumulation and fixed-order combine by ticket as launch_dot_multi
+struct DotBandParams {
+    const void* g; const float* t; double* partials; unsigned* counter; float* result;
+    int g_bf16, batch, channels, M, T, accumulate;
+    int edges[kMaxChannels + 1];
+    int blocks[kMaxChannels];       // workgroups of group c (>= 1)
+};
+void dot_band_deal(const int* edges, int channels, int batch, int T, int* blocks);
+hipError_t launch_dot_band(const DotBandParams& p, hipStream_t s);
 // the same exchange for a value that is already in memory (one wave): buf[0] = sum over ranks of buf[0]
 hipError_t launch_mailbox_allreduce(float* buf, const MailboxArgs& mb, hipStream_t s);
 

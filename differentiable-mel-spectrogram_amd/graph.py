@@ -170,7 +170,8 @@ class GraphedStep:
                  inputs=None, zero_copy=None):
         self.step_fn, self.layers = step_fn, list(layers)
         if any(getattr(lay, "MAX_CHANNELS", 0) for lay in self.layers):
-            raise ValueError("GraphedStep does not drive a MultiWindowMelSpectrogram: capture its step with torch.cuda.graph")
+            raise ValueError(f"GraphedStep does not drive a {next(type(lay).__name__ for lay in self.layers if getattr(lay, 'MAX_CHANNELS', 0))}: "
+                             "capture its step with torch.cuda.graph")
         self.inputs = None if inputs is None else list(inputs)
         if zero_copy is not None and self.inputs is None:
             raise ValueError("GraphedStep(zero_copy=...) needs inputs=[...]")

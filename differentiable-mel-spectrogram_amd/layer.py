@@ -762,6 +762,127 @@ class MultiWindowMelSpectrogram(nn.Module):
                 f"waveform_grad={self.waveform_grad}")
 
 
+class _BandFunction(torch.autograd.Function):
+    """forward: dmel_forward_band(_dev) -- one launch per distinct n_fft for all K channels, every channel writing its own rows of ONE
+    (B, 1, M, T) image and of its tangent; backward: dmel_backward_band (the K row-group dot products in one launch)."""
+
+    @staticmethod
+    def forward(ctx, x, lambd, plan, lam_host, edges, log, eps, out_dtype, want_tangent):
+        B, K = x.shape[0], lambd.shape[0]
+        out = torch.empty((B, 1, plan.n_mels, plan.n_time), dtype=out_dtype, device=x.device)
+        tangent = torch.empty(out.shape, dtype=torch.float32, device=x.device) if want_tangent else None
+        scratch = torch.empty((plan.scratch_bytes_multi(B, K),), dtype=torch.uint8, device=x.device)
+        bf16 = out_dtype == torch.bfloat16
+        with _on_device(x.device):
+            if lam_host is not None:
+                plan.forward_band(x.data_ptr(), B, lam_host, edges, out.data_ptr(), tangent.data_ptr() if want_tangent else None, log, eps,
+                                  _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
+            else:
+                lam = lambd.detach()
+                if lam.dtype != torch.float32 or not lam.is_contiguous():
+                    lam = lam.to(torch.float32).contiguous()
+                plan.forward_band_dev(x.data_ptr(), B, lam.data_ptr(), edges, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
+                                      log, eps, _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
+        ctx.plan, ctx.K, ctx.lambd_dtype, ctx.edges, ctx.want_tangent = plan, K, lambd.dtype, edges, want_tangent
+        if want_tangent:
+            ctx.save_for_backward(tangent, scratch)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        bf16 = grad_out.dtype == torch.bfloat16
+        g = grad_out
+        if not bf16 and g.dtype != torch.float32:
+            g = g.to(torch.float32)
+        if not g.is_contiguous():
+            g = g.contiguous()
+        dl = None
+        if ctx.want_tangent:
+            tangent, scratch = ctx.saved_tensors
+            with _on_device(g.device):
+                dl = torch.empty((ctx.K,), dtype=torch.float32, device=g.device)
+                ctx.plan.backward_band(g.data_ptr(), tangent.data_ptr(), g.shape[0], ctx.edges, dl.data_ptr(), _stream_ptr(g.device),
+                                       scratch.data_ptr(), grad_bf16=bf16)
+                if ctx.lambd_dtype != torch.float32:
+                    dl = dl.to(ctx.lambd_dtype)
+        return None, dl, None, None, None, None, None, None, None
+
+
+class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
+    """A trainable window width per GROUP OF MEL BANDS inside one image: the scalar layer's output shape, K resolutions.
+
+        BandSplitMelSpectrogram(init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
+                                band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False)
+        forward(x: (B, n_points)) -> (B, 1, n_mels, n_points // hop_length + 1)
+
+    ``band_edges`` are K + 1 integers ``0 = e_0 < e_1 < ... < e_K = n_mels`` (default ``e_k = (k * n_mels) // K``).  Rows
+    ``e_k ... e_{k+1} - 1`` of the image are those rows of what ``MelSpectrogramLayer(lambd[k], ..., optimized=True)`` returns for the
+    same ``x``, bit for bit (fp32 and bf16, training and ``torch.no_grad()`` kernels): each group has its own n_fft =
+    next_pow2(int(6 |lambd[k]|)) and the HTK bank of THAT n_fft, and ``lambd.grad[k]`` sums ``grad_out * d out / d lambd[k]`` over the
+    group's rows.  The rows of the other channels are never computed into memory.  The parameter is ``lambd`` of shape ``(K,)``,
+    1 <= K <= 8, every n_fft in 32 ... 16384, so the layer drops into the nets of ``nets.py`` / ``panns.py``
+    (``net.spectrogram_layer = BandSplitMelSpectrogram(...)``) and ``nets.make_optimizer`` puts it in the ``lr_tf`` group as it is.
+
+    The intended order is WIDE windows for the LOW bands: a mel band narrower than one bin of its group's n_fft is an all-zero row of
+    that HTK bank, as in the scalar layer (value ``0`` / ``log(eps)``, gradient exactly 0), which is what a short window on low bands gives.
+
+    ``band_edges`` is a plain attribute reconstructed from the constructor; it is NOT part of ``state_dict`` (whose only key stays
+    ``lambd``, as the scalar layer's checkpoints): build the layer with the same edges before loading.
+
+    ``lambd_sync=False`` keeps the K values on the device with one host picture per channel exactly as the multi-window layer
+    (``resync()``, ``lambd_status(channel)``, ``set_tracking``); a channel no launch covered makes ITS rows NaN, leaves the other
+    groups' rows untouched, and the next forward raises naming the channel.  The sync-free step can be captured with ``torch.cuda.graph``.
+    Out of scope, not forgotten (each raises and says what to use instead): a waveform gradient (``x.requires_grad``), per-clip
+    ``lengths``, ``SlotInput``, ``GraphedStep`` and ``LambdAdam(fused_into_backward=...)``; band edges and the filterbank are not trainable."""
+
+    def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
+                 band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False):
+        super().__init__(init_lambd, n_mels, n_points, sample_rate, f_min, f_max, hop_length, normalize_window, log=log, eps=eps,
+                         out_dtype=out_dtype, lambd_sync=lambd_sync)
+        K = self.lambd.shape[0]
+        if band_edges is None:
+            if K > n_mels:
+                raise ValueError(f"{K} groups need at least {K} mel bands, got n_mels = {n_mels}")
+            edges = [(k * n_mels) // K for k in range(K + 1)]
+        else:
+            raw = band_edges.tolist() if torch.is_tensor(band_edges) else list(band_edges)
+            if any(int(v) != v for v in raw):
+                raise ValueError(f"band_edges must be integers, got {raw}")
+            edges = [int(v) for v in raw]
+        if len(edges) != K + 1:
+            raise ValueError(f"band_edges needs K + 1 = {K + 1} entries for {K} window widths, got {len(edges)}")
+        if edges[0] != 0 or edges[-1] != n_mels or any(b <= a for a, b in zip(edges, edges[1:])):
+            raise ValueError(f"band_edges must be 0 = e_0 < e_1 < ... < e_K = n_mels = {n_mels} (every group non-empty), got {edges}")
+        self.band_edges = tuple(edges)
+
+    def forward(self, x, lengths=None):
+        if lengths is not None:
+            raise RuntimeError("BandSplitMelSpectrogram does not take per-clip lengths (MelSpectrogramLayer does)")
+        if isinstance(x, SlotInput):
+            raise RuntimeError("BandSplitMelSpectrogram does not take a SlotInput: pass the batch tensor (MelSpectrogramLayer takes slots)")
+        if x.dim() != 2:
+            raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
+        if x.shape[1] != self.n_points:
+            raise RuntimeError(f"input has {x.shape[1]} points, the layer was built for n_points={self.n_points}")
+        if not x.is_cuda:
+            raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
+        if x.requires_grad:
+            raise RuntimeError("BandSplitMelSpectrogram has no waveform gradient: pass x.detach() (MelSpectrogramLayer and "
+                               "MultiWindowMelSpectrogram(waveform_grad=True) have one)")
+        if self.lambd.device != x.device:
+            raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
+        xf = x if x.dtype == torch.float32 else _to_f32(x)
+        if not xf.is_contiguous():
+            xf = xf.contiguous()
+        lam_host = [float(v) for v in self.lambd.detach().cpu().tolist()] if self.lambd_sync else None
+        want = torch.is_grad_enabled() and self.lambd.requires_grad
+        return _BandFunction.apply(xf, self.lambd, self._plan_for(x.device), lam_host, self.band_edges, self.log, self.eps, self.out_dtype, want)
+
+    def extra_repr(self):
+        return (f"band_edges={list(self.band_edges)}, n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
+                f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}")
+
+
 class _DspecFunction(torch.autograd.Function):
     """forward: dmel_spectrogram_ex (carries d spec / d lambd); backward: dmel_backward and, for a waveform that requires grad,
     dmel_backward_x_spec."""

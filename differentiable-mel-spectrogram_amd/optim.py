@@ -64,7 +64,7 @@ class LambdAdam(torch.optim.Optimizer):
         if self._fused_layer is not None:
             lay = self._fused_layer
             if getattr(lay, "MAX_CHANNELS", 0):
-                raise ValueError("LambdAdam(fused_into_backward=...) serves MelSpectrogramLayer only, not MultiWindowMelSpectrogram")
+                raise ValueError(f"LambdAdam(fused_into_backward=...) serves MelSpectrogramLayer only, not {type(lay).__name__}: use torch.optim.Adam")
             if getattr(lay, "learnable_fb", False) or getattr(lay, "lambd_sync", False):
                 raise ValueError("LambdAdam(fused_into_backward=layer): the layer's only parameter must be lambd, kept on the device (lambd_sync=False)")
             ps = [p for g in self.param_groups for p in g["params"]]

@@ -486,6 +486,24 @@ dmel_status dmel_backward_x_multi_dev(dmel_plan* plan, const float* x, int32_t b
  * ascending n_fft with their channel masks; arrays of 24 (3 x 8) entries.  count = 0 before the first such call. */
 dmel_status dmel_plan_last_multi_launch(dmel_plan* plan, int32_t* n_ffts, uint32_t* channel_masks, int32_t* count);
 
+/* ---- the band-split layer: a trainable window width per GROUP OF MEL BANDS inside one image (dmel_amd.BandSplitMelSpectrogram) ----------
+ * out and tangent are (batch, 1, n_mels, n_time), the scalar layer's shape.  band_edges: K + 1 HOST integers 0 = e_0 < e_1 < ... < e_K =
+ * n_mels (validated, taken by value: the array may be reused at once); rows e_k ... e_{k+1} - 1 are what dmel_forward* computes for
+ * lambd[k], bit for bit, and no other row is computed into memory.  Everything else -- K, the n_fft range, flags, scratch
+ * (dmel_scratch_bytes_multi(plan, batch, K), required), one launch per DISTINCT n_fft, host values (dmel_forward_band) or device values with
+ * one host picture per channel, guards, dmel_plan_lambd_status_channel, DMEL_ERR_LAMBD_TRACKING -- is dmel_forward_multi(_dev)'s.  A channel no
+ * launch covered makes ITS rows NaN and leaves the other groups' rows untouched.  A plan serves one of the two layers: they share the per-channel
+ * lambd pictures.  NULL / invalid band_edges, K outside 1 ... 8: DMEL_ERR_INVALID_ARGUMENT before any device work. */
+dmel_status dmel_forward_band(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, const int32_t* band_edges,
+                              uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream);
+dmel_status dmel_forward_band_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, const int32_t* band_edges,
+                                  uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream);
+/* dlambd[k] (= or += with accumulate) sum over clips and rows e_k ... e_{k+1} - 1 of grad_out . tangent, both (batch, 1, n_mels, n_time): K
+ * values in ONE deterministic launch (fp64 accumulation, workgroups dealt to the groups in proportion to their rows, fixed-order combine; bf16
+ * gradients widened exactly).  Not with an attached mailbox or fused Adam. */
+dmel_status dmel_backward_band(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int32_t batch, int32_t channels,
+                               const int32_t* band_edges, int32_t accumulate, float* dlambd, void* scratch, void* stream);
+
 /* Introspection for tests / benchmarks */
 typedef struct dmel_plan_info {
     int32_t n_fft;             /* of the most recent forward                                */
