@@ -405,6 +405,12 @@ class Plan:
         _check(load().dmel_forward_dev(self._h, x_ptr, batch, lambd_ptr, (DMEL_FLAG_LOG if log else 0) | int(extra_flags), float(eps),
                                        out_ptr, tangent_ptr, scratch_ptr, stream))
 
+    def forward_lengths(self, x_ptr: int, lengths_ptr: int, batch: int, lambd: float, out_ptr: int, tangent_ptr: int | None, log: bool,
+                        eps: float, stream: int, scratch_ptr: int | None = None, extra_flags: int = 0):
+        """dmel_forward_lengths: clips ``x[b, :lengths[b]]`` (int32 lengths on the device), lambd by value."""
+        _check(load().dmel_forward_lengths(self._h, x_ptr, lengths_ptr, batch, C.c_float(float(lambd)),
+                                           (DMEL_FLAG_LOG if log else 0) | int(extra_flags), float(eps), out_ptr, tangent_ptr, scratch_ptr, stream))
+
     def forward_dev_fixed(self, x_ptr: int, batch: int, lambd_ptr: int, n_fft_: int, out_ptr: int, tangent_ptr: int | None, log: bool,
                           eps: float, stream: int, scratch_ptr: int | None = None, extra_flags: int = 0):
         """dmel_forward_dev_fixed: one launch for ``n_fft_``, lambd read and checked on the device (trainable filterbank)."""

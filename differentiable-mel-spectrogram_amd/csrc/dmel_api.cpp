@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -1026,6 +1027,21 @@ dmel_status check_device(const dmel_plan* pl)
     return DMEL_OK;
 }
 
+// include/dmel.h, "Alignment": what the library only reads (x, grad_out, lengths, the filterbank, a saved tangent or spectrogram) needs
+// the alignment of its element -- the kernels dispatch on the address --, what it stores through is written
+// with 16- and 8-byte stores that no kernel guards (the fused forward's epilogue: float4 / float2 / packed bf16 rows of out and
+// tangent; fp64 partials in scratch) and must be 16-byte aligned.  Checked on the host before anything is launched; NULL = not given.
+struct StorePtr { const char* name; const void* ptr; };
+dmel_status check_store_aligned(const char* fn, std::initializer_list<StorePtr> ptrs)
+{
+    for (const StorePtr& sp : ptrs)
+        if (sp.ptr && (reinterpret_cast<uintptr_t>(sp.ptr) & 15u) != 0)
+            return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(fn) + ": " + sp.name + " must be 16-byte aligned (the kernels store through it with "
+                        "16-byte writes); its address ends in " + std::to_string((unsigned)(reinterpret_cast<uintptr_t>(sp.ptr) & 15u)) +
+                        " modulo 16.  Pointers that are only read (x, grad_out, lengths, filterbank) need their element's alignment");
+    return DMEL_OK;
+}
+
 dmel_status check_forward_args(dmel_plan* pl, const float* x, int batch, const void* out)
 {
     if (!pl) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
@@ -1425,6 +1441,7 @@ dmel_status dmel_forward_scratch(dmel_plan* plan, const float* x, int32_t batch,
                                  double eps, void* out, float* tangent, void* scratch, void* stream)
 {
     if (flags & DMEL_FLAG_X_INDIRECT) return fail(DMEL_ERR_INVALID_ARGUMENT, "DMEL_FLAG_X_INDIRECT belongs to dmel_forward_dev");
+    { dmel_status sa = check_store_aligned("dmel_forward", {{"out", out}, {"tangent", tangent}, {"scratch", scratch}}); if (sa != DMEL_OK) return sa; }
     if (flags & DMEL_FLAG_FULL_WINDOW) {
         if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
         const int L = plan->cfg.n_points;
@@ -1460,6 +1477,7 @@ static dmel_status forward_dev_impl(dmel_plan* plan, const float* x, int32_t bat
 {
     dmel_status st = check_forward_args(plan, x, batch, out);
     if (st != DMEL_OK) return st;
+    if ((st = check_store_aligned(lengths ? "dmel_forward_dev_lengths" : "dmel_forward_dev", {{"out", out}, {"tangent", tangent}, {"scratch", scratch}})) != DMEL_OK) return st;
     if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
     if (flags & DMEL_FLAG_FULL_WINDOW)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev: DMEL_FLAG_FULL_WINDOW has a fixed n_fft, use dmel_forward");
@@ -1564,6 +1582,7 @@ dmel_status dmel_forward_lengths(dmel_plan* plan, const float* x, const int32_t*
 {
     if (!plan || !x || !lengths || !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_lengths: plan / x / lengths / out is NULL");
     if (flags & ~kLengthsFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_lengths: flags other than LOG, OUT_BF16, X_INDIRECT");
+    { dmel_status sa = check_store_aligned("dmel_forward_lengths", {{"out", out}, {"tangent", tangent}, {"scratch", scratch}}); if (sa != DMEL_OK) return sa; }
     if (!std::isfinite(lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
     const int N = dmel_n_fft(lambd);
     if (N < dmel::kMinFastNfft || N > dmel::kMaxFastNfft)
@@ -1586,6 +1605,7 @@ dmel_status dmel_forward_dev_fixed(dmel_plan* plan, const float* x, int32_t batc
 {
     dmel_status st = check_forward_args(plan, x, batch, out);
     if (st != DMEL_OK) return st;
+    if ((st = check_store_aligned("dmel_forward_dev_fixed", {{"out", out}, {"tangent", tangent}, {"scratch", scratch}})) != DMEL_OK) return st;
     if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
     if (flags & DMEL_FLAG_X_INDIRECT) return fail(DMEL_ERR_INVALID_ARGUMENT, "DMEL_FLAG_X_INDIRECT belongs to dmel_forward_dev");
     if (flags & DMEL_FLAG_FULL_WINDOW) {
@@ -1635,6 +1655,7 @@ dmel_status dmel_forward_dev_fixed_spec(dmel_plan* plan, const float* x, int32_t
     if (!spec) return dmel_forward_dev_fixed(plan, x, batch, lambd_dev, n_fft, flags, eps, out, tangent, scratch, stream);
     dmel_status st = check_forward_args(plan, x, batch, out);
     if (st != DMEL_OK) return st;
+    if ((st = check_store_aligned("dmel_forward_dev_fixed_spec", {{"out", out}, {"tangent", tangent}, {"spec", spec}, {"scratch", scratch}})) != DMEL_OK) return st;
     if (!lambd_dev || !tangent) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_fixed_spec: lambd_dev / tangent is NULL (the training forward saves the spectrogram)");
     if (flags & DMEL_FLAG_FULL_WINDOW) return fail(DMEL_ERR_UNSUPPORTED, "dmel_forward_dev_fixed_spec: not with DMEL_FLAG_FULL_WINDOW");
     if (n_fft < dmel::kMinFastNfft || n_fft > dmel::kMaxNfft || (n_fft & (n_fft - 1)))
@@ -1768,10 +1789,12 @@ size_t dmel_scratch_bytes_multi(const dmel_plan* plan, int32_t batch, int32_t ch
 
 namespace {
 
-dmel_status check_multi_args(dmel_plan* pl, const float* x, int batch, int channels, uint32_t flags, const void* out, void* scratch)
+dmel_status check_multi_args(dmel_plan* pl, const float* x, int batch, int channels, uint32_t flags, const void* out, const float* tangent,
+                             void* scratch, const char* fn)
 {
     dmel_status st = check_forward_args(pl, x, batch, out);
     if (st != DMEL_OK) return st;
+    if ((st = check_store_aligned(fn, {{"out", out}, {"tangent", tangent}, {"scratch", scratch}})) != DMEL_OK) return st;
     if (channels < 1 || channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, "channels must be 1 ... 8");
     if (flags & ~(uint32_t)(DMEL_FLAG_LOG | DMEL_FLAG_OUT_BF16))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi: only DMEL_FLAG_LOG and DMEL_FLAG_OUT_BF16 are accepted");
@@ -1844,7 +1867,7 @@ dmel_status check_band_plan(const dmel_plan* pl, const int32_t* edges, int chann
 dmel_status forward_multi_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, uint32_t flags,
                                double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges)
 {
-    dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, scratch);
+    dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, tangent, scratch, edges ? "dmel_forward_band" : "dmel_forward_multi");
     if (st != DMEL_OK) return st;
     if (!lambd_host) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_host is NULL");
     std::map<int, uint32_t> u;
@@ -1871,7 +1894,7 @@ dmel_status forward_multi_impl(dmel_plan* plan, const float* x, int32_t batch, c
 dmel_status forward_multi_dev_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
                                    double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges)
 {
-    dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, scratch);
+    dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, tangent, scratch, edges ? "dmel_forward_band_dev" : "dmel_forward_multi_dev");
     if (st != DMEL_OK) return st;
     if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
     std::lock_guard<std::mutex> lock(plan->mu);
@@ -2014,6 +2037,7 @@ dmel_status dmel_backward_band(dmel_plan* plan, const void* grad_out, int32_t gr
     if ((st = check_band_plan(plan, band_edges, channels, "dmel_backward_band")) != DMEL_OK) return st;
     if (batch < 0 || !dlambd || !scratch || (batch > 0 && (!grad_out || !tangent)))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: bad arguments");
+    if ((st = check_store_aligned("dmel_backward_band", {{"scratch", scratch}})) != DMEL_OK) return st;
     if (grad_dtype != DMEL_DTYPE_F32 && grad_dtype != DMEL_DTYPE_BF16)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
     if (plan->mailbox || plan->fused_adam.param)
@@ -2042,6 +2066,7 @@ dmel_status dmel_backward_multi(dmel_plan* plan, const void* grad_out, int32_t g
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
     if (batch < 0 || channels < 1 || channels > dmel::kMaxChannels || !dlambd || !scratch || (batch > 0 && (!grad_out || !tangent)))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: bad arguments");
+    { dmel_status sa = check_store_aligned("dmel_backward_multi", {{"scratch", scratch}}); if (sa != DMEL_OK) return sa; }
     if (grad_dtype != DMEL_DTYPE_F32 && grad_dtype != DMEL_DTYPE_BF16)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
     if (plan->mailbox || plan->fused_adam.param)
@@ -2091,6 +2116,7 @@ dmel_status dmel_plan_lambd_status_channel(dmel_plan* plan, int32_t channel, dme
 dmel_status dmel_spectrogram(dmel_plan* plan, const float* x, int32_t batch, float lambd,
                              int32_t remove_dc, float* spec, void* stream)
 {
+    { dmel_status sa = check_store_aligned("dmel_spectrogram", {{"spec", spec}}); if (sa != DMEL_OK) return sa; }
     return run_forward(plan, x, batch, lambd, 0u, 0.0, spec, nullptr, dmel::kSpec, remove_dc ? 1 : 0, stream);
 }
 
@@ -2098,6 +2124,7 @@ dmel_status dmel_spectrogram_ex(dmel_plan* plan, const float* x, int32_t batch, 
                                 uint32_t flags, float* spec, float* tangent, void* stream)
 {
     if (n_fft < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft < 0");
+    { dmel_status sa = check_store_aligned("dmel_spectrogram_ex", {{"spec", spec}, {"tangent", tangent}}); if (sa != DMEL_OK) return sa; }
     return run_forward(plan, x, batch, lambd, 0u, 0.0, spec, tangent, tangent ? dmel::kSpecTrain : dmel::kSpec,
                        (flags & DMEL_SPEC_REMOVE_DC) ? 1 : 0, stream, n_fft, (flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0);
 }
@@ -2106,6 +2133,7 @@ dmel_status dmel_spectrogram_ex_dev(dmel_plan* plan, const float* x, int32_t bat
                                     uint32_t flags, float* spec, float* tangent, void* stream)
 {
     if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
+    { dmel_status sa = check_store_aligned("dmel_spectrogram_ex_dev", {{"spec", spec}, {"tangent", tangent}}); if (sa != DMEL_OK) return sa; }
     if (n_fft <= 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_spectrogram_ex_dev: n_fft must be given (a length that depends on lambd needs the host value: dmel_spectrogram_ex)");
     return run_forward(plan, x, batch, 0.f, 0u, 0.0, spec, tangent, tangent ? dmel::kSpecTrain : dmel::kSpec,
                        (flags & DMEL_SPEC_REMOVE_DC) ? 1 : 0, stream, n_fft, (flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0, nullptr, lambd_dev);
@@ -2130,6 +2158,7 @@ dmel_status dmel_backward_scratch(dmel_plan* plan, const void* grad_out, int32_t
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward: bad arguments");
     if (grad_dtype != DMEL_DTYPE_F32 && grad_dtype != DMEL_DTYPE_BF16)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward: grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
+    { dmel_status sa = check_store_aligned("dmel_backward", {{"scratch", scratch}}); if (sa != DMEL_OK) return sa; }
     { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2205,6 +2234,7 @@ dmel_status backward_fb_impl(dmel_plan* plan, const float* x, int32_t batch, flo
     if (!grad_fb || (batch > 0 && ((!x && !saved_spec) || !grad_out))) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_fb: x / grad_out / grad_fb is NULL");
     if ((flags & DMEL_FLAG_LOG) && batch > 0 && !out)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_fb: DMEL_FLAG_LOG needs the saved log output");
+    { dmel_status sa = check_store_aligned("dmel_backward_fb", {{"grad_fb", grad_fb}, {"scratch", rider ? rider->scratch : nullptr}}); if (sa != DMEL_OK) return sa; }
     if (!lambd_dev && !saved_spec && !std::isfinite(lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
     const bool full = (flags & DMEL_FLAG_FULL_WINDOW) != 0;
     if (lambd_dev && !full && (n_fft_dev < 1 || n_fft_dev > dmel::kMaxNfft || (n_fft_dev & (n_fft_dev - 1))))
@@ -2341,6 +2371,7 @@ dmel_status backward_x_impl(dmel_plan* plan, const float* x, int32_t batch, floa
                             bool check_nfft = false)
 {
     if (lambd_dev && n_over <= 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd on the device needs an explicit n_fft");
+    { dmel_status sa = check_store_aligned("dmel_backward_x", {{"grad_x", grad_x}}); if (sa != DMEL_OK) return sa; }
     const int N = n_over > 0 ? n_over : dmel_n_fft(lambd);
     const bool big = N > dmel::kMaxNfft || (N & (N - 1));              // dmel_big.hip: chirp-z / global-memory FFT, both directions
     if (N < 1 || N > dmel::kMaxBigFft || (big && (N & 1)))
@@ -2544,6 +2575,7 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
                                   const int* ns, const uint32_t* mask, int nl, bool log, const float* grad_out, const float* out,
                                   float* grad_x, void* stream)
 {
+    { dmel_status sa = check_store_aligned("dmel_backward_x_multi", {{"grad_x", grad_x}}); if (sa != DMEL_OK) return sa; }
     { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

@@ -17,6 +17,17 @@
  *     (models.py:38) and n_fft = next_pow2(int(6*|lambd|)) (time_frequency.py:39,60-65).
  *   - a plan owns its device tables and a default scratch; calls that use the plan's scratch from different streams
  *     are ordered after each other by the library (an event), calls with caller scratch are independent.
+ *
+ * Alignment
+ *   - pointers the library only READS need the alignment of their element and nothing more: x, lengths, lambd_dev, the
+ *     filterbank, grad_out (4 bytes for fp32, 2 for bf16), and a tangent, saved output or saved spectrogram handed back to a
+ *     backward call.  A contiguous view into a larger buffer, a slice of a concatenated gradient or the address in a
+ *     DMEL_FLAG_X_INDIRECT cell is fine at any element offset: the kernels choose their loads by the address they are given.
+ *   - pointers the library STORES through must be 16-byte aligned: out, tangent, spec, grad_x, grad_fb and a caller's scratch.
+ *     The kernels write them with 8- and 16-byte stores (packed bf16 pairs for DMEL_FLAG_OUT_BF16) that are guarded by shape only.
+ *     Every entry point checks this on the host and returns DMEL_ERR_INVALID_ARGUMENT, naming the argument, before it launches
+ *     anything.  hipMalloc and every framework allocator return blocks aligned far beyond this; it matters when a caller carves
+ *     outputs out of one block.  (dlambd and the optimizer's one-element tensors are stored as single floats: 4 bytes.)
  */
 #ifndef DMEL_H
 #define DMEL_H
@@ -32,7 +43,7 @@ extern "C" {
 
 typedef enum dmel_status {
     DMEL_OK = 0,
-    DMEL_ERR_INVALID_ARGUMENT = 1,  /* bad shape / null pointer / negative size          */
+    DMEL_ERR_INVALID_ARGUMENT = 1,  /* bad shape / null pointer / negative size / an output pointer that is not 16-byte aligned */
     DMEL_ERR_UNSUPPORTED = 2,       /* a transform that needs an FFT of more than 1048576 points (|lambd| > 174762, or an
                                        optimized=False clip longer than 262144 samples) */
     DMEL_ERR_HIP = 3,               /* a HIP runtime call failed (message has the detail) */
