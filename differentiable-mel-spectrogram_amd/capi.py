@@ -45,7 +45,7 @@ SYMBOLS = (
     "dmel_scratch_bytes_multi", "dmel_forward_multi", "dmel_forward_multi_dev", "dmel_backward_multi", "dmel_plan_lambd_status_channel",
     "dmel_decide_launch_multi", "dmel_backward_x_multi", "dmel_backward_x_multi_dev", "dmel_plan_last_multi_launch",
     "dmel_forward_band", "dmel_forward_band_dev", "dmel_backward_band",
-    "dmel_forward_lengths", "dmel_forward_dev_lengths",
+    "dmel_forward_lengths", "dmel_forward_dev_lengths", "dmel_backward_x_lengths", "dmel_backward_x_dev_lengths",
 )
 TORCH_LIB_PATH = os.path.join(_PKG_DIR, "libdmel_torch.so")
 
@@ -160,6 +160,10 @@ def load():
     L.dmel_forward_lengths.restype = C.c_int
     L.dmel_forward_dev_lengths.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
     L.dmel_forward_dev_lengths.restype = C.c_int
+    L.dmel_backward_x_lengths.argtypes = [vp, vp, vp, C.c_int32, C.c_float, C.c_uint32, vp, vp, vp, vp]
+    L.dmel_backward_x_lengths.restype = C.c_int
+    L.dmel_backward_x_dev_lengths.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, vp, vp, vp, vp]
+    L.dmel_backward_x_dev_lengths.restype = C.c_int
     L.dmel_forward_dev_fixed.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.c_double, vp, vp, vp, vp]
     L.dmel_forward_dev_fixed.restype = C.c_int
     L.dmel_backward_fb_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, vp, vp, vp, vp]
@@ -410,6 +414,25 @@ class Plan:
         """dmel_forward_lengths: clips ``x[b, :lengths[b]]`` (int32 lengths on the device), lambd by value."""
         _check(load().dmel_forward_lengths(self._h, x_ptr, lengths_ptr, batch, C.c_float(float(lambd)),
                                            (DMEL_FLAG_LOG if log else 0) | int(extra_flags), float(eps), out_ptr, tangent_ptr, scratch_ptr, stream))
+
+    def forward_dev_lengths(self, x_ptr: int, lengths_ptr: int, batch: int, lambd_ptr: int, out_ptr: int, tangent_ptr: int | None, log: bool,
+                            eps: float, stream: int, scratch_ptr: int | None = None, extra_flags: int = 0):
+        """dmel_forward_dev_lengths: clips ``x[b, :lengths[b]]`` with lambd left on the device (no host read)."""
+        _check(load().dmel_forward_dev_lengths(self._h, x_ptr, lengths_ptr, batch, lambd_ptr, (DMEL_FLAG_LOG if log else 0) | int(extra_flags),
+                                               float(eps), out_ptr, tangent_ptr, scratch_ptr, stream))
+
+    def backward_x_lengths(self, x_ptr: int, lengths_ptr: int, batch: int, lambd: float, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int,
+                           log: bool, stream: int):
+        """dmel_backward_x_lengths: the waveform gradient of clips ``x[b, :lengths[b]]`` (zero past a clip, NaN for an invalid length)."""
+        _check(load().dmel_backward_x_lengths(self._h, x_ptr, lengths_ptr, batch, C.c_float(float(lambd)), DMEL_FLAG_LOG if log else 0, grad_ptr,
+                                              out_ptr if log else None, grad_x_ptr, stream))
+
+    def backward_x_dev_lengths(self, x_ptr: int, lengths_ptr: int, batch: int, lambd_ptr: int, n_fft_: int, grad_ptr: int, out_ptr: int | None,
+                               grad_x_ptr: int, log: bool, stream: int, extra_flags: int = 0):
+        """dmel_backward_x_dev_lengths: the same with lambd read on the device (n_fft_: what this step's forward launched for)."""
+        _check(load().dmel_backward_x_dev_lengths(self._h, x_ptr, lengths_ptr, batch, lambd_ptr, int(n_fft_),
+                                                  (DMEL_FLAG_LOG if log else 0) | int(extra_flags), grad_ptr, out_ptr if log else None, grad_x_ptr,
+                                                  stream))
 
     def forward_dev_fixed(self, x_ptr: int, batch: int, lambd_ptr: int, n_fft_: int, out_ptr: int, tangent_ptr: int | None, log: bool,
                           eps: float, stream: int, scratch_ptr: int | None = None, extra_flags: int = 0):

@@ -1295,6 +1295,7 @@ dmel_status dmel_plan_create(const dmel_config* cfg, dmel_plan** plan)
     DMEL_HIP(dmel::forward_len_prepare_attributes());
     DMEL_HIP(dmel::forward_band_prepare_attributes());
     DMEL_HIP(dmel::xgrad_prepare_attributes());
+    DMEL_HIP(dmel::xgrad_len_prepare_attributes());
     DMEL_HIP(dmel::big_prepare_attributes());
     dmel_plan* pl = new (std::nothrow) dmel_plan();
     if (!pl) return fail(DMEL_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -2368,12 +2369,15 @@ namespace {
 // from the caller (n_over), never from a host copy of lambd
 dmel_status backward_x_impl(dmel_plan* plan, const float* x, int32_t batch, float lambd, int n_over, int win_half, int spec_mode, bool log,
                             const float* grad_out, const float* out, float* grad_x, void* stream, const float* lambd_dev = nullptr,
-                            bool check_nfft = false)
+                            bool check_nfft = false, const int32_t* lengths = nullptr)
 {
     if (lambd_dev && n_over <= 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd on the device needs an explicit n_fft");
-    { dmel_status sa = check_store_aligned("dmel_backward_x", {{"grad_x", grad_x}}); if (sa != DMEL_OK) return sa; }
+    { dmel_status sa = check_store_aligned(lengths ? "dmel_backward_x_lengths" : "dmel_backward_x", {{"grad_x", grad_x}}); if (sa != DMEL_OK) return sa; }
     const int N = n_over > 0 ? n_over : dmel_n_fft(lambd);
     const bool big = N > dmel::kMaxNfft || (N & (N - 1));              // dmel_big.hip: chirp-z / global-memory FFT, both directions
+    // per-clip lengths (dmel_xgrad_len.hip): the range of the lengths forward, the mel layer's Gaussian window
+    if (lengths && (big || N < dmel::kMinFastNfft || spec_mode || win_half))
+        return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform with per-clip lengths: n_fft 32 ... 16384 (n_fft = " + std::to_string(N) + ")");
     if (N < 1 || N > dmel::kMaxBigFft || (big && (N & 1)))
         return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: n_fft = " + std::to_string(N) + " (even lengths up to " +
                     std::to_string(dmel::kMaxBigFft) + ")");
@@ -2447,6 +2451,7 @@ dmel_status backward_x_impl(dmel_plan* plan, const float* x, int32_t batch, floa
     pp.N = N; pp.normalize = plan->cfg.normalize_window; pp.win_half = win_half;
     pp.center = win_half ? (float)((N / 2) / 2) + (float)(N / 2) / 2.0f : (float)N / 2.0f;      // as launch_forward_n
     pp.lam.dev = lambd_dev; pp.lam.val = lambd_dev ? 0.f : lambd; pp.lam.role = dmel::kLamQuiet;
+    pp.lengths = lengths;                                   // the partial sums then stop at the clip's end, as in the forward
     // short clips with the plain Gaussian window: the wave-FFT kernel evaluates the window and adds up its clip itself
     const bool own_prep = wave_path && !win_half && !plan->cfg.normalize_window && plan->cfg.n_points <= 32768 && std::getenv("DMEL_XGRAD_PREP") == nullptr;
     if (!own_prep) DMEL_HIP(dmel::launch_prep(pp, s));
@@ -2468,6 +2473,11 @@ dmel_status backward_x_impl(dmel_plan* plan, const float* x, int32_t batch, floa
     if (big) {
         DMEL_HIP(dmel::launch_xgrad_big(xp, big_grid, s));
         DMEL_HIP(dmel::launch_xgrad_gather(xp, s));
+    } else if (lengths) {
+        dmel::XgradLenParams lp{};
+        static_cast<dmel::XgradParams&>(lp) = xp;
+        lp.lengths = lengths; lp.fpt = wave_path ? fpt : 0;
+        DMEL_HIP(dmel::launch_xgrad_len(lp, s));
     } else {
         DMEL_HIP(dmel::launch_xgrad(xp, s));
     }
@@ -2520,6 +2530,36 @@ dmel_status dmel_backward_x_dev(dmel_plan* plan, const float* x, int32_t batch, 
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev: DMEL_FLAG_CHECK_NFFT has no meaning with DMEL_FLAG_FULL_WINDOW (n_fft = 2 n_points)");
     return backward_x_impl(plan, x, batch, 0.f, full ? 2 * plan->cfg.n_points : n_fft, full ? 1 : 0, 0, (flags & DMEL_FLAG_LOG) != 0,
                            grad_out, out, grad_x, stream, lambd_dev, (flags & DMEL_FLAG_CHECK_NFFT) != 0);
+}
+
+dmel_status dmel_backward_x_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, float lambd, uint32_t flags,
+                                    const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
+    if (batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch < 0");
+    if (batch == 0) return DMEL_OK;
+    if (!x || !lengths || !grad_out || !grad_x) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_lengths: x / lengths / grad_out / grad_x is NULL");
+    if (flags & ~DMEL_FLAG_LOG) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_lengths: flags other than LOG");
+    if ((flags & DMEL_FLAG_LOG) && !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_lengths: DMEL_FLAG_LOG needs the saved log output");
+    if (!std::isfinite(lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
+    return backward_x_impl(plan, x, batch, lambd, 0, 0, 0, (flags & DMEL_FLAG_LOG) != 0, grad_out, out, grad_x, stream, nullptr, false, lengths);
+}
+
+dmel_status dmel_backward_x_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                        int32_t n_fft, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
+    if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
+    if (batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch < 0");
+    if (batch == 0) return DMEL_OK;
+    if (!x || !lengths || !grad_out || !grad_x)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev_lengths: x / lengths / grad_out / grad_x is NULL");
+    if (flags & ~(DMEL_FLAG_LOG | DMEL_FLAG_CHECK_NFFT)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev_lengths: flags other than LOG, CHECK_NFFT");
+    if ((flags & DMEL_FLAG_LOG) && !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev_lengths: DMEL_FLAG_LOG needs the saved log output");
+    if (n_fft < 1 || (n_fft & (n_fft - 1)))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be a power of two (the n_fft this step's forward was issued for)");
+    return backward_x_impl(plan, x, batch, 0.f, n_fft, 0, 0, (flags & DMEL_FLAG_LOG) != 0, grad_out, out, grad_x, stream, lambd_dev,
+                           (flags & DMEL_FLAG_CHECK_NFFT) != 0, lengths);
 }
 
 dmel_status dmel_backward_x_spec_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft, uint32_t flags,

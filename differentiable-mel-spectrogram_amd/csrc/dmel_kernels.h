@@ -536,6 +536,17 @@ bool xgrad_wave_shape(int n_fft, int n_mels, int win_n, int* frames_per_tile);  
 int xgrad_chunks(int L);      // gather chunks per clip (size of XgradParams::csum per clip)
 hipError_t launch_xgrad_frames(const XgradParams& p, hipStream_t s);           // the LDS radix-2 frames kernel alone (no gather)
 
+// dmel_xgrad_len.hip: the scalar layer's gradient w.r.t. the waveform over clips of per-clip lengths (dmel_backward_x_lengths,
+// dmel_backward_x_dev_lengths).  Clip b is x[b, :lengths[b]] with Tc = lengths[b] / hop + 1 frames; L stays the row stride of x and grad_x,
+// T the row stride of grad_out and out.  grad_x[b, lengths[b]:] = 0; a length outside 1 ... L makes the row NaN.  The HTK mel layer
+// (spec_mode 0), power-of-two n_fft 32 ... 16384.
+struct XgradLenParams : XgradParams {
+    const int* lengths;         // (B) device, read by the kernels when they run
+    int fpt;                    // wave path: frames per tile (clip b's tiles are q < ceil(Tc / fpt); the others are neither written nor read)
+};
+hipError_t launch_xgrad_len(const XgradLenParams& p, hipStream_t s);
+hipError_t xgrad_len_prepare_attributes();
+
 // the multi-window layer's gradient w.r.t. the waveform.  grad_out / out are (B, K, M, T); every channel has its own window table, segment
 // (or frame) region and fp64 sums.  dmel_xgrad_wave_multi_kernel<N>: grid = count x B x tiles, channel slot w / ch_grid, channel = nibble
 // `slot` of ch_list (as FwdParams::ch_list); p.lam_dev is the base of the K device values (channel c reads lam_dev + c) or nullptr,

@@ -16,21 +16,12 @@
 // Kernel 2 (one workgroup per 4096 samples): overlap-add as a gather in increasing frame order (deterministic, no atomics) minus
 // the mean of the clip's gradient, which comes from fp64 per-frame sums left by kernel 1 (a third kernel used to subtract it).
 // A correctness-first path: about 10x the time of the fused forward at config 2.
-#include "dmel_kernels.h"
+#include "dmel_xgrad_plan.h"
 #include "dmel_ldsfft.h"
-#include "dmel_wavefft.h"
 
 namespace dmel {
 
-constexpr int kXgThreads = 256;
-
-// DMEL_FLAG_CHECK_NFFT (the optimized=True layer with x.requires_grad and lambd left on the device): the step's forward ran one
-// launch per candidate n_fft and only the one lambd asks for did the work (lam_prologue); the backward does the same
-__device__ __forceinline__ bool xgrad_not_this_nfft(const XgradParams& p)
-{
-    return p.check_nfft && p.lam_dev && lam_n_fft(__builtin_fabsf(*(const __attribute__((address_space(4))) float*)p.lam_dev)) != p.N;
-}
-
+// (dmel_xgrad_len.hip holds a copy of this kernel with per-clip bounds, dmel_xgrad_frames_len_kernel: a fix here belongs there too)
 template <bool TWLDS>
 __global__ void __launch_bounds__(kXgThreads) dmel_xgrad_frames_kernel(XgradParams p)
 {
@@ -128,8 +119,6 @@ __global__ void __launch_bounds__(kXgThreads) dmel_xgrad_frames_kernel(XgradPara
 // order (deterministic, no atomics) and subtracts the mean of the clip's gradient (models.py:38 removes the clip's DC, so the
 // gradient has none either).  The mean comes from the per-frame sums the first kernel left: every workgroup adds them up in the
 // same fixed order (strided partial sums, then a tree), so every chunk of a clip subtracts the same bits.
-constexpr int kXgChunk = 4096;
-
 __global__ void __launch_bounds__(256) dmel_xgrad_gather_kernel(XgradParams p)
 {
     __shared__ double red[256];
@@ -187,18 +176,7 @@ __device__ __forceinline__ void xstamp(int wgid, int wave, int lane, int idx)
 #define XSTAMP(i) do {} while (0)
 #endif
 
-template <int N> struct XgPlan {
-    using P = FftPlanSel<N, true>;
-    static constexpr int R = P::R, C = P::C, G = N / R, FPW = 64 / G;
-    // (2048 with 8 waves -- one workgroup per CU, 16-frame tiles: kernel 81 us against 77 at BASELINE config 3, combine pass 8.8 against 10.1)
-    static constexpr int WAVES = (N == 1024) ? 8 : 4;
-    static constexpr int LDS_MAX = 80 * 1024;                          // two workgroups per CU
-    static constexpr int SLOTS = WAVES * FPW, FPT = 2 * SLOTS, THREADS = 64 * WAVES;
-    static constexpr int SS = slot_stride_f2(N, R, C, 0, 0);          // float2 entries per slot
-    static constexpr int MINW = (N >= 2048) ? 2 : 4;                   // waves per SIMD the LDS footprint admits
-    static constexpr int PADP = (R == 16 && C > 1) ? 16 : 0;           // the C groups of 16 lanes write a plane on different banks
-};
-
+// (XgPlan<N>, the kernel's geometry: dmel_xgrad_plan.h)
 // the kernel itself: dmel_xgrad_wave_kernel<N> (scalar layer) and dmel_xgrad_wave_multi_kernel<N> (multi-window layer, XgradMultiParams)
 #define DMEL_XG_MULTI 0
 #include "dmel_xgrad_wave_body.inc"
@@ -349,34 +327,6 @@ __global__ void __launch_bounds__(256) dmel_xgrad_combine_multi_kernel(XgradComb
         const int i = lo + tid + 256 * r;
         if (i < hi) gx[i] = acc[r];
     });
-}
-
-template <int N> static size_t xgrad_wave_tw2_off(int M, int win_n)
-{
-    using PL = XgPlan<N>;
-    size_t gm = (size_t)(M + 1) * PL::FPT * sizeof(float);          // one zero row behind the last mel band
-    if (gm < PL::THREADS * sizeof(double)) gm = PL::THREADS * sizeof(double);
-    return (size_t)PL::SLOTS * PL::SS * 8 + (size_t)((win_n + 3) & ~3) * sizeof(float) + gm;
-}
-
-template <int N> static size_t xgrad_wave_lds(int M, int win_n)
-{
-    using PL = XgPlan<N>;
-    return xgrad_wave_tw2_off<N>(M, win_n) + (PL::C > 1 ? (size_t)PL::R * PL::C * 8 : 0) + 64;      // + one partial sum per wave
-}
-
-template <class F> static bool xgrad_with_plan(int n, F&& f)
-{
-    switch (n) {
-    case 32: f(IC<32>{}); return true;
-    case 64: f(IC<64>{}); return true;
-    case 128: f(IC<128>{}); return true;
-    case 256: f(IC<256>{}); return true;
-    case 512: f(IC<512>{}); return true;
-    case 1024: f(IC<1024>{}); return true;
-    case 2048: f(IC<2048>{}); return true;
-    default: return false;
-    }
 }
 
 // the wave-FFT path takes this shape (otherwise the LDS radix-2 kernels above run)

@@ -1,0 +1,62 @@
+// dmel_xgrad_plan.h -- what the two translation units of the gradient w.r.t. the waveform share: dmel_xgrad.hip (clips of n_points samples,
+// the scalar and the multi-window layer) and dmel_xgrad_len.hip (clips of per-clip lengths).  The geometry of the wave-FFT kernel
+// (csrc/dmel_xgrad_wave_body.inc), its LDS layout and the dispatch over n_fft.  (The launch parameters, XgradParams and XgradLenParams, are in dmel_kernels.h.)
+#pragma once
+#include "dmel_kernels.h"
+#include "dmel_wavefft.h"
+
+namespace dmel {
+
+constexpr int kXgThreads = 256;
+
+// DMEL_FLAG_CHECK_NFFT (the optimized=True layer with x.requires_grad and lambd left on the device): the step's forward ran one
+// launch per candidate n_fft and only the one lambd asks for did the work (lam_prologue); the backward does the same
+__device__ __forceinline__ bool xgrad_not_this_nfft(const XgradParams& p)
+{
+    return p.check_nfft && p.lam_dev && lam_n_fft(__builtin_fabsf(*(const __attribute__((address_space(4))) float*)p.lam_dev)) != p.N;
+}
+
+// samples of a clip per workgroup of the gather / combine kernels
+constexpr int kXgChunk = 4096;
+
+template <int N> struct XgPlan {
+    using P = FftPlanSel<N, true>;
+    static constexpr int R = P::R, C = P::C, G = N / R, FPW = 64 / G;
+    // (2048 with 8 waves -- one workgroup per CU, 16-frame tiles: kernel 81 us against 77 at BASELINE config 3, combine pass 8.8 against 10.1)
+    static constexpr int WAVES = (N == 1024) ? 8 : 4;
+    static constexpr int LDS_MAX = 80 * 1024;                          // two workgroups per CU
+    static constexpr int SLOTS = WAVES * FPW, FPT = 2 * SLOTS, THREADS = 64 * WAVES;
+    static constexpr int SS = slot_stride_f2(N, R, C, 0, 0);          // float2 entries per slot
+    static constexpr int MINW = (N >= 2048) ? 2 : 4;                   // waves per SIMD the LDS footprint admits
+    static constexpr int PADP = (R == 16 && C > 1) ? 16 : 0;           // the C groups of 16 lanes write a plane on different banks
+};
+
+template <int N> static size_t xgrad_wave_tw2_off(int M, int win_n)
+{
+    using PL = XgPlan<N>;
+    size_t gm = (size_t)(M + 1) * PL::FPT * sizeof(float);          // one zero row behind the last mel band
+    if (gm < PL::THREADS * sizeof(double)) gm = PL::THREADS * sizeof(double);
+    return (size_t)PL::SLOTS * PL::SS * 8 + (size_t)((win_n + 3) & ~3) * sizeof(float) + gm;
+}
+
+template <int N> static size_t xgrad_wave_lds(int M, int win_n)
+{
+    using PL = XgPlan<N>;
+    return xgrad_wave_tw2_off<N>(M, win_n) + (PL::C > 1 ? (size_t)PL::R * PL::C * 8 : 0) + 64;      // + one partial sum per wave
+}
+
+template <class F> static bool xgrad_with_plan(int n, F&& f)
+{
+    switch (n) {
+    case 32: f(IC<32>{}); return true;
+    case 64: f(IC<64>{}); return true;
+    case 128: f(IC<128>{}); return true;
+    case 256: f(IC<256>{}); return true;
+    case 512: f(IC<512>{}); return true;
+    case 1024: f(IC<1024>{}); return true;
+    case 2048: f(IC<2048>{}); return true;
+    default: return false;
+    }
+}
+
+}  // namespace dmel

@@ -1,15 +1,33 @@
 // dmel_xgrad_wave_body.inc -- the wave-FFT kernel of the gradient w.r.t. the waveform, included twice by dmel_xgrad.hip: DMEL_XG_MULTI = 0
 // makes dmel_xgrad_wave_kernel (the scalar layer), 1 makes dmel_xgrad_wave_multi_kernel (the multi-window layer: the channel slot comes out of
-// the relabelled workgroup index, as in dmel_fwd_multi_kernel).  The XG_* names below expand, for the scalar kernel, to exactly the tokens it
-// was written with, so that its code does not change.
+// the relabelled workgroup index, as in dmel_fwd_multi_kernel).  dmel_xgrad_len.hip includes it a third time with DMEL_XG_LEN = 1:
+// dmel_xgrad_wave_len_kernel, the scalar layer over clips of per-clip lengths (XgradLenParams).  The XG_* names below expand, for the two
+// kernels of dmel_xgrad.hip, to exactly the tokens they were written with, so that their code does not change.
 #if DMEL_XG_MULTI
 #define XG_KERNEL dmel_xgrad_wave_multi_kernel
 #define XG_PARAMS XgradMultiParams mp
 #define XG_BO bo
+#elif DMEL_XG_LEN
+#define XG_KERNEL dmel_xgrad_wave_len_kernel
+#define XG_PARAMS XgradLenParams p
+#define XG_BO b
 #else
 #define XG_KERNEL dmel_xgrad_wave_kernel
 #define XG_PARAMS XgradParams p
 #define XG_BO b
+#endif
+// sample-space bounds of a clip: L (also the row stride of x) and fl32(1 / L), or the clip's own length Lc (dmel_xgrad_wave_len_kernel); its
+// frames: T (also the row stride of grad_out / out), or Tc
+#if DMEL_XG_LEN
+#define XG_LC Lc
+#define XG_PSUM_L Lc
+#define XG_INV_L inv_Lc
+#define XG_TC Tc
+#else
+#define XG_LC L
+#define XG_PSUM_L p.L
+#define XG_INV_L p.inv_L
+#define XG_TC T
 #endif
 template <int N>
 __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KERNEL(XG_PARAMS)
@@ -60,6 +78,15 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
     XSTAMP(0);
     const int tiles = p.tiles, M = p.M, T = p.T, hop = p.hop, L = p.L;
     const int b = wg / tiles, tile = wg % tiles;
+#if DMEL_XG_LEN
+    // the clip is x[b, :Lc] (one scalar load: uniform over the workgroup) with Tc = Lc / hop + 1 frames; the frames past them are pad frames
+    // (zero mel gradient).  A tile whose first frame is a pad frame, and every tile of a clip whose length is outside 1 ... L, does nothing:
+    // dmel_xgrad_combine_len_kernel reads neither its segment nor its sum.
+    const ClipLen cl = clip_len(p.lengths, b, L, hop);
+    const int Lc = cl.Lc, Tc = cl.Tc;
+    const float inv_Lc = 1.0f / (float)Lc;
+    if (!cl.ok || tile * FPT >= Tc) return;
+#endif
 #if DMEL_XG_MULTI
     const int bo = b * mp.ch_out + ch;                            // the clip's row of grad_out / out: (B, K, M, T)
 #endif
@@ -71,8 +98,8 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
     const int tA = t0 + 2 * slot;
     const int f0 = tA * hop - N / 2;                              // first sample of frame tA; frame tA + 1 starts hop later
     // samples of both frames: plain offsets when the pair lies inside the clip, else clamped (and zeroed at windowing time)
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + (size_t)b * L, (unsigned)L * 4u);
-    const bool inside = __all((f0 >= 0) && (f0 + hop + N <= L));
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + (size_t)b * L, (unsigned)XG_LC * 4u);
+    const bool inside = __all((f0 >= 0) && (f0 + hop + N <= XG_LC));
     float xa[R], xc[R];
     if (inside) {
         static_for<0, R>([&](auto aa) {
@@ -83,8 +110,8 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
     } else {
         static_for<0, R>([&](auto aa) {
             constexpr int a = decltype(aa)::value;
-            xa[a] = buf_f32(rx, clampi(f0 + lg + G * a, L - 1) * 4);
-            xc[a] = buf_f32(rx, clampi(f0 + hop + lg + G * a, L - 1) * 4);
+            xa[a] = buf_f32(rx, clampi(f0 + lg + G * a, XG_LC - 1) * 4);
+            xc[a] = buf_f32(rx, clampi(f0 + hop + lg + G * a, XG_LC - 1) * 4);
         });
     }
     // everything else the prologue needs is requested before anything is waited for: the first batch of gm (four words per
@@ -99,7 +126,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
         static_for<0, 4>([&](auto uu) {
             constexpr int u = decltype(uu)::value;
             const int idx = base + u * THREADS, m = idx / FPT, t = t0 + idx % FPT;
-            const bool ok = idx < total && t < T;
+            const bool ok = idx < total && t < XG_TC;
             const unsigned o = ok ? (unsigned)(m * T + t) : 0u;
             v[u] = gb[o];
             y[u] = ysrc[o];
@@ -111,7 +138,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
             const int idx = base + u * THREADS, t = t0 + idx % FPT;
             if (idx < total) {
                 const float val = yb ? v[u] * expf(-y[u]) : v[u];
-                gm[idx] = t < T ? val : 0.f;
+                gm[idx] = t < XG_TC ? val : 0.f;
             }
         });
     };
@@ -129,7 +156,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
         constexpr int KB = 8;
         if ((reinterpret_cast<uintptr_t>(xc) & 15) == 0) {
             const float4* x4 = reinterpret_cast<const float4*>(xc);
-            const int n4 = L / 4;
+            const int n4 = XG_LC / 4;
             for (int base = 0; base < n4; base += THREADS * KB) {
                 float4 v[KB];
                 static_for<0, KB>([&](auto jj) {
@@ -145,7 +172,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
             }
             i0 = n4 * 4;
         }
-        for (int i = i0 + tid; i < L; i += THREADS) a0 += xc[i];
+        for (int i = i0 + tid; i < XG_LC; i += THREADS) a0 += xc[i];
         // lambd by value, or read here from the parameter's storage (a uniform scalar load; dmel_backward_x_dev: no host read)
         float win_denom = p.win_denom;
         if (p.lam_dev) win_denom = __builtin_fabsf(*(const __attribute__((address_space(4))) float*)p.lam_dev) + 1e-15f;   // scalar load: see lam_load
@@ -165,11 +192,11 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
         __syncthreads();
         float tot = 0.f;
         for (int q = 0; q < THREADS / 64; ++q) tot += redm[q];
-        mean = mean_quotient(tot, L, p.inv_L);
+        mean = mean_quotient(tot, XG_LC, XG_INV_L);
     } else {
         float wv[WPT];
         static_for<0, WPT>([&](auto ww) { constexpr int wi = decltype(ww)::value; const int n = tid + THREADS * wi; wv[wi] = p.win2[n < WN ? n : 0].x; });
-        mean = clip_mean_psum(p.psum, p.nchunks, b, p.L);
+        mean = clip_mean_psum(p.psum, p.nchunks, b, XG_PSUM_L);
         static_for<0, WPT>([&](auto ww) { constexpr int wi = decltype(ww)::value; const int n = tid + THREADS * wi; if (n < WN) win[n] = wv[wi]; });
     }
     if (total > 0) {
@@ -196,8 +223,8 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
             if (inside) z[a] = v2f{xa[a] - mean, xc[a] - mean} * splat(w);
             else {
                 const int ia = f0 + lg + G * a, ib = ia + hop;
-                const float va = (ia >= 0 && ia < L) ? xa[a] - mean : 0.f;
-                const float vb = (ib >= 0 && ib < L) ? xc[a] - mean : 0.f;
+                const float va = (ia >= 0 && ia < XG_LC) ? xa[a] - mean : 0.f;
+                const float vb = (ib >= 0 && ib < XG_LC) ? xc[a] - mean : 0.f;
                 z[a] = v2f{va, vb} * splat(w);
             }
         });
@@ -215,7 +242,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
     //   lane 0: N - G i itself; one padding step further when it starts an R*R block (mbA), bin 0 for i = 0 (mb0)
     {
         v2f wk[NPAIR], wn[NPAIR];
-        const bool hasA = tA < T, hasB = tA + 1 < T;
+        const bool hasA = tA < XG_TC, hasB = tA + 1 < XG_TC;
         // row k of the filterbank as (c0, c1, first column, columns): an HTK row has two non-zero columns, and consecutive lanes
         // read consecutive 16-byte entries (the coefficients themselves lie a whole row of M floats apart: 64 cache lines per
         // load).  Rows with more columns (a trained, dense bank: p.long_rows, uniform) add the rest from the matrix.
@@ -343,7 +370,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
     };
     const int K = __builtin_amdgcn_readfirstlane(div_hop(N + hop - 1));
     const int qs = __builtin_amdgcn_readfirstlane(div_hop(THREADS)), rs = THREADS - qs * hop;
-    const bool all_in = s0 >= 0 && s0 + span <= L;
+    const bool all_in = s0 >= 0 && s0 + span <= XG_LC;
     int t = div_hop(tid), m = tid - t * hop;
     float fsum = 0.f;
     for (int i = tid; i < span; i += THREADS) {
@@ -358,7 +385,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
         }
         seg[i] = acc;
         if (all_in) fsum += acc;
-        else { const long long ia = s0 + i; fsum += (ia >= 0 && ia < L) ? acc : 0.f; }
+        else { const long long ia = s0 + i; fsum += (ia >= 0 && ia < XG_LC) ? acc : 0.f; }
         m += rs; t += qs;
         if (m >= hop) { m -= hop; t += 1; }
     }
@@ -379,3 +406,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
 #undef XG_KERNEL
 #undef XG_PARAMS
 #undef XG_BO
+#undef XG_LC
+#undef XG_PSUM_L
+#undef XG_INV_L
+#undef XG_TC

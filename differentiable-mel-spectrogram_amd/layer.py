@@ -244,6 +244,88 @@ class _DmelFbDevFunction(torch.autograd.Function):
         return gx, dl, None, None, None, None, gfb, None, None, None, None
 
 
+class _DmelLenXFunction(torch.autograd.Function):
+    """forward(x, lengths) with a waveform gradient (``MelSpectrogramLayer(lengths_waveform_grad=True)`` and ``x.requires_grad``): the
+    launches of torch.ops.dmel.mel_spectrogram_lengths -- dmel_forward_dev_lengths, or dmel_forward_lengths when ``lam_host`` is given
+    (lambd_sync) -- with ``x``, ``lengths`` and the fp32 output kept for the backward.  backward: the same dot product for ``lambd`` and
+    dmel_backward_x_lengths for ``x``; with lambd on the device one dmel_backward_x_dev_lengths per n_fft the forward launched for
+    (DMEL_FLAG_CHECK_NFFT) over a NaN-filled grad_x, as _DmelFbDevFunction: no host read, the step can be captured into a HIP graph."""
+
+    @staticmethod
+    def forward(ctx, x, lengths, lambd, plan, lam_host, log, eps, out_dtype):
+        B = x.shape[0]
+        want_tangent = ctx.needs_input_grad[2]
+        want_x = ctx.needs_input_grad[0]
+        round_later = out_dtype == torch.bfloat16 and log and want_x       # see _DmelFunction.forward
+        kdtype = torch.float32 if round_later else out_dtype
+        out = torch.empty((B, 1, plan.n_mels, plan.n_time), dtype=kdtype, device=x.device)
+        tangent = torch.empty(out.shape, dtype=torch.float32, device=x.device) if want_tangent else None
+        scratch = torch.empty((plan.scratch_bytes(B),), dtype=torch.uint8, device=x.device)
+        lam = lambd.detach()
+        if lam.dtype != torch.float32:
+            lam = lam.to(torch.float32)
+        flags = capi.DMEL_FLAG_OUT_BF16 if kdtype == torch.bfloat16 else 0
+        ctx.cands = None
+        with _on_device(x.device):
+            if lam_host is not None:
+                plan.forward_lengths(x.data_ptr(), lengths.data_ptr(), B, lam_host, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
+                                     log, eps, _stream_ptr(x.device), scratch.data_ptr(), extra_flags=flags)
+            else:
+                plan.forward_dev_lengths(x.data_ptr(), lengths.data_ptr(), B, lam.data_ptr(), out.data_ptr(),
+                                         tangent.data_ptr() if want_tangent else None, log, eps, _stream_ptr(x.device), scratch.data_ptr(),
+                                         extra_flags=flags)
+                # what that call launched for (host-side bookkeeping of the plan: no device read)
+                n0, guards = plan.info()["n_fft"], plan.lambd_status()["guards"]
+                ctx.cands = [n0] + ([2 * n0] if guards & 2 else []) + ([n0 // 2] if guards & 1 else [])
+        ctx.plan, ctx.lam_host, ctx.log = plan, lam_host, bool(log)
+        ctx.lambd_shape, ctx.lambd_dtype = lambd.shape, lambd.dtype
+        ctx.want_tangent, ctx.want_x = want_tangent, want_x
+        saved = [scratch]
+        if want_tangent:
+            saved.append(tangent)
+        if want_x:
+            saved += [x, lengths, lam]
+            if log:
+                saved.append(out)
+        ctx.save_for_backward(*saved)
+        return out.to(torch.bfloat16) if round_later else out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        saved = list(ctx.saved_tensors)
+        scratch = saved.pop(0)
+        bf16 = grad_out.dtype == torch.bfloat16
+        g = grad_out
+        if not bf16 and g.dtype != torch.float32:
+            g = g.to(torch.float32)
+        if not g.is_contiguous():
+            g = g.contiguous()
+        dl = gx = None
+        with _on_device(g.device):
+            if ctx.want_tangent:
+                tangent = saved.pop(0)
+                dl = torch.empty(tuple(ctx.lambd_shape), dtype=torch.float32, device=g.device)
+                ctx.plan.backward_scratch(g.data_ptr(), tangent.data_ptr(), g.numel(), dl.data_ptr(), _stream_ptr(g.device), scratch.data_ptr(),
+                                          grad_bf16=bf16)
+                if ctx.lambd_dtype != torch.float32:
+                    dl = dl.to(ctx.lambd_dtype)
+            if ctx.want_x:
+                x, lengths, lam = saved.pop(0), saved.pop(0), saved.pop(0)
+                out = saved.pop(0) if ctx.log else None
+                g32 = g.to(torch.float32)
+                optr = out.data_ptr() if ctx.log else None
+                if ctx.cands is None:
+                    gx = torch.empty_like(x)
+                    ctx.plan.backward_x_lengths(x.data_ptr(), lengths.data_ptr(), x.shape[0], ctx.lam_host, g32.data_ptr(), optr, gx.data_ptr(),
+                                                ctx.log, _stream_ptr(g.device))
+                else:
+                    gx = torch.full_like(x, float("nan"))
+                    for n in ctx.cands:
+                        ctx.plan.backward_x_dev_lengths(x.data_ptr(), lengths.data_ptr(), x.shape[0], lam.data_ptr(), n, g32.data_ptr(), optr,
+                                                        gx.data_ptr(), ctx.log, _stream_ptr(g.device), extra_flags=capi.DMEL_FLAG_CHECK_NFFT)
+        return gx, None, dl, None, None, None, None, None
+
+
 class SlotInput:
     """A batch handed to the layer BY ADDRESS (round 5): ``cell`` is a one-element int64 device tensor holding the address of a contiguous
     fp32 ``(batch, n_points)`` tensor on the same device; the fused forward reads that address when it RUNS (``DMEL_FLAG_X_INDIRECT``).
@@ -344,13 +426,22 @@ class MelSpectrogramLayer(nn.Module):
     a captured step sees what the tensor holds when it replays): a length outside ``1 ... n_points`` makes that clip's rows NaN (int64
     lengths are clamped on the device before they are narrowed to int32, so no value wraps into the valid range).  fp64 clips lose their
     own mean in fp64 before the cast to fp32, as ``forward(x)`` does.
-    HTK bank with ``optimized=True`` only, no waveform gradient, clips that start at sample 0.
+    HTK bank with ``optimized=True`` only, clips that start at sample 0, and by default no waveform gradient.
+    ``lengths_waveform_grad=True`` (keyword-only, off by default: such a forward keeps ``x``, ``lengths`` and the fp32 output alive until the
+    backward) lets ``forward(x, lengths)`` take an ``x`` that requires grad.  The output and ``lambd.grad`` keep their bits;
+    ``x.grad[b, :lengths[b]]`` is what autograd through the reference layer built with ``n_points = lengths[b]`` returns for that clip and
+    the cotangent of its valid frames (so the gradient's own mean is taken over the clip's samples), ``x.grad[b, lengths[b]:]`` is ``+0.0``,
+    the cotangent of pad frames is never read, and a length outside ``1 ... n_points`` makes the row ``x.grad[b]`` NaN.  With
+    ``lambd_sync=False`` the step has no host read and can be captured.  A ``SlotInput`` carries no gradient (it is an address, not a
+    tensor of the graph); ``learnable_fb`` and ``optimized=False`` refuse ``lengths`` with or without the flag.
     """
 
     def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1,
                  device="cpu", optimized=False, normalize_window=False, *, log=False, eps=1e-10, learnable_fb=False,
-                 out_dtype=torch.float32, lambd_sync=False, mfma="fp32", save_spec=True):
+                 out_dtype=torch.float32, lambd_sync=False, mfma="fp32", save_spec=True, lengths_waveform_grad=False):
         super().__init__()
+        self.lengths_waveform_grad = bool(lengths_waveform_grad)      # forward(x, lengths) accepts an x that requires grad (opt-in: that
+                                                                      # forward keeps x, lengths and the fp32 output alive until the backward)
         if not torch.is_tensor(init_lambd):
             init_lambd = torch.tensor(float(init_lambd), dtype=torch.float32)
         if mfma not in ("fp32", "bf16x3"):
@@ -449,11 +540,16 @@ class MelSpectrogramLayer(nn.Module):
     # -- forward ------------------------------------------------------------------------------
     def _forward_lengths(self, x, lengths):
         """forward(x, lengths): torch.ops.dmel.mel_spectrogram_lengths (the hot path's C++ autograd node over dmel_forward_dev_lengths, or
-        dmel_forward_lengths with lambd_sync).  Shape, dtype and device of ``lengths`` are checked here; its values never leave the device."""
+        dmel_forward_lengths with lambd_sync).  Shape, dtype and device of ``lengths`` are checked here; its values never leave the device.
+        With ``lengths_waveform_grad=True`` an ``x`` that requires grad takes _DmelLenXFunction instead: the same launches, and a backward to
+        the waveform."""
+        want_x = self.lengths_waveform_grad and torch.is_grad_enabled() and not isinstance(x, SlotInput) and x.requires_grad
         if self.mel_fb is not None:
-            raise RuntimeError("per-clip lengths run the HTK bank only: learnable_fb=True does not take lengths")
+            raise RuntimeError("per-clip lengths run the HTK bank only: learnable_fb=True does not take lengths"
+                               + (" (and has no waveform gradient with them)" if want_x else ""))
         if not self.optimized:
-            raise RuntimeError("per-clip lengths need optimized=True (the optimized=False branch's n_fft = 2 n_points depends on the clip length)")
+            raise RuntimeError("per-clip lengths need optimized=True (the optimized=False branch's n_fft = 2 n_points depends on the clip length)"
+                               + ("; the waveform gradient of per-clip lengths needs it too" if want_x else ""))
         if not torch.is_tensor(lengths):
             raise TypeError(f"lengths must be a 1-D integer tensor, got {type(lengths).__name__}")
         if lengths.dtype not in (torch.int32, torch.int64):
@@ -480,13 +576,17 @@ class MelSpectrogramLayer(nn.Module):
             return _len_op()(x.view(), lengths, lam, self._plan_for(x.device).handle, flags | capi.DMEL_FLAG_X_INDIRECT, self.eps, False, bf16)
         if not x.is_cuda:
             raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
-        if x.requires_grad:
+        if x.requires_grad and not self.lengths_waveform_grad:
             raise RuntimeError("per-clip lengths have no waveform gradient: pass x.detach()")
         if self.lambd.device != x.device:
             raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
         xf = x if x.dtype == torch.float32 else _to_f32_lengths(x, lengths)
         if not xf.is_contiguous():
             xf = xf.contiguous()
+        if xf.requires_grad and torch.is_grad_enabled():
+            # lengths_waveform_grad=True: the gradient flows back through the conversions above (the fp64 path's masked mean included)
+            return _DmelLenXFunction.apply(xf, lengths, self.lambd, self._plan_for(x.device), self._lambd_host() if self.lambd_sync else None,
+                                           self.log, self.eps, self.out_dtype)
         return _len_op()(xf, lengths, lam, self._plan_for(x.device).handle, flags, self.eps, self.lambd_sync, bf16)
 
     def forward(self, x, lengths=None):

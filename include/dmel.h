@@ -80,7 +80,7 @@ typedef struct dmel_plan dmel_plan;
                                    caller-supplied DENSE filterbank) run on the bf16 matrix pipe as three split-bf16 products per fp32
                                    product (hi hi + lo hi + hi lo, fp32 accumulate: ~2e-5 relative, inside the 1e-4 bar; 16 x the fp32 MFMA
                                    rate).  Default: exact fp32 MFMA (v_mfma_f32_16x16x4_f32).  The HTK bank's banded contraction ignores it. */
-#define DMEL_FLAG_CHECK_NFFT 16u /* dmel_backward_x_dev only: the kernels do their work only if the device value of lambd asks for exactly the
+#define DMEL_FLAG_CHECK_NFFT 16u /* dmel_backward_x_dev(_lengths) only: the kernels do their work only if the device value of lambd asks for exactly the
                                    `n_fft` of this call (time_frequency.py:39,60-65 evaluated on the device) and otherwise leave grad_x
                                    untouched.  For the optimized=True layer whose forward (dmel_forward_dev) issued one launch per candidate
                                    n_fft: the caller fills grad_x with NaN and issues one dmel_backward_x_dev per candidate. */
@@ -351,6 +351,18 @@ dmel_status dmel_backward_x_dev(dmel_plan* plan, const float* x, int32_t batch, 
                                 const float* grad_out, const float* out, float* grad_x, void* stream);
 dmel_status dmel_backward_x_spec_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft, uint32_t flags,
                                      const float* grad_spec, float* grad_x, void* stream);
+/* dmel_backward_x / dmel_backward_x_dev over clips of per-clip lengths: the backward of dmel_forward_lengths / dmel_forward_dev_lengths
+ * (`lengths` as there: device, read by the kernels only).  With Lc = lengths[b] and Tc = Lc / hop_length + 1, grad_x[b, :Lc] is what
+ * dmel_backward_x of a plan with n_points = Lc returns for x[b, :Lc] and grad_out[b, :, :Tc] (the clip's own mean, and the mean of its
+ * gradient, over Lc samples); grad_x[b, Lc:] = +0.  x[b, Lc:], grad_out[b, :, Tc:] and out[b, :, Tc:] are never read; tiles of pad frames
+ * are not transformed.  A length outside 1 ... n_points makes the row grad_x[b, :] NaN and changes no other row.  grad_out, out and
+ * grad_x keep their row strides (n_time, n_points).  Flags: DMEL_FLAG_LOG and, for dmel_backward_x_dev_lengths, DMEL_FLAG_CHECK_NFFT
+ * (as dmel_backward_x_dev: one call per n_fft the forward launched for, over a NaN-filled grad_x).  The HTK bank and power-of-two n_fft
+ * 32 ... 16384 only (otherwise DMEL_ERR_UNSUPPORTED).  With all lengths at n_points the result is dmel_backward_x's, bit for bit. */
+dmel_status dmel_backward_x_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, float lambd, uint32_t flags,
+                                    const float* grad_out, const float* out, float* grad_x, void* stream);
+dmel_status dmel_backward_x_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                        int32_t n_fft, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream);
 
 /* Power spectrogram only, (batch, n_fft/2+1, n_time) fp32 = time_frequency.differentiable_spectrogram
  * (time_frequency.py:32-58, optimized branch) applied per clip; remove_dc != 0 adds models.py:38. */
