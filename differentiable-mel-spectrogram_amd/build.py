@@ -5,6 +5,7 @@ source tree):
                     against the installed torch's headers, no device code"""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -15,8 +16,13 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libdmel_hip.so")
 TORCH_LIB_PATH = os.path.join(PKG_DIR, "libdmel_torch.so")
 OBJ_DIR = os.path.join(PKG_DIR, "build")
-SOURCES = ["dmel_fwd.hip", "dmel_fwd_len.hip", "dmel_fwd_band.hip", "dmel_aux.hip", "dmel_big.hip", "dmel_xgrad.hip", "dmel_xgrad_len.hip", "dmel_api.cpp", "dmel_comm.cpp"]
-HEADERS = [os.path.join(CSRC, "dmel_kernels.h"), os.path.join(CSRC, "dmel_fwd_body.inc"), os.path.join(CSRC, "dmel_fwd_log.h"),os.path.join(CSRC, "dmel_xgrad_wave_body.inc"), os.path.join(CSRC, "dmel_xgrad_plan.h"), os.path.join(CSRC, "dmel_ldsfft.h"), os.path.join(CSRC, "dmel_wavefft.h"), os.path.join(os.path.dirname(PKG_DIR), "include", "dmel.h")]
+# the fused forward's three sources are compiled FWD_PARTS times each (-DDMEL_FWD_SPLIT -DDMEL_FWD_PART=k): their large instantiations in parallel
+SPLIT_SOURCES = ["dmel_fwd.hip", "dmel_fwd_len.hip", "dmel_fwd_band.hip"]
+FWD_PARTS = 4
+SOURCES = SPLIT_SOURCES + ["dmel_aux.hip", "dmel_big.hip", "dmel_xgrad.hip", "dmel_xgrad_len.hip", "dmel_api.cpp", "dmel_comm.cpp"]
+PUBLIC_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "dmel.h")
+# every object is stale when any shared file under csrc/ is newer: a new header needs no entry here
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + [PUBLIC_HEADER]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 
@@ -34,17 +40,12 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-# csrc/dmel_fwd.hip, csrc/dmel_fwd_len.hip and csrc/dmel_fwd_band.hip are compiled FWD_PARTS times each (-DDMEL_FWD_SPLIT -DDMEL_FWD_PART=k): their large
-# instantiations in parallel
-FWD_PARTS = 4
-
-
 def _units():
     """(source path, object path, extra flags) of every translation unit"""
     for src in SOURCES:
         sp = os.path.join(CSRC, src)
         stem = os.path.splitext(src)[0]
-        if src in ("dmel_fwd.hip", "dmel_fwd_len.hip", "dmel_fwd_band.hip"):
+        if src in SPLIT_SOURCES:
             for k in range(FWD_PARTS):
                 yield sp, os.path.join(OBJ_DIR, f"{stem}_part{k}.o"), ["-DDMEL_FWD_SPLIT", f"-DDMEL_FWD_PART={k}"]
         else:
@@ -97,7 +98,7 @@ def build_torch(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("torch is not importable: libdmel_torch.so cannot be built")
     tdir = list(spec.submodule_search_locations)[0]
     src = os.path.join(CSRC, "dmel_torch.cpp")
-    if not (force or _stale(TORCH_LIB_PATH, [src, HEADERS[-1], LIB_PATH])):
+    if not (force or _stale(TORCH_LIB_PATH, [src, PUBLIC_HEADER, LIB_PATH])):
         return TORCH_LIB_PATH
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++")
     if not cxx:

@@ -778,6 +778,29 @@ dmel_status big_tables_for(dmel_plan* pl, int N, dmel_plan::BigTab* out, const f
     return DMEL_OK;
 }
 
+// the window's centre in table coordinates.  The whole-clip window of the optimized=False branches is centred at L/2 as a real number inside its
+// L = n_fft/2 entries (time_frequency.py:24), which torch.stft places (n_fft - L) / 2 = L/2 (integer) entries into the frame
+float window_center(int N, int win_half) { return win_half ? (float)((N / 2) / 2) + (float)(N / 2) / 2.0f : (float)N / 2.0f; }
+
+// the big path's plan-owned window table (N entries) and per-workgroup sequences (need_z entries, transforms longer than LDS) grow here
+dmel_status grow_big_workspace(dmel_plan* pl, int N, size_t need_z, hipStream_t s)
+{
+    if ((size_t)N <= pl->big_win_n && need_z <= pl->big_z_n) return DMEL_OK;
+    if (is_capturing(s)) return fail(DMEL_ERR_INVALID_ARGUMENT, "workspace must grow but the stream is capturing: run one call eagerly first");
+    DMEL_HIP(hipDeviceSynchronize());
+    if ((size_t)N > pl->big_win_n) {
+        (void)hipFree(pl->big_win); pl->big_win = nullptr; pl->big_win_n = 0;
+        DMEL_HIP(hipMalloc(&pl->big_win, (size_t)N * sizeof(float2)));
+        pl->big_win_n = (size_t)N;
+    }
+    if (need_z > pl->big_z_n) {
+        (void)hipFree(pl->big_z); pl->big_z = nullptr; pl->big_z_n = 0;
+        DMEL_HIP(hipMalloc(&pl->big_z, need_z * sizeof(float2)));
+        pl->big_z_n = need_z;
+    }
+    return DMEL_OK;
+}
+
 // One launch (plus, when needed, the partial-sum / window-table kernel in front of it) of the forward for a given n_fft.
 // `lam` says where lambd comes from and whether the kernels check it against N (dmel_kernels.h); `sc` is the scratch of
 // this call.  Shared by every entry point; the plan mutex is held by the caller.
@@ -806,9 +829,7 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     NfftTables* tb = nullptr;
     dmel_status st = build_tables(pl, N, &tb);
     if (st != DMEL_OK) return st;
-    // the whole-clip window of the optimized=False branches is centred at L/2 as a real number inside its L = n_fft/2 entries
-    // (time_frequency.py:24), which torch.stft places (n_fft - L) / 2 = L/2 (integer) entries into the frame
-    const float center = win_half ? (float)((N / 2) / 2) + (float)(N / 2) / 2.0f : (float)N / 2.0f;
+    const float center = window_center(N, win_half);
     if (big) {
         // ---- lengths the LDS kernels do not reach: global-memory FFT / Bluestein (dmel_big.hip) ------------------------
         dmel_plan::BigTab bt;
@@ -844,20 +865,7 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
         const long long units = (long long)batch * (pair ? (pl->T + 1) / 2 : pl->T);
         const int grid = dmel::big_grid(units, bt.M);
         const size_t need_z = dmel::big_uses_global(bt.M) ? (size_t)grid * bt.M : 0;
-        if ((size_t)N > pl->big_win_n || need_z > pl->big_z_n) {
-            if (is_capturing(s)) return fail(DMEL_ERR_INVALID_ARGUMENT, "workspace must grow but the stream is capturing: run one call eagerly first");
-            DMEL_HIP(hipDeviceSynchronize());
-            if ((size_t)N > pl->big_win_n) {
-                (void)hipFree(pl->big_win); pl->big_win = nullptr; pl->big_win_n = 0;
-                DMEL_HIP(hipMalloc(&pl->big_win, (size_t)N * sizeof(float2)));
-                pl->big_win_n = (size_t)N;
-            }
-            if (need_z > pl->big_z_n) {
-                (void)hipFree(pl->big_z); pl->big_z = nullptr; pl->big_z_n = 0;
-                DMEL_HIP(hipMalloc(&pl->big_z, need_z * sizeof(float2)));
-                pl->big_z_n = need_z;
-            }
-        }
+        if ((st = grow_big_workspace(pl, N, need_z, s)) != DMEL_OK) return st;
         const bool need_sums = remove_dc && !*sums_done;
         const size_t m0 = prof_mark(pl, s);
         {
@@ -982,19 +990,14 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     }
     if (grid > 0x7fffffffLL) return fail(DMEL_ERR_INVALID_ARGUMENT, "too many tiles for one launch");
     if (grid <= dmel::forward_resident_workgroups(N, mode)) fp.flags |= dmel::kFwdEdgeFirst;      // one round: see the kernel's prologue
-    if (lengths) {
-        dmel::FwdLenParams lp{};
-        static_cast<dmel::FwdParams&>(lp) = fp;
-        lp.lengths = lengths;
-        DMEL_HIP(dmel::launch_forward_len(N, mode, tpw, lp, (int)grid, s));
-    } else if (ml && ml->edges) {
-        dmel::FwdBandParams bp{};
-        static_cast<dmel::FwdParams&>(bp) = fp;
-        for (int c = 0; c <= dmel::kMaxChannels; ++c) bp.band_edges[c] = ml->edges[std::min(c, ml->channels)];
-        DMEL_HIP(dmel::launch_forward_band(N, mode, tpw, bp, (int)grid, s));
-    } else {
-        DMEL_HIP(dmel::launch_forward(N, mode, tpw, fp, (int)grid, s));
-    }
+    // the kernel follows the parameter type: per-clip lengths, the band-split layer's row ranges, or neither
+    const bool band = ml && ml->edges;
+    dmel::FwdLenParams lp{};
+    lp.lengths = lengths;
+    dmel::FwdBandParams bp{};
+    for (int c = 0; band && c <= dmel::kMaxChannels; ++c) bp.band_edges[c] = ml->edges[std::min(c, ml->channels)];
+    auto launch = [&](auto& q) { static_cast<dmel::FwdParams&>(q) = fp; return dmel::launch_forward(N, mode, tpw, q, (int)grid, s); };
+    DMEL_HIP(lengths ? launch(lp) : band ? launch(bp) : launch(fp));
     prof_span(pl, m1, prof_mark(pl, s), 1);
     pl->info.kernel_path = 0; pl->info.frames_per_tile = fpt; pl->info.grid_fwd = (int)grid;
     pl->info.fb_blocks = tb->n_entries; pl->info.fb_blocks_dense = tb->n_dense;
@@ -1291,12 +1294,7 @@ dmel_status dmel_plan_create(const dmel_config* cfg, dmel_plan** plan)
     DMEL_HIP(hipGetDeviceProperties(&prop, dev));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(DMEL_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", libdmel_hip is built for gfx950 only");
-    DMEL_HIP(dmel::forward_prepare_attributes());
-    DMEL_HIP(dmel::forward_len_prepare_attributes());
-    DMEL_HIP(dmel::forward_band_prepare_attributes());
-    DMEL_HIP(dmel::xgrad_prepare_attributes());
-    DMEL_HIP(dmel::xgrad_len_prepare_attributes());
-    DMEL_HIP(dmel::big_prepare_attributes());
+    DMEL_HIP(dmel::prepare_attributes());
     dmel_plan* pl = new (std::nothrow) dmel_plan();
     if (!pl) return fail(DMEL_ERR_OUT_OF_MEMORY, "host allocation failed");
     pl->cfg = *cfg;
@@ -2427,29 +2425,13 @@ dmel_status backward_x_impl(dmel_plan* plan, const float* x, int32_t batch, floa
     // the big path's window table and (sequences longer than LDS) per-workgroup workspace are plan-owned, like the forward's
     const long long units = (long long)batch * ((plan->T + 1) / 2);
     const int big_grid = big ? dmel::big_grid(units, bt.M) : 0;
-    if (big) {
-        const size_t need_z = dmel::big_uses_global(bt.M) ? (size_t)big_grid * bt.M : 0;
-        if ((size_t)N > plan->big_win_n || need_z > plan->big_z_n) {
-            if (is_capturing(s)) return fail(DMEL_ERR_INVALID_ARGUMENT, "workspace must grow but the stream is capturing: run one call eagerly first");
-            DMEL_HIP(hipDeviceSynchronize());
-            if ((size_t)N > plan->big_win_n) {
-                (void)hipFree(plan->big_win); plan->big_win = nullptr; plan->big_win_n = 0;
-                DMEL_HIP(hipMalloc(&plan->big_win, (size_t)N * sizeof(float2)));
-                plan->big_win_n = (size_t)N;
-            }
-            if (need_z > plan->big_z_n) {
-                (void)hipFree(plan->big_z); plan->big_z = nullptr; plan->big_z_n = 0;
-                DMEL_HIP(hipMalloc(&plan->big_z, need_z * sizeof(float2)));
-                plan->big_z_n = need_z;
-            }
-        }
-    }
+    if (big && (st = grow_big_workspace(plan, N, dmel::big_uses_global(bt.M) ? (size_t)big_grid * bt.M : 0, s)) != DMEL_OK) return st;
     // clip sums + window table (the tangent half of the table is not used here)
     dmel::PrepParams pp{};
     pp.x = x; pp.psum = sc.psum; pp.win2 = big ? plan->big_win : sc.win;
     pp.B = batch; pp.L = plan->cfg.n_points; pp.nchunks = plan->nchunks; pp.chunk = plan->chunk;
     pp.N = N; pp.normalize = plan->cfg.normalize_window; pp.win_half = win_half;
-    pp.center = win_half ? (float)((N / 2) / 2) + (float)(N / 2) / 2.0f : (float)N / 2.0f;      // as launch_forward_n
+    pp.center = window_center(N, win_half);
     pp.lam.dev = lambd_dev; pp.lam.val = lambd_dev ? 0.f : lambd; pp.lam.role = dmel::kLamQuiet;
     pp.lengths = lengths;                                   // the partial sums then stop at the clip's end, as in the forward
     // short clips with the plain Gaussian window: the wave-FFT kernel evaluates the window and adds up its clip itself

@@ -25,16 +25,10 @@
 //
 // Reference semantics restated here: models.py:33-56 (layer forward), time_frequency.py:21-30
 // (window), :32-58 (STFT, |.|^2), models.py:73 (log).
-#include "dmel_kernels.h"
-#include "dmel_wavefft.h"
-
+#include "dmel_fwd_dispatch.h"
 
 namespace dmel {
 
-
-#ifndef DMEL_FWD_PART
-#define DMEL_FWD_PART 0
-#endif
 #if DMEL_FWD_PART == 0
 // ---- prep kernel: per-clip partial sums (DC removal, models.py:38) + window tables -----------
 __global__ void __launch_bounds__(kThreads) dmel_prep_kernel(PrepParams p)
@@ -179,116 +173,31 @@ __device__ __forceinline__ void stamp_place(int wgid, int wave, int lane)
 #include "dmel_fwd_body.inc"
 #undef DMEL_FWD_MULTI
 
-template <int N, int MODE, int TPW> static hipError_t launch_one(const FwdParams& p, int grid, hipStream_t s)
-{
-    constexpr FftGeom g = geom_mode<N, MODE>();
-    constexpr int lds = g.LDS_BYTES;
-    if (p.ch_out) hipLaunchKernelGGL((dmel_fwd_multi_kernel<N, MODE, TPW>), dim3(grid), dim3(g.THREADS), lds, s, p);
-    else hipLaunchKernelGGL((dmel_fwd_kernel<N, MODE, TPW>), dim3(grid), dim3(g.THREADS), lds, s, p);
-    return hipGetLastError();
-}
-
 // two tiles per workgroup are built for the sizes whose launches are large enough to use them (forward_tiles_per_wg)
 template <int N, bool PAIR> constexpr bool has_tpw2() { return N >= 256 && (N <= 512 || (N == 1024 && geom<N, PAIR>().G == 64)); }   // (32 x 32 plan at 1024: 16-frame tiles, two of them spill)
 
 // kTrainH (dense contraction on the bf16 matrix pipe) exists for the sizes whose frames live inside one wave, one tile per workgroup
 template <int N> constexpr bool has_hsplit() { return N >= kHsplitMinNfft && N <= kHsplitMaxNfft; }
 
-template <int N, int MODE> static hipError_t launch_mode(int tpw, const FwdParams& p, int grid, hipStream_t s)
-{
-    if constexpr (MODE == kTrainH) {
-        if constexpr (has_hsplit<N>()) { if (tpw == 1) return launch_one<N, MODE, 1>(p, grid, s); }
-        return hipErrorInvalidValue;
-    } else if constexpr (MODE == kTrainW) {
-        if constexpr (wlc_size(N)) { if (tpw == 1) return launch_one<N, MODE, 1>(p, grid, s); }
-        return hipErrorInvalidValue;
-    } else if constexpr (MODE == kTrainWW) {
-        if constexpr (wlc_wide_size(N)) { if (tpw == 1) return launch_one<N, MODE, 1>(p, grid, s); }
-        return hipErrorInvalidValue;
-    } else {
-        if constexpr (has_tpw2<N, mode_pairs(MODE)>()) { if (tpw == 2) return launch_one<N, MODE, 2>(p, grid, s); }
-        if (tpw != 1) return hipErrorInvalidValue;
-        return launch_one<N, MODE, 1>(p, grid, s);
+// this file's variant (dmel_fwd_dispatch.h): every mode; the contraction variants one tile per workgroup, the others also two where has_tpw2
+struct FwdVariant {
+    using Params = FwdParams;
+    using Modes = FwdModes<kTrain, kInfer, kSpec, kSpecTrain, kTrainH, kTrainW, kTrainWW>;
+    template <int N, int MODE, int TPW> static constexpr bool exists()
+    {
+        if (MODE == kTrainH) return TPW == 1 && has_hsplit<N>();
+        if (MODE == kTrainW) return TPW == 1 && wlc_size(N);
+        if (MODE == kTrainWW) return TPW == 1 && wlc_wide_size(N);
+        return TPW == 1 || (TPW == 2 && has_tpw2<N, mode_pairs(MODE)>());
     }
-}
-
-template <int N> static hipError_t launch_n(int mode, int tpw, const FwdParams& p, int grid, hipStream_t s)
-{
-    switch (mode) {
-        case kTrain: return launch_mode<N, kTrain>(tpw, p, grid, s);
-        case kInfer: return launch_mode<N, kInfer>(tpw, p, grid, s);
-        case kSpec: return launch_mode<N, kSpec>(tpw, p, grid, s);
-        case kSpecTrain: return launch_mode<N, kSpecTrain>(tpw, p, grid, s);
-        case kTrainH: return launch_mode<N, kTrainH>(tpw, p, grid, s);
-        case kTrainW: return launch_mode<N, kTrainW>(tpw, p, grid, s);
-        case kTrainWW: return launch_mode<N, kTrainWW>(tpw, p, grid, s);
-    }
-    return hipErrorInvalidValue;
-}
-
-// -DDMEL_ONLY_NFFT=<n>: development builds that instantiate one transform size only (tools/build_variant.sh).  Never defined for
-// libdmel_hip.so.
-// -DDMEL_FWD_SPLIT -DDMEL_FWD_PART=<k>, k = 0..3: build.py compiles this file four times for libdmel_hip.so so that the
-// instantiations of the large transforms -- minutes of compile time each -- build in parallel: part 0 holds everything that is
-// not a template instantiation plus the sizes up to 512, parts 1-3 hold 1024 / 2048 + 16384 / 4096 + 8192 and nothing else.
-// Without DMEL_FWD_SPLIT (the tools' one-command builds) everything is in this one translation unit.
-#ifndef DMEL_FWD_PART
-#define DMEL_FWD_PART 0
-#endif
-constexpr int fwd_part_of(int n) { return n <= 512 ? 0 : n == 1024 ? 1 : (n == 2048 || n == 16384) ? 2 : 3; }
-#if defined(DMEL_ONLY_NFFT)
-#define DMEL_FWD_HERE(n) ((n) == DMEL_ONLY_NFFT)
-#elif defined(DMEL_FWD_SPLIT)
-#define DMEL_FWD_HERE(n) (fwd_part_of(n) == DMEL_FWD_PART)
-#else
-#define DMEL_FWD_HERE(n) true
-#endif
-template <int N> static hipError_t launch_size(int mode, int tpw, const FwdParams& p, int grid, hipStream_t s)
-{
-    if constexpr (DMEL_FWD_HERE(N)) return launch_n<N>(mode, tpw, p, grid, s);
-    else return hipErrorInvalidValue;
-}
-
-#define DMEL_CAT2(a, b) a##b
-#define DMEL_CAT(a, b) DMEL_CAT2(a, b)
-hipError_t DMEL_CAT(launch_forward_part, DMEL_FWD_PART)(int n_fft, int mode, int tpw, const FwdParams& p, int grid, hipStream_t s)
-{
-    switch (n_fft) {
-        case 32: return launch_size<32>(mode, tpw, p, grid, s);
-        case 64: return launch_size<64>(mode, tpw, p, grid, s);
-        case 128: return launch_size<128>(mode, tpw, p, grid, s);
-        case 256: return launch_size<256>(mode, tpw, p, grid, s);
-        case 512: return launch_size<512>(mode, tpw, p, grid, s);
-        case 1024: return launch_size<1024>(mode, tpw, p, grid, s);
-        case 2048: return launch_size<2048>(mode, tpw, p, grid, s);
-        case 4096: return launch_size<4096>(mode, tpw, p, grid, s);
-        case 8192: return launch_size<8192>(mode, tpw, p, grid, s);
-        case 16384: return launch_size<16384>(mode, tpw, p, grid, s);
-    }
-    return hipErrorInvalidValue;
-}
+    template <int N, int MODE, int TPW> static constexpr void (*kernels[])(FwdParams) = {dmel_fwd_kernel<N, MODE, TPW>, dmel_fwd_multi_kernel<N, MODE, TPW>};
+    static int pick(const FwdParams& p) { return p.ch_out ? 1 : 0; }
+};
+DMEL_FWD_PARTS_OF(FwdVariant)
 
 #if DMEL_FWD_PART == 0
-#if defined(DMEL_FWD_SPLIT) && !defined(DMEL_ONLY_NFFT)
-#define DMEL_FWD_PARTS 1
-hipError_t launch_forward_part1(int, int, int, const FwdParams&, int, hipStream_t);
-hipError_t launch_forward_part2(int, int, int, const FwdParams&, int, hipStream_t);
-hipError_t launch_forward_part3(int, int, int, const FwdParams&, int, hipStream_t);
-hipError_t forward_prepare_attributes_part1();
-hipError_t forward_prepare_attributes_part2();
-hipError_t forward_prepare_attributes_part3();
-#endif
-hipError_t launch_forward(int n_fft, int mode, int tpw, const FwdParams& p, int grid, hipStream_t s)
-{
-#ifdef DMEL_FWD_PARTS
-    switch (fwd_part_of(n_fft)) {
-        case 1: return launch_forward_part1(n_fft, mode, tpw, p, grid, s);
-        case 2: return launch_forward_part2(n_fft, mode, tpw, p, grid, s);
-        case 3: return launch_forward_part3(n_fft, mode, tpw, p, grid, s);
-    }
-#endif
-    return launch_forward_part0(n_fft, mode, tpw, p, grid, s);
-}
+hipError_t launch_forward(int n_fft, int mode, int tpw, const FwdParams& p, int grid, hipStream_t s) { return fwd_launch<FwdVariant>(n_fft, mode, tpw, p, grid, s); }
+hipError_t forward_prepare_attributes() { return fwd_set_attr<FwdVariant>(); }
 
 bool forward_has_hsplit(int n_fft) { return n_fft >= kHsplitMinNfft && n_fft <= kHsplitMaxNfft && (n_fft & (n_fft - 1)) == 0; }
 bool forward_has_wlc(int n_fft) { return wlc_size(n_fft); }
@@ -296,22 +205,10 @@ bool forward_wlc_one_frame(int n_fft) { return wlc_size(n_fft) && n_fft >= 2048;
 bool forward_has_wlc_wide(int n_fft) { return wlc_wide_size(n_fft); }
 bool forward_window_in_lds(int n_fft) { return n_fft >= kMinFastNfft && n_fft <= kWinLdsMaxNfft; }
 
-// One place that maps a run-time (n_fft, pair) to the compile-time geometry
+// the geometry of the plan for a run-time (n_fft, pair)
 template <class F> static bool with_geom(int n_fft, bool pair, F&& f)
 {
-    switch (n_fft) {
-        case 32: f(pair ? geom<32, true>() : geom<32, false>()); return true;
-        case 64: f(pair ? geom<64, true>() : geom<64, false>()); return true;
-        case 128: f(pair ? geom<128, true>() : geom<128, false>()); return true;
-        case 256: f(pair ? geom<256, true>() : geom<256, false>()); return true;
-        case 512: f(pair ? geom<512, true>() : geom<512, false>()); return true;
-        case 1024: f(pair ? geom<1024, true>() : geom<1024, false>()); return true;
-        case 2048: f(pair ? geom<2048, true>() : geom<2048, false>()); return true;
-        case 4096: f(pair ? geom<4096, true>() : geom<4096, false>()); return true;
-        case 8192: f(pair ? geom<8192, true>() : geom<8192, false>()); return true;
-        case 16384: f(pair ? geom<16384, true>() : geom<16384, false>()); return true;
-    }
-    return false;
+    return with_nfft(n_fft, [&](auto nn) { constexpr int N = decltype(nn)::value; f(pair ? geom<N, true>() : geom<N, false>()); });
 }
 
 // (R, C) of the plan for n_fft: the host builds the twiddle tables from these
@@ -349,13 +246,9 @@ int forward_frames_per_tile(int n_fft, int mode)
 bool forward_two_tiles(int n_fft, int mode)
 {
     if (mode_wlc(mode) || mode == kTrainH) return false;          // one tile per workgroup (launch_mode)
-    const bool pr = mode_pairs(mode);
-    switch (n_fft) {
-        case 256: return pr ? has_tpw2<256, true>() : has_tpw2<256, false>();
-        case 512: return pr ? has_tpw2<512, true>() : has_tpw2<512, false>();
-        case 1024: return pr ? has_tpw2<1024, true>() : has_tpw2<1024, false>();
-    }
-    return false;
+    bool two = false;
+    with_nfft(n_fft, [&](auto nn) { constexpr int N = decltype(nn)::value; two = mode_pairs(mode) ? has_tpw2<N, true>() : has_tpw2<N, false>(); });
+    return two;
 }
 
 // Tiles per workgroup for a launch over `batch` clips of `tiles_per_clip` tiles.  A launch runs in rounds of the workgroups
@@ -401,78 +294,6 @@ int forward_nbpre(int n_fft)
 }
 
 #endif   // DMEL_FWD_PART == 0
-
-template <int N, int MODE, int TPW> static hipError_t set_attr()
-{
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dmel_fwd_kernel<N, MODE, TPW>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, geom_mode<N, MODE>().LDS_BYTES);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&dmel_fwd_multi_kernel<N, MODE, TPW>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, geom_mode<N, MODE>().LDS_BYTES);
-}
-template <int N, int MODE> static hipError_t set_attr_mode()
-{
-    if constexpr (MODE == kTrainH) {
-        if constexpr (has_hsplit<N>()) return set_attr<N, MODE, 1>();
-        else return hipSuccess;
-    } else if constexpr (MODE == kTrainW) {
-        if constexpr (wlc_size(N)) return set_attr<N, MODE, 1>();
-        else return hipSuccess;
-    } else if constexpr (MODE == kTrainWW) {
-        if constexpr (wlc_wide_size(N)) return set_attr<N, MODE, 1>();
-        else return hipSuccess;
-    } else {
-        hipError_t e = set_attr<N, MODE, 1>();
-        if (e != hipSuccess) return e;
-        if constexpr (has_tpw2<N, mode_pairs(MODE)>()) return set_attr<N, MODE, 2>();
-        else return hipSuccess;
-    }
-}
-template <int N> static hipError_t set_attr_n()
-{
-    if constexpr (!DMEL_FWD_HERE(N)) return hipSuccess;
-    else {
-        static_assert(geom<N, true>().WAVES == geom<N, false>().WAVES && geom<N, true>().NBPRE == geom<N, false>().NBPRE,
-                      "both plans of a size share the filterbank fragment layout");
-        hipError_t e;
-        if ((e = set_attr_mode<N, kTrain>()) != hipSuccess) return e;
-        if ((e = set_attr_mode<N, kInfer>()) != hipSuccess) return e;
-        if ((e = set_attr_mode<N, kSpec>()) != hipSuccess) return e;
-        if ((e = set_attr_mode<N, kTrainH>()) != hipSuccess) return e;
-        if ((e = set_attr_mode<N, kTrainW>()) != hipSuccess) return e;
-        if ((e = set_attr_mode<N, kTrainWW>()) != hipSuccess) return e;
-        return set_attr_mode<N, kSpecTrain>();
-    }
-}
-
-hipError_t DMEL_CAT(forward_prepare_attributes_part, DMEL_FWD_PART)()
-{
-    hipError_t e;
-    if ((e = set_attr_n<32>()) != hipSuccess) return e;
-    if ((e = set_attr_n<64>()) != hipSuccess) return e;
-    if ((e = set_attr_n<128>()) != hipSuccess) return e;
-    if ((e = set_attr_n<256>()) != hipSuccess) return e;
-    if ((e = set_attr_n<512>()) != hipSuccess) return e;
-    if ((e = set_attr_n<1024>()) != hipSuccess) return e;
-    if ((e = set_attr_n<2048>()) != hipSuccess) return e;
-    if ((e = set_attr_n<4096>()) != hipSuccess) return e;
-    if ((e = set_attr_n<8192>()) != hipSuccess) return e;
-    return set_attr_n<16384>();
-}
-
-#if DMEL_FWD_PART == 0
-hipError_t forward_prepare_attributes()
-{
-    hipError_t e;
-    if ((e = forward_prepare_attributes_part0()) != hipSuccess) return e;
-#ifdef DMEL_FWD_PARTS
-    if ((e = forward_prepare_attributes_part1()) != hipSuccess) return e;
-    if ((e = forward_prepare_attributes_part2()) != hipSuccess) return e;
-    if ((e = forward_prepare_attributes_part3()) != hipSuccess) return e;
-#endif
-    return hipSuccess;
-}
-#endif
 
 }  // namespace dmel
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 
 namespace dmel {
 
@@ -435,11 +436,10 @@ struct PrepParams {
 };
 
 hipError_t launch_prep(const PrepParams& p, hipStream_t s);
+// the fused forward: the kernel is picked by the parameter type (dmel_fwd.hip, dmel_fwd_len.hip, dmel_fwd_band.hip)
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdParams& p, int grid, hipStream_t s);
-hipError_t launch_forward_len(int n_fft, int mode, int tiles_per_wg, const FwdLenParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
-hipError_t forward_len_prepare_attributes();   // ... and the dynamic-LDS limit of its instantiations
-hipError_t launch_forward_band(int n_fft, int mode, int tiles_per_wg, const FwdBandParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
-hipError_t forward_band_prepare_attributes();
+hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdLenParams& p, int grid, hipStream_t s);    // kTrain, kTrainW, kInfer
+hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdBandParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
 int forward_tiles_per_wg(int n_fft, int mode, int batch, int tiles_per_clip);          // 1 or 2: what launch_forward should be given
 bool forward_two_tiles(int n_fft, int mode);          // the two-tiles-per-workgroup instantiation exists for this size and mode
 int forward_lds_bytes(int n_fft, int mode);
@@ -452,7 +452,6 @@ bool forward_has_wlc(int n_fft);           // kTrainW is built for this size
 bool forward_wlc_one_frame(int n_fft);     // ... with one frame per wave (two of the four MFMA rows idle: wide quads are split over blocks)
 bool forward_has_wlc_wide(int n_fft);      // ... and kTrainWW
 bool forward_window_in_lds(int n_fft);     // the kernel builds its own window table (otherwise dmel_prep_kernel writes FwdParams::win2)   // radix per lane and cross-lane radix of the plan (layout of tw1 / tw2)
-hipError_t forward_prepare_attributes();   // raises the dynamic-LDS limit of every instantiation once
 
 // direct-DFT kernel for n_fft < 32 (and as an on-device cross-check of the fast path)
 // DMEL_FLAG_X_INDIRECT (every forward kernel since round 6): the batch's address comes from a pointer cell, read with one scalar load
@@ -494,7 +493,6 @@ struct BigParams {
 };
 hipError_t launch_big(const BigParams& p, hipStream_t s);
 bool big_can_split(int m_half, int n_mels);
-hipError_t big_prepare_attributes();
 bool big_uses_global(int m_fft);
 int big_grid(long long units, int m_fft);
 
@@ -531,7 +529,6 @@ struct XgradParams {
 hipError_t launch_xgrad(const XgradParams& p, hipStream_t s);
 hipError_t launch_xgrad_big(const XgradParams& p, int grid, hipStream_t s);     // frames kernel on the global-memory FFT / chirp-z transforms
 hipError_t launch_xgrad_gather(const XgradParams& p, hipStream_t s);           // ordered overlap-add of the (B, T, N) frame gradients + mean
-hipError_t xgrad_prepare_attributes();
 bool xgrad_wave_shape(int n_fft, int n_mels, int win_n, int* frames_per_tile);   // the wave-FFT kernel takes this shape
 int xgrad_chunks(int L);      // gather chunks per clip (size of XgradParams::csum per clip)
 hipError_t launch_xgrad_frames(const XgradParams& p, hipStream_t s);           // the LDS radix-2 frames kernel alone (no gather)
@@ -545,7 +542,6 @@ struct XgradLenParams : XgradParams {
     int fpt;                    // wave path: frames per tile (clip b's tiles are q < ceil(Tc / fpt); the others are neither written nor read)
 };
 hipError_t launch_xgrad_len(const XgradLenParams& p, hipStream_t s);
-hipError_t xgrad_len_prepare_attributes();
 
 // the multi-window layer's gradient w.r.t. the waveform.  grad_out / out are (B, K, M, T); every channel has its own window table, segment
 // (or frame) region and fp64 sums.  dmel_xgrad_wave_multi_kernel<N>: grid = count x B x tiles, channel slot w / ch_grid, channel = nibble
@@ -672,5 +668,20 @@ void dot_band_deal(const int* edges, int channels, int batch, int T, int* blocks
 hipError_t launch_dot_band(const DotBandParams& p, hipStream_t s);
 // the same exchange for a value that is already in memory (one wave): buf[0] = sum over ranks of buf[0]
 hipError_t launch_mailbox_allreduce(float* buf, const MailboxArgs& mb, hipStream_t s);
+
+// raises the dynamic-LDS limit of every kernel that needs it, once per plan: each translation unit does its own kernels
+hipError_t forward_prepare_attributes();
+hipError_t forward_len_prepare_attributes();
+hipError_t forward_band_prepare_attributes();
+hipError_t xgrad_prepare_attributes();
+hipError_t xgrad_len_prepare_attributes();
+hipError_t big_prepare_attributes();
+inline hipError_t prepare_attributes()
+{
+    for (auto unit : {forward_prepare_attributes, forward_len_prepare_attributes, forward_band_prepare_attributes, xgrad_prepare_attributes,
+                      xgrad_len_prepare_attributes, big_prepare_attributes})
+        if (const hipError_t e = unit(); e != hipSuccess) return e;
+    return hipSuccess;
+}
 
 }  // namespace dmel

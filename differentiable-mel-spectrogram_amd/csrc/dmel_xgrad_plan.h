@@ -1,7 +1,9 @@
 // dmel_xgrad_plan.h -- what the two translation units of the gradient w.r.t. the waveform share: dmel_xgrad.hip (clips of n_points samples,
 // the scalar and the multi-window layer) and dmel_xgrad_len.hip (clips of per-clip lengths).  The geometry of the wave-FFT kernel
-// (csrc/dmel_xgrad_wave_body.inc), its LDS layout and the dispatch over n_fft.  (The launch parameters, XgradParams and XgradLenParams, are in dmel_kernels.h.)
+// (csrc/dmel_xgrad_wave_body.inc), its LDS layout, the dispatch over n_fft and the clip-length load.  (The launch parameters, XgradParams and
+// XgradLenParams, are in dmel_kernels.h; the kernels both units instantiate and their launch logic in dmel_xgrad_body.h.)
 #pragma once
+#include <type_traits>
 #include "dmel_kernels.h"
 #include "dmel_wavefft.h"
 
@@ -14,6 +16,21 @@ constexpr int kXgThreads = 256;
 __device__ __forceinline__ bool xgrad_not_this_nfft(const XgradParams& p)
 {
     return p.check_nfft && p.lam_dev && lam_n_fft(__builtin_fabsf(*(const __attribute__((address_space(4))) float*)p.lam_dev)) != p.N;
+}
+
+// the length-aware build of a kernel body or launcher: its parameters carry the per-clip lengths
+template <class P> constexpr bool kXgLen = std::is_same<P, XgradLenParams>::value;
+
+// the clip's length: one scalar load, uniform over the workgroup (as dmel_fwd_len_kernel); an invalid one reads as 1 until the caller returns
+struct ClipLen { int Lc, Tc; bool ok; };
+__device__ __forceinline__ ClipLen clip_len(const int* lengths, int b, int L, int hop)
+{
+    const int raw = *(const __attribute__((address_space(4))) int*)(lengths + b);
+    ClipLen c;
+    c.ok = raw >= 1 && raw <= L;
+    c.Lc = __builtin_amdgcn_readfirstlane(c.ok ? raw : 1);
+    c.Tc = c.Lc / hop + 1;
+    return c;
 }
 
 // samples of a clip per workgroup of the gather / combine kernels

@@ -105,7 +105,7 @@ def test_never_read_and_exactly_zero(lam, log):
     assert _same(y, y3) and _same(gx, gx3) and _zero_past(gx3, MIXED)
 
 
-@pytest.mark.parametrize("lam", [40.0, 700.0], ids=["nfft256", "nfft8192"])
+@pytest.mark.parametrize("lam", [40.0, 700.0, 2000.0], ids=["nfft256", "nfft8192", "nfft16384"])
 def test_a_row_is_the_one_clip_batch(lam):
     B, M, hop = len(MIXED), 32, 100
     x, g, lengths = _x(B, 5), _g(B, M, hop, 6), _len(MIXED)
