@@ -30,23 +30,6 @@ DMEL_DTYPE_F32, DMEL_DTYPE_BF16 = 0, 1
 MAX_NFFT = 16384          # largest transform of the HIP kernels (kMaxNfft in csrc/dmel_kernels.h)
 MIN_FAST_NFFT = 32        # smallest transform of the fused kernel (kMinFastNfft); the multi-window layer serves MIN_FAST_NFFT ... MAX_NFFT
 
-# every symbol include/dmel.h declares (tests check the library exports exactly these)
-SYMBOLS = (
-    "dmel_abi_version", "dmel_n_fft", "dmel_window_host", "dmel_mel_fbanks_host", "dmel_contraction_partition_host", "dmel_last_error",
-    "dmel_device_count", "dmel_plan_create", "dmel_plan_destroy", "dmel_plan_set_filterbank",
-    "dmel_forward", "dmel_backward", "dmel_backward_ex", "dmel_backward_fb", "dmel_backward_x", "dmel_spectrogram", "dmel_plan_get_info",
-    "dmel_plan_set_profiling", "dmel_plan_get_profile", "dmel_spectrogram_ex",
-    "dmel_comm_unique_id", "dmel_comm_create", "dmel_comm_destroy", "dmel_comm_allreduce_async", "dmel_comm_wait",
-    "dmel_comm_allreduce", "dmel_scratch_bytes", "dmel_plan_set_filterbank_dev", "dmel_forward_scratch", "dmel_forward_dev", "dmel_forward_dev_fixed", "dmel_backward_fb_dev", "dmel_backward_scratch", "dmel_plan_get_config",
-    "dmel_plan_lambd_status", "dmel_plan_set_tracking", "dmel_plan_lambd_reset",
-    "dmel_plan_retain", "dmel_plan_release", "dmel_plan_lambd_report", "dmel_decide_launch", "dmel_plan_force_launch",
-    "dmel_adam_step", "dmel_mailbox_create", "dmel_mailbox_connect", "dmel_mailbox_destroy", "dmel_mailbox_allreduce", "dmel_mailbox_error",
-    "dmel_mailbox_set_spin_limit", "dmel_mailbox_set_timeout_ms", "dmel_plan_is_live", "dmel_lambd_ring_size", "dmel_spectrogram_ex_dev", "dmel_forward_dev_fixed_spec", "dmel_backward_fb_saved", "dmel_backward_fb_saved_dl", "dmel_backward_x_dev", "dmel_backward_x_spec_dev", "dmel_plan_attach_mailbox", "dmel_backward_x_spec", "dmel_plan_attach_adam",
-    "dmel_scratch_bytes_multi", "dmel_forward_multi", "dmel_forward_multi_dev", "dmel_backward_multi", "dmel_plan_lambd_status_channel",
-    "dmel_decide_launch_multi", "dmel_backward_x_multi", "dmel_backward_x_multi_dev", "dmel_plan_last_multi_launch",
-    "dmel_forward_band", "dmel_forward_band_dev", "dmel_backward_band",
-    "dmel_forward_lengths", "dmel_forward_dev_lengths", "dmel_backward_x_lengths", "dmel_backward_x_dev_lengths",
-)
 TORCH_LIB_PATH = os.path.join(_PKG_DIR, "libdmel_torch.so")
 
 
@@ -84,6 +67,93 @@ class DmelError(RuntimeError):
         self.status = status
 
 
+# name -> (restype, argtypes) of every function include/dmel.h declares, in the header's order.  The header is the authority: tests compare the
+# names and the parameter counts with it and the library's exports with the names.  ``vp`` is any device or opaque pointer (an int, None or a
+# ctypes array), the typed pointers are host arrays and out-parameters, ``buf`` a byte buffer (uint8_t[]), ``status`` the dmel_status enum.
+P = C.POINTER
+vp, vpp, fp, i32p, u32p, buf = C.c_void_p, P(C.c_void_p), P(C.c_float), P(C.c_int32), P(C.c_uint32), C.c_char_p
+status, i32, u32, i64, u64, f32, f64 = C.c_int, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+_SIGNATURES = {
+    "dmel_abi_version": (i32, []),
+    "dmel_n_fft": (i32, [f32]),
+    "dmel_window_host": (status, [f32, i32, i32, fp, fp]),
+    "dmel_mel_fbanks_host": (status, [i32, f64, f64, i32, i32, fp]),
+    "dmel_contraction_partition_host": (status, [i32p, i32, i32, i32p, i32p, i32p, i32p, i32p, i32p]),
+    "dmel_last_error": (C.c_char_p, []),
+    "dmel_device_count": (i32, []),
+    "dmel_plan_create": (status, [P(DmelConfig), vpp]),
+    "dmel_plan_destroy": (status, [vp]),
+    "dmel_plan_retain": (status, [vp]),
+    "dmel_plan_release": (status, [vp]),
+    "dmel_plan_is_live": (i32, [vp]),
+    "dmel_lambd_ring_size": (i32, []),
+    "dmel_plan_get_config": (status, [vp, P(DmelConfig)]),
+    "dmel_plan_set_filterbank": (status, [vp, i32, fp]),
+    "dmel_plan_set_filterbank_dev": (status, [vp, i32, vp, vp]),
+    "dmel_forward": (status, [vp, vp, i32, f32, u32, f64, vp, vp, vp]),
+    "dmel_scratch_bytes": (C.c_size_t, [vp, i32]),
+    "dmel_forward_scratch": (status, [vp, vp, i32, f32, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_dev": (status, [vp, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_dev_fixed": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_dev_fixed_spec": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp, vp]),
+    "dmel_forward_lengths": (status, [vp, vp, vp, i32, f32, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_dev_lengths": (status, [vp, vp, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
+    "dmel_plan_lambd_status": (status, [vp, P(DmelLambdStatus)]),
+    "dmel_plan_lambd_report": (status, [vp, u32, fp, i32p]),
+    "dmel_decide_launch": (status, [f32, f32, f32, i32p, i32p]),
+    "dmel_plan_force_launch": (status, [vp, i32, i32]),
+    "dmel_plan_set_tracking": (status, [vp, i32, i32]),
+    "dmel_plan_lambd_reset": (status, [vp]),
+    "dmel_backward": (status, [vp, vp, vp, i64, i32, vp, vp]),
+    "dmel_backward_ex": (status, [vp, vp, i32, vp, i64, i32, vp, vp]),
+    "dmel_backward_scratch": (status, [vp, vp, i32, vp, i64, i32, vp, vp, vp]),
+    "dmel_backward_fb": (status, [vp, vp, i32, f32, u32, vp, vp, vp, vp]),
+    "dmel_backward_fb_dev": (status, [vp, vp, i32, vp, i32, u32, vp, vp, vp, vp]),
+    "dmel_backward_fb_saved": (status, [vp, vp, i32, i32, u32, vp, vp, vp, vp]),
+    "dmel_backward_fb_saved_dl": (status, [vp, vp, i32, i32, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "dmel_backward_x": (status, [vp, vp, i32, f32, u32, vp, vp, vp, vp]),
+    "dmel_backward_x_spec": (status, [vp, vp, i32, f32, i32, u32, vp, vp, vp]),
+    "dmel_backward_x_dev": (status, [vp, vp, i32, vp, i32, u32, vp, vp, vp, vp]),
+    "dmel_backward_x_spec_dev": (status, [vp, vp, i32, vp, i32, u32, vp, vp, vp]),
+    "dmel_backward_x_lengths": (status, [vp, vp, vp, i32, f32, u32, vp, vp, vp, vp]),
+    "dmel_backward_x_dev_lengths": (status, [vp, vp, vp, i32, vp, i32, u32, vp, vp, vp, vp]),
+    "dmel_spectrogram": (status, [vp, vp, i32, f32, i32, vp, vp]),
+    "dmel_spectrogram_ex": (status, [vp, vp, i32, f32, i32, u32, vp, vp, vp]),
+    "dmel_spectrogram_ex_dev": (status, [vp, vp, i32, vp, i32, u32, vp, vp, vp]),
+    "dmel_comm_unique_id": (status, [buf]),
+    "dmel_comm_create": (status, [buf, i32, i32, vpp]),
+    "dmel_comm_destroy": (status, [vp]),
+    "dmel_comm_allreduce_async": (status, [vp, vp, i32, vp, i32p]),
+    "dmel_comm_allreduce": (status, [vp, vp, i32, vp]),
+    "dmel_comm_wait": (status, [vp, i32, vp]),
+    "dmel_mailbox_create": (status, [i32, i32, vpp, buf]),
+    "dmel_mailbox_connect": (status, [vp, buf]),
+    "dmel_mailbox_destroy": (status, [vp]),
+    "dmel_mailbox_allreduce": (status, [vp, vp, vp]),
+    "dmel_mailbox_error": (status, [vp, i32p, u32p, i32p]),
+    "dmel_mailbox_set_spin_limit": (status, [vp, u32]),
+    "dmel_mailbox_set_timeout_ms": (status, [vp, u64]),
+    "dmel_plan_attach_mailbox": (status, [vp, vp]),
+    "dmel_adam_step": (status, [vp, vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i32, vp]),
+    "dmel_plan_attach_adam": (status, [vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32]),
+    "dmel_scratch_bytes_multi": (C.c_size_t, [vp, i32, i32]),
+    "dmel_forward_multi": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_multi_dev": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
+    "dmel_backward_multi": (status, [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
+    "dmel_plan_lambd_status_channel": (status, [vp, i32, P(DmelLambdStatus)]),
+    "dmel_decide_launch_multi": (status, [fp, fp, i32, f32, i32p, u32p, i32p]),
+    "dmel_backward_x_multi": (status, [vp, vp, i32, fp, i32, u32, vp, vp, vp, vp]),
+    "dmel_backward_x_multi_dev": (status, [vp, vp, i32, vp, i32, i32p, u32p, i32, u32, vp, vp, vp, vp]),
+    "dmel_plan_last_multi_launch": (status, [vp, i32p, u32p, i32p]),
+    "dmel_forward_band": (status, [vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_band_dev": (status, [vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
+    "dmel_backward_band": (status, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "dmel_plan_get_info": (status, [vp, P(DmelPlanInfo)]),
+    "dmel_plan_set_profiling": (status, [vp, i32]),
+    "dmel_plan_get_profile": (status, [vp, P(DmelProfile)]),
+}
+SYMBOLS = tuple(_SIGNATURES)
+
 _lib = None
 
 
@@ -98,156 +168,9 @@ def load():
             "(python -c 'import __graft_entry__ as g; g.build()' or python differentiable-mel-spectrogram_amd/build.py). "
             "There is no CPU fallback for the DMEL layer.")
     L = C.CDLL(LIB_PATH)
-    vp, fp = C.c_void_p, C.POINTER(C.c_float)
-    L.dmel_abi_version.restype = C.c_int32
-    L.dmel_n_fft.argtypes = [C.c_float]
-    L.dmel_n_fft.restype = C.c_int32
-    L.dmel_window_host.argtypes = [C.c_float, C.c_int32, C.c_int32, fp, fp]
-    L.dmel_window_host.restype = C.c_int
-    L.dmel_mel_fbanks_host.argtypes = [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, fp]
-    L.dmel_mel_fbanks_host.restype = C.c_int
-    L.dmel_last_error.restype = C.c_char_p
-    L.dmel_device_count.restype = C.c_int32
-    L.dmel_plan_create.argtypes = [C.POINTER(DmelConfig), C.POINTER(vp)]
-    L.dmel_plan_create.restype = C.c_int
-    L.dmel_plan_destroy.argtypes = [vp]
-    L.dmel_plan_destroy.restype = C.c_int
-    L.dmel_plan_set_filterbank.argtypes = [vp, C.c_int32, fp]
-    L.dmel_plan_set_filterbank.restype = C.c_int
-    L.dmel_forward.argtypes = [vp, vp, C.c_int32, C.c_float, C.c_uint32, C.c_double, vp, vp, vp]
-    L.dmel_forward.restype = C.c_int
-    L.dmel_backward.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, vp, vp]
-    L.dmel_backward.restype = C.c_int
-    L.dmel_backward_ex.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp]
-    L.dmel_backward_ex.restype = C.c_int
-    L.dmel_backward_fb.argtypes = [vp, vp, C.c_int32, C.c_float, C.c_uint32, vp, vp, vp, vp]
-    L.dmel_backward_fb.restype = C.c_int
-    L.dmel_backward_x.argtypes = [vp, vp, C.c_int32, C.c_float, C.c_uint32, vp, vp, vp, vp]
-    L.dmel_backward_x.restype = C.c_int
-    L.dmel_backward_x_spec.argtypes = [vp, vp, C.c_int32, C.c_float, C.c_int32, C.c_uint32, vp, vp, vp]
-    L.dmel_backward_x_spec.restype = C.c_int
-    L.dmel_spectrogram.argtypes = [vp, vp, C.c_int32, C.c_float, C.c_int32, vp, vp]
-    L.dmel_spectrogram.restype = C.c_int
-    L.dmel_spectrogram_ex.argtypes = [vp, vp, C.c_int32, C.c_float, C.c_int32, C.c_uint32, vp, vp, vp]
-    L.dmel_spectrogram_ex.restype = C.c_int
-    L.dmel_comm_unique_id.argtypes = [C.c_char_p]
-    L.dmel_comm_unique_id.restype = C.c_int
-    L.dmel_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.dmel_comm_create.restype = C.c_int
-    L.dmel_comm_destroy.argtypes = [vp]
-    L.dmel_comm_destroy.restype = C.c_int
-    L.dmel_comm_allreduce_async.argtypes = [vp, vp, C.c_int32, vp, C.POINTER(C.c_int32)]
-    L.dmel_comm_allreduce_async.restype = C.c_int
-    L.dmel_comm_allreduce.argtypes = [vp, vp, C.c_int32, vp]
-    L.dmel_comm_allreduce.restype = C.c_int
-    L.dmel_comm_wait.argtypes = [vp, C.c_int32, vp]
-    L.dmel_comm_wait.restype = C.c_int
-    L.dmel_plan_get_info.argtypes = [vp, C.POINTER(DmelPlanInfo)]
-    L.dmel_plan_get_info.restype = C.c_int
-    L.dmel_plan_set_profiling.argtypes = [vp, C.c_int32]
-    L.dmel_plan_set_profiling.restype = C.c_int
-    L.dmel_plan_get_profile.argtypes = [vp, C.POINTER(DmelProfile)]
-    L.dmel_plan_get_profile.restype = C.c_int
-    L.dmel_plan_set_filterbank_dev.argtypes = [vp, C.c_int32, vp, vp]
-    L.dmel_plan_set_filterbank_dev.restype = C.c_int
-    L.dmel_scratch_bytes.argtypes = [vp, C.c_int32]
-    L.dmel_scratch_bytes.restype = C.c_size_t
-    L.dmel_forward_scratch.argtypes = [vp, vp, C.c_int32, C.c_float, C.c_uint32, C.c_double, vp, vp, vp, vp]
-    L.dmel_forward_scratch.restype = C.c_int
-    L.dmel_forward_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
-    L.dmel_forward_dev.restype = C.c_int
-    L.dmel_forward_lengths.argtypes = [vp, vp, vp, C.c_int32, C.c_float, C.c_uint32, C.c_double, vp, vp, vp, vp]
-    L.dmel_forward_lengths.restype = C.c_int
-    L.dmel_forward_dev_lengths.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
-    L.dmel_forward_dev_lengths.restype = C.c_int
-    L.dmel_backward_x_lengths.argtypes = [vp, vp, vp, C.c_int32, C.c_float, C.c_uint32, vp, vp, vp, vp]
-    L.dmel_backward_x_lengths.restype = C.c_int
-    L.dmel_backward_x_dev_lengths.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, vp, vp, vp, vp]
-    L.dmel_backward_x_dev_lengths.restype = C.c_int
-    L.dmel_forward_dev_fixed.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.c_double, vp, vp, vp, vp]
-    L.dmel_forward_dev_fixed.restype = C.c_int
-    L.dmel_backward_fb_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, vp, vp, vp, vp]
-    L.dmel_backward_fb_dev.restype = C.c_int
-    L.dmel_backward_scratch.argtypes = [vp, vp, C.c_int32, vp, C.c_int64, C.c_int32, vp, vp, vp]
-    L.dmel_backward_scratch.restype = C.c_int
-    L.dmel_plan_get_config.argtypes = [vp, C.POINTER(DmelConfig)]
-    L.dmel_plan_get_config.restype = C.c_int
-    L.dmel_plan_lambd_status.argtypes = [vp, C.POINTER(DmelLambdStatus)]
-    L.dmel_plan_lambd_status.restype = C.c_int
-    L.dmel_plan_set_tracking.argtypes = [vp, C.c_int32, C.c_int32]
-    L.dmel_plan_set_tracking.restype = C.c_int
-    L.dmel_plan_lambd_reset.argtypes = [vp]
-    L.dmel_plan_lambd_reset.restype = C.c_int
-    L.dmel_plan_retain.argtypes = [vp]
-    L.dmel_plan_retain.restype = C.c_int
-    L.dmel_plan_release.argtypes = [vp]
-    L.dmel_plan_release.restype = C.c_int
-    L.dmel_plan_lambd_report.argtypes = [vp, C.c_uint32, fp, C.POINTER(C.c_int32)]
-    L.dmel_plan_lambd_report.restype = C.c_int
-    L.dmel_decide_launch.argtypes = [C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.dmel_decide_launch.restype = C.c_int
-    L.dmel_plan_force_launch.argtypes = [vp, C.c_int32, C.c_int32]
-    L.dmel_plan_force_launch.restype = C.c_int
-    L.dmel_scratch_bytes_multi.argtypes = [vp, C.c_int32, C.c_int32]
-    L.dmel_scratch_bytes_multi.restype = C.c_size_t
-    L.dmel_forward_multi.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.c_double, vp, vp, vp, vp]
-    L.dmel_forward_multi.restype = C.c_int
-    L.dmel_forward_multi_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.c_double, vp, vp, vp, vp]
-    L.dmel_forward_multi_dev.restype = C.c_int
-    L.dmel_backward_multi.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
-    L.dmel_backward_multi.restype = C.c_int
-    L.dmel_plan_lambd_status_channel.argtypes = [vp, C.c_int32, C.POINTER(DmelLambdStatus)]
-    L.dmel_plan_lambd_status_channel.restype = C.c_int
-    L.dmel_decide_launch_multi.argtypes = [fp, fp, C.c_int32, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
-    L.dmel_decide_launch_multi.restype = C.c_int
-    L.dmel_backward_x_multi.argtypes = [vp, vp, C.c_int32, fp, C.c_int32, C.c_uint32, vp, vp, vp, vp]
-    L.dmel_backward_x_multi.restype = C.c_int
-    L.dmel_backward_x_multi_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_int32, C.c_uint32,
-                                            vp, vp, vp, vp]
-    L.dmel_backward_x_multi_dev.restype = C.c_int
-    L.dmel_plan_last_multi_launch.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
-    L.dmel_plan_last_multi_launch.restype = C.c_int
-    L.dmel_forward_band.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
-    L.dmel_forward_band.restype = C.c_int
-    L.dmel_forward_band_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_uint32, C.c_double, vp, vp, vp, vp]
-    L.dmel_forward_band_dev.restype = C.c_int
-    L.dmel_backward_band.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp]
-    L.dmel_backward_band.restype = C.c_int
-    L.dmel_mailbox_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(vp), C.c_char_p]
-    L.dmel_mailbox_create.restype = C.c_int
-    L.dmel_mailbox_connect.argtypes = [vp, C.c_char_p]
-    L.dmel_mailbox_connect.restype = C.c_int
-    L.dmel_mailbox_destroy.argtypes = [vp]
-    L.dmel_mailbox_destroy.restype = C.c_int
-    L.dmel_adam_step.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, vp]
-    L.dmel_adam_step.restype = C.c_int
-    L.dmel_plan_attach_adam.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32]
-    L.dmel_plan_attach_adam.restype = C.c_int
-    L.dmel_mailbox_allreduce.argtypes = [vp, vp, vp]
-    L.dmel_mailbox_allreduce.restype = C.c_int
-    L.dmel_mailbox_error.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
-    L.dmel_mailbox_error.restype = C.c_int
-    L.dmel_mailbox_set_spin_limit.argtypes = [vp, C.c_uint32]
-    L.dmel_mailbox_set_spin_limit.restype = C.c_int
-    L.dmel_lambd_ring_size.restype = C.c_int32
-    L.dmel_forward_dev_fixed_spec.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.c_double, vp, vp, vp, vp, vp]
-    L.dmel_forward_dev_fixed_spec.restype = C.c_int
-    L.dmel_backward_fb_saved.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint32, vp, vp, vp, vp]
-    L.dmel_backward_fb_saved.restype = C.c_int
-    L.dmel_backward_fb_saved_dl.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
-    L.dmel_backward_fb_saved_dl.restype = C.c_int
-    L.dmel_spectrogram_ex_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, vp, vp, vp]
-    L.dmel_spectrogram_ex_dev.restype = C.c_int
-    L.dmel_backward_x_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, vp, vp, vp, vp]
-    L.dmel_backward_x_dev.restype = C.c_int
-    L.dmel_backward_x_spec_dev.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, C.c_uint32, vp, vp, vp]
-    L.dmel_backward_x_spec_dev.restype = C.c_int
-    L.dmel_plan_is_live.argtypes = [vp]
-    L.dmel_plan_is_live.restype = C.c_int32
-    L.dmel_mailbox_set_timeout_ms.argtypes = [vp, C.c_uint64]
-    L.dmel_mailbox_set_timeout_ms.restype = C.c_int
-    L.dmel_plan_attach_mailbox.argtypes = [vp, vp]
-    L.dmel_plan_attach_mailbox.restype = C.c_int
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -337,7 +260,6 @@ def contraction_partition(units, waves: int = 8):
     u = (i32 * 8)(*([int(v) for v in units] + [0] * (8 - n)))
     own, npc = (i32 * 8)(), i32(0)
     pw, pt, pf, pu = (i32 * 8)(), (i32 * 8)(), (i32 * 8)(), (i32 * 8)()
-    L.dmel_contraction_partition_host.restype = C.c_int
     _check(L.dmel_contraction_partition_host(u, n, int(waves), own, C.byref(npc), pw, pt, pf, pu))
     return list(own)[:waves], [(pw[i], pt[i], pf[i], pu[i]) for i in range(npc.value)]
 
@@ -348,6 +270,16 @@ def mel_fbanks_host(n_freqs: int, f_min: float, f_max: float, n_mels: int, sampl
     _check(load().dmel_mel_fbanks_host(n_freqs, float(f_min), float(f_max), n_mels, sample_rate,
                                        fb.ctypes.data_as(C.POINTER(C.c_float))))
     return fb
+
+
+def _floats(values):
+    """a host array of C floats (the K window widths passed by value)"""
+    return (C.c_float * len(values))(*[float(v) for v in values])
+
+
+def _ints(values):
+    """a host array of int32 (the K + 1 band edges)"""
+    return (C.c_int32 * len(values))(*[int(v) for v in values])
 
 
 class Plan:
@@ -502,7 +434,7 @@ class Plan:
     def forward_multi(self, x_ptr: int, batch: int, lambd, out_ptr: int, tangent_ptr: int | None, log: bool, eps: float, stream: int,
                       scratch_ptr: int, out_bf16: bool = False):
         """lambd: the K host values (a sequence of floats)"""
-        lam = (C.c_float * len(lambd))(*[float(v) for v in lambd])
+        lam = _floats(lambd)
         flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
         _check(load().dmel_forward_multi(self._h, x_ptr, batch, lam, len(lambd), flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream))
 
@@ -521,28 +453,28 @@ class Plan:
     def forward_band(self, x_ptr: int, batch: int, lambd, edges, out_ptr: int, tangent_ptr: int | None, log: bool, eps: float, stream: int,
                      scratch_ptr: int, out_bf16: bool = False):
         """lambd: the K host values; edges: K + 1 host integers"""
-        lam = (C.c_float * len(lambd))(*[float(v) for v in lambd])
-        ed = (C.c_int32 * len(edges))(*[int(v) for v in edges])
+        lam = _floats(lambd)
+        ed = _ints(edges)
         flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
         _check(load().dmel_forward_band(self._h, x_ptr, batch, lam, len(lambd), ed, flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream))
 
     def forward_band_dev(self, x_ptr: int, batch: int, lambd_ptr: int, edges, out_ptr: int, tangent_ptr: int | None, log: bool,
                          eps: float, stream: int, scratch_ptr: int, out_bf16: bool = False):
-        ed = (C.c_int32 * len(edges))(*[int(v) for v in edges])
+        ed = _ints(edges)
         flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
         _check(load().dmel_forward_band_dev(self._h, x_ptr, batch, lambd_ptr, len(edges) - 1, ed, flags, float(eps), out_ptr, tangent_ptr,
                                             scratch_ptr, stream))
 
     def backward_band(self, grad_ptr: int, tangent_ptr: int, batch: int, edges, dlambd_ptr: int, stream: int, scratch_ptr: int,
                       accumulate: bool = False, grad_bf16: bool = False):
-        ed = (C.c_int32 * len(edges))(*[int(v) for v in edges])
+        ed = _ints(edges)
         _check(load().dmel_backward_band(self._h, grad_ptr, DMEL_DTYPE_BF16 if grad_bf16 else DMEL_DTYPE_F32, tangent_ptr, int(batch),
                                          len(edges) - 1, ed, int(accumulate), dlambd_ptr, scratch_ptr, stream))
 
     def backward_x_multi(self, x_ptr: int, batch: int, lambd, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int, log: bool, stream: int):
         """dmel_backward_x_multi: grad_x = sum over channels (ascending) of the scalar layer's waveform gradient; lambd: the K host values;
         grad_ptr / out_ptr: (B, K, M, T) fp32"""
-        lam = (C.c_float * len(lambd))(*[float(v) for v in lambd])
+        lam = _floats(lambd)
         _check(load().dmel_backward_x_multi(self._h, x_ptr, batch, lam, len(lambd), DMEL_FLAG_LOG if log else 0, grad_ptr, out_ptr, grad_x_ptr,
                                             stream))
 

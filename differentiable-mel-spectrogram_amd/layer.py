@@ -15,6 +15,12 @@ There is no CPU fallback.
 check the n_fft they were launched for (include/dmel.h, dmel_forward_dev), so a training step queues
 without the host waiting and can be captured into a HIP graph.  ``lambd_sync=True`` reads it to the
 host at every forward, as the reference does (time_frequency.py:39).
+
+Layout of this file.  What the autograd Functions share is written once, in front of them: ``_cotangent`` (the incoming
+gradient), ``_alloc`` (output, tangent, scratch and the rule for a bf16 log output whose backward needs fp32 values),
+``_lambd_f32``, ``_launched_for`` (the n_fft candidates of a tracked forward), ``_tracked_backward_x`` (the waveform gradient over
+them) and ``_dl_like``.  What the modules share sits in front of them: ``_check_input`` (every refusal of every ``forward``, in one
+order), ``_as_f32_contiguous`` and the plan cache (``_PlanCache``; with lambd tracking ``_PlanCachingModule``).
 """
 from __future__ import annotations
 
@@ -48,6 +54,79 @@ class _on_device:
         return False
 
 
+def _ptr(t):
+    """the device address of an optional tensor"""
+    return None if t is None else t.data_ptr()
+
+
+def _cotangent(grad_out):
+    """(g, is_bf16): the gradient of a bf16 output is read as it is and widened in the kernel, any other dtype goes to fp32;
+    contiguous either way."""
+    bf16 = grad_out.dtype == torch.bfloat16
+    g = grad_out
+    if not bf16 and g.dtype != torch.float32:
+        g = g.to(torch.float32)
+    if not g.is_contiguous():
+        g = g.contiguous()
+    return g, bf16
+
+
+def _alloc(x, shape, out_dtype, want_tangent, keeps_log_out=False, scratch_bytes=None):
+    """(out, tangent, scratch, round_later) of one forward on x's device: the output (models.py:36, fp32 there), the fp32 tangent
+    d out / d lambd when a gradient to lambd will be asked for, and the launch's scratch when it takes one.
+    ``keeps_log_out``: the backward rebuilds 1 / (mel + eps) from the saved log output (dL/dx, dL/dfb).  That needs the fp32 values, so
+    a bf16 output is then produced in fp32 (``round_later``) and rounded by the caller after it has been saved, instead of in the
+    kernel: bit-identical either way."""
+    round_later = out_dtype == torch.bfloat16 and keeps_log_out
+    out = torch.empty(shape, dtype=torch.float32 if round_later else out_dtype, device=x.device)
+    tangent = torch.empty(shape, dtype=torch.float32, device=x.device) if want_tangent else None
+    scratch = None if scratch_bytes is None else torch.empty((scratch_bytes,), dtype=torch.uint8, device=x.device)
+    return out, tangent, scratch, round_later
+
+
+def _out_flag(out) -> int:
+    return capi.DMEL_FLAG_OUT_BF16 if out.dtype == torch.bfloat16 else 0
+
+
+def _lambd_f32(lambd):
+    """lambd as the kernels read it from the device: detached, fp32, contiguous (a (K,) parameter may be a strided view)"""
+    lam = lambd.detach()
+    if lam.dtype != torch.float32 or not lam.is_contiguous():
+        lam = lam.to(torch.float32).contiguous()
+    return lam
+
+
+def _launched_for(plan):
+    """The n_fft candidates the tracked forward just issued on ``plan`` launched for: n0, 2 n0, n0 // 2 as its guards say (host-side
+    bookkeeping of the plan: no device read)."""
+    n0, guards = plan.info()["n_fft"], plan.lambd_status()["guards"]
+    return [n0] + ([2 * n0] if guards & 2 else []) + ([n0 // 2] if (guards & 1) and n0 >= 2 else [])
+
+
+def _tracked_backward_x(plan, x, lengths, lam, cands, g32, out, log, stream):
+    """The waveform gradient of a tracked forward, without a host read: one dmel_backward_x_dev(_lengths) per candidate n_fft
+    (DMEL_FLAG_CHECK_NFFT: the device value of lambd picks the one that works) over a NaN-filled grad_x; a lambd no launch covered
+    leaves the NaN, as that forward's output is."""
+    gx = torch.full_like(x, float("nan"))
+    for n in cands:
+        if lengths is None:
+            plan.backward_x_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), n, g32.data_ptr(), _ptr(out), gx.data_ptr(), log, stream,
+                                extra_flags=capi.DMEL_FLAG_CHECK_NFFT)
+        else:
+            plan.backward_x_dev_lengths(x.data_ptr(), lengths.data_ptr(), x.shape[0], lam.data_ptr(), n, g32.data_ptr(), _ptr(out),
+                                        gx.data_ptr(), log, stream, extra_flags=capi.DMEL_FLAG_CHECK_NFFT)
+    return gx
+
+
+def _dl_like(dl, shape, dtype):
+    """the fp32 gradient the kernels wrote, in the shape and dtype of the parameter ``lambd``"""
+    if dl.shape != shape:
+        dl = dl.reshape(shape)
+    if dtype != torch.float32:
+        dl = dl.to(dtype)
+    return dl
+
+
 class _DmelFunction(torch.autograd.Function):
     """forward: dmel_forward (carries d out / d lambd); backward: dmel_backward (one dot product) and, when a
     filterbank tensor that requires grad was passed, dmel_backward_fb (adjoint of models.py:53)."""
@@ -55,20 +134,13 @@ class _DmelFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, lambd, plan, lam_host, log, eps, full_window=False, fb=None, out_dtype=torch.float32):
         B = x.shape[0]
-        want_tangent = ctx.needs_input_grad[1]
+        want_x, want_tangent = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         want_fb = fb is not None and ctx.needs_input_grad[7]
-        want_x = ctx.needs_input_grad[0]
-        # dL/dx and dL/dfb rebuild 1 / (mel + eps) from the saved log output: that needs the fp32 values, so a bf16 output
-        # is produced by rounding an fp32 one here instead of in the kernel (bit-identical either way)
-        round_later = out_dtype == torch.bfloat16 and log and (want_x or want_fb)
-        kdtype = torch.float32 if round_later else out_dtype
-        out = torch.empty((B, 1, plan.n_mels, plan.n_time), dtype=kdtype, device=x.device)     # models.py:36 (fp32 there)
-        tangent = torch.empty(out.shape, dtype=torch.float32, device=x.device) if want_tangent else None
+        out, tangent, _, round_later = _alloc(x, (B, 1, plan.n_mels, plan.n_time), out_dtype, want_tangent, log and (want_x or want_fb))
         flags = capi.DMEL_FLAG_FULL_WINDOW if full_window else 0
         with _on_device(x.device):
-            plan.forward(x.data_ptr(), B, lam_host, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
-                         log, eps, _stream_ptr(x.device),
-                         extra_flags=flags | (capi.DMEL_FLAG_OUT_BF16 if kdtype == torch.bfloat16 else 0))
+            plan.forward(x.data_ptr(), B, lam_host, out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
+                         extra_flags=flags | _out_flag(out))
         ctx.plan = plan
         ctx.lambd_shape = lambd.shape
         ctx.lambd_dtype = lambd.dtype
@@ -87,22 +159,14 @@ class _DmelFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         saved = list(ctx.saved_tensors)
-        bf16 = grad_out.dtype == torch.bfloat16          # gradient of a bf16 output: read as it is, widened in the kernel
-        g = grad_out
-        if not bf16 and g.dtype != torch.float32:
-            g = g.to(torch.float32)
-        if not g.is_contiguous():
-            g = g.contiguous()
+        g, bf16 = _cotangent(grad_out)
         dl = gfb = gx = None
         with _on_device(g.device):
             if ctx.want_tangent:
                 tangent = saved.pop(0)
                 dl = torch.empty((1,), dtype=torch.float32, device=g.device)
                 ctx.plan.backward(g.data_ptr(), tangent.data_ptr(), g.numel(), dl.data_ptr(), _stream_ptr(g.device), grad_bf16=bf16)
-                if ctx.lambd_shape != dl.shape:
-                    dl = dl.reshape(ctx.lambd_shape)
-                if ctx.lambd_dtype != torch.float32:
-                    dl = dl.to(ctx.lambd_dtype)
+                dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
             if ctx.want_fb or ctx.want_x:
                 lam_host, log, flags, fb_meta = ctx.fb_args
                 x = saved.pop(0)
@@ -110,13 +174,13 @@ class _DmelFunction(torch.autograd.Function):
                 g = g.to(torch.float32)
             if ctx.want_x:
                 gx = torch.empty_like(x)
-                ctx.plan.backward_x(x.data_ptr(), x.shape[0], lam_host, g.data_ptr(), out.data_ptr() if log else None,
-                                    gx.data_ptr(), log, _stream_ptr(g.device), extra_flags=flags)
+                ctx.plan.backward_x(x.data_ptr(), x.shape[0], lam_host, g.data_ptr(), _ptr(out), gx.data_ptr(), log, _stream_ptr(g.device),
+                                    extra_flags=flags)
             if ctx.want_fb:
                 fb_shape, fb_dtype = fb_meta
                 gfb = torch.empty(fb_shape, dtype=torch.float32, device=g.device)
-                ctx.plan.backward_fb(x.data_ptr(), x.shape[0], lam_host, g.data_ptr(), out.data_ptr() if log else None,
-                                     gfb.data_ptr(), log, _stream_ptr(g.device), extra_flags=flags)
+                ctx.plan.backward_fb(x.data_ptr(), x.shape[0], lam_host, g.data_ptr(), _ptr(out), gfb.data_ptr(), log, _stream_ptr(g.device),
+                                     extra_flags=flags)
                 gfb = gfb.to(fb_dtype)
         return gx, dl, None, None, None, None, None, gfb, None
 
@@ -128,47 +192,35 @@ class _DmelFbDevFunction(torch.autograd.Function):
     waveform (dmel_backward_x_dev).  No host read anywhere: the step queues without waiting and can be captured into a HIP graph.
 
     ``n_fft == 0`` (HTK bank, optimized=True, x.requires_grad): the tracked forward dmel_forward_dev -- one launch per candidate n_fft,
-    the device value of lambd picks the one that works -- and a waveform gradient issued the same way (DMEL_FLAG_CHECK_NFFT: one
-    dmel_backward_x_dev per candidate over a NaN-filled grad_x; a lambd no launch covered leaves the NaN, as that forward's output is)."""
+    the device value of lambd picks the one that works -- and a waveform gradient issued the same way (_tracked_backward_x)."""
 
     @staticmethod
     def forward(ctx, x, lambd, plan, n_fft, log, eps, fb, out_dtype, full_window=False, mfma_flags=0, save_spec=False):
         B = x.shape[0]
-        want_tangent = ctx.needs_input_grad[1]
+        want_x, want_tangent = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         want_fb = fb is not None and ctx.needs_input_grad[6]
-        want_x = ctx.needs_input_grad[0]
-        # the spectrogram the contraction consumes, kept for the filterbank gradient (fused training kernel only)
         tracked = n_fft == 0
         if tracked and (fb is not None or full_window):
             raise ValueError("n_fft = 0 (tracked forward) is the HTK bank with optimized=True")
+        # the spectrogram the contraction consumes, kept for the filterbank gradient (fused training kernel only)
         keep_spec = bool(save_spec and want_fb and want_tangent and not full_window and 32 <= n_fft <= 16384 and (n_fft & (n_fft - 1)) == 0)
-        round_later = out_dtype == torch.bfloat16 and log and (want_fb or want_x)       # see _DmelFunction.forward
-        kdtype = torch.float32 if round_later else out_dtype
-        out = torch.empty((B, 1, plan.n_mels, plan.n_time), dtype=kdtype, device=x.device)
-        tangent = torch.empty(out.shape, dtype=torch.float32, device=x.device) if want_tangent else None
-        scratch = torch.empty((plan.scratch_bytes(B),), dtype=torch.uint8, device=x.device)
-        lam = lambd.detach()
-        if lam.dtype != torch.float32:
-            lam = lam.to(torch.float32)
+        out, tangent, scratch, round_later = _alloc(x, (B, 1, plan.n_mels, plan.n_time), out_dtype, want_tangent, log and (want_fb or want_x),
+                                                    plan.scratch_bytes(B))
+        lam = _lambd_f32(lambd)
         flags = (capi.DMEL_FLAG_FULL_WINDOW if full_window else 0) | int(mfma_flags)
         spec = torch.empty((B, n_fft // 2 + 1, plan.n_time), dtype=torch.float32, device=x.device) if keep_spec else None
         ctx.cands = None
         with _on_device(x.device):
             if tracked:
-                plan.forward_dev(x.data_ptr(), B, lam.data_ptr(), out.data_ptr(), tangent.data_ptr() if want_tangent else None, log, eps,
-                                 _stream_ptr(x.device), scratch.data_ptr(),
-                                 extra_flags=capi.DMEL_FLAG_OUT_BF16 if kdtype == torch.bfloat16 else 0)
-                # what that call launched for (host-side bookkeeping of the plan: no device read)
-                n0, guards = plan.info()["n_fft"], plan.lambd_status()["guards"]
-                ctx.cands = [n0] + ([2 * n0] if guards & 2 else []) + ([n0 // 2] if (guards & 1) and n0 >= 2 else [])
+                plan.forward_dev(x.data_ptr(), B, lam.data_ptr(), out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
+                                 scratch.data_ptr(), extra_flags=_out_flag(out))
+                ctx.cands = _launched_for(plan)
             elif keep_spec:
                 plan.forward_dev_fixed_spec(x.data_ptr(), B, lam.data_ptr(), n_fft, out.data_ptr(), tangent.data_ptr(), spec.data_ptr(),
-                                            log, eps, _stream_ptr(x.device), scratch.data_ptr(),
-                                            extra_flags=flags | (capi.DMEL_FLAG_OUT_BF16 if kdtype == torch.bfloat16 else 0))
+                                            log, eps, _stream_ptr(x.device), scratch.data_ptr(), extra_flags=flags | _out_flag(out))
             else:
-                plan.forward_dev_fixed(x.data_ptr(), B, lam.data_ptr(), n_fft, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
-                                       log, eps, _stream_ptr(x.device), scratch.data_ptr(),
-                                       extra_flags=flags | (capi.DMEL_FLAG_OUT_BF16 if kdtype == torch.bfloat16 else 0))
+                plan.forward_dev_fixed(x.data_ptr(), B, lam.data_ptr(), n_fft, out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
+                                       scratch.data_ptr(), extra_flags=flags | _out_flag(out))
         ctx.plan, ctx.n_fft, ctx.log, ctx.flags, ctx.keep_spec = plan, n_fft, bool(log), flags, keep_spec
         ctx.lambd_shape, ctx.lambd_dtype = lambd.shape, lambd.dtype
         ctx.want_tangent, ctx.want_fb, ctx.want_x = want_tangent, want_fb, want_x
@@ -190,57 +242,46 @@ class _DmelFbDevFunction(torch.autograd.Function):
         saved = list(ctx.saved_tensors)
         spec = saved.pop() if ctx.keep_spec else None
         scratch = saved.pop(0)
-        bf16 = grad_out.dtype == torch.bfloat16
-        g = grad_out
-        if not bf16 and g.dtype != torch.float32:
-            g = g.to(torch.float32)
-        if not g.is_contiguous():
-            g = g.contiguous()
+        g, bf16 = _cotangent(grad_out)
         dl = gfb = gx = None
         # d lambd rides in the launch of the filterbank gradient (dmel_backward_fb_saved_dl: one kernel less per step, the same bits)
         ride = ctx.want_tangent and ctx.want_fb and spec is not None and not bf16 and g.numel() > 0
+        stream = _stream_ptr(g.device)
         with _on_device(g.device):
             if ctx.want_tangent:
                 tangent = saved.pop(0)
                 dl = torch.empty(tuple(ctx.lambd_shape), dtype=torch.float32, device=g.device)
                 if not ride:
-                    ctx.plan.backward_scratch(g.data_ptr(), tangent.data_ptr(), g.numel(), dl.data_ptr(), _stream_ptr(g.device),
-                                              scratch.data_ptr(), grad_bf16=bf16)
+                    ctx.plan.backward_scratch(g.data_ptr(), tangent.data_ptr(), g.numel(), dl.data_ptr(), stream, scratch.data_ptr(), grad_bf16=bf16)
             if ctx.want_fb or ctx.want_x:
                 x, lam = saved.pop(0), saved.pop(0)
                 out = saved.pop(0).to(torch.float32) if ctx.log else None
                 g32 = g.to(torch.float32)
-            if ctx.want_x and ctx.cands is not None:
-                if max(ctx.cands) > 16384:
-                    # transforms beyond the fused kernels have no checked backward: the one case that reads lambd (n_fft >= 16384)
-                    gx = torch.empty_like(x)
-                    ctx.plan.backward_x(x.data_ptr(), x.shape[0], float(lam), g32.data_ptr(), out.data_ptr() if ctx.log else None,
-                                        gx.data_ptr(), ctx.log, _stream_ptr(g.device))
-                else:
-                    gx = torch.full_like(x, float("nan"))
-                    for n in ctx.cands:
-                        ctx.plan.backward_x_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), n, g32.data_ptr(), out.data_ptr() if ctx.log else None,
-                                                gx.data_ptr(), ctx.log, _stream_ptr(g.device), extra_flags=capi.DMEL_FLAG_CHECK_NFFT)
+            if ctx.want_x and ctx.cands is not None and max(ctx.cands) > 16384:
+                # transforms beyond the fused kernels have no checked backward: the one case that reads lambd (n_fft >= 16384)
+                gx = torch.empty_like(x)
+                ctx.plan.backward_x(x.data_ptr(), x.shape[0], float(lam), g32.data_ptr(), _ptr(out), gx.data_ptr(), ctx.log, stream)
+            elif ctx.want_x and ctx.cands is not None:
+                gx = _tracked_backward_x(ctx.plan, x, None, lam, ctx.cands, g32, out, ctx.log, stream)
             elif ctx.want_x:
                 gx = torch.empty_like(x)
-                ctx.plan.backward_x_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.n_fft, g32.data_ptr(), out.data_ptr() if ctx.log else None,
-                                        gx.data_ptr(), ctx.log, _stream_ptr(g.device), extra_flags=ctx.flags)
+                ctx.plan.backward_x_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.n_fft, g32.data_ptr(), _ptr(out), gx.data_ptr(), ctx.log,
+                                        stream, extra_flags=ctx.flags)
             if ctx.want_fb:
                 fb_shape, fb_dtype = ctx.fb_meta
                 gfb = torch.empty(fb_shape, dtype=torch.float32, device=g.device)
                 if ride:
-                    ctx.plan.backward_fb_saved_dl(spec.data_ptr(), x.shape[0], ctx.n_fft, g32.data_ptr(), out.data_ptr() if ctx.log else None,
-                                                  tangent.data_ptr(), gfb.data_ptr(), dl.data_ptr(), scratch.data_ptr(), ctx.log,
-                                                  _stream_ptr(g.device), extra_flags=ctx.flags)
+                    ctx.plan.backward_fb_saved_dl(spec.data_ptr(), x.shape[0], ctx.n_fft, g32.data_ptr(), _ptr(out), tangent.data_ptr(),
+                                                  gfb.data_ptr(), dl.data_ptr(), scratch.data_ptr(), ctx.log, stream, extra_flags=ctx.flags)
                 elif spec is not None:
-                    ctx.plan.backward_fb_saved(spec.data_ptr(), x.shape[0], ctx.n_fft, g32.data_ptr(), out.data_ptr() if ctx.log else None,
-                                               gfb.data_ptr(), ctx.log, _stream_ptr(g.device), extra_flags=ctx.flags)
+                    ctx.plan.backward_fb_saved(spec.data_ptr(), x.shape[0], ctx.n_fft, g32.data_ptr(), _ptr(out), gfb.data_ptr(), ctx.log, stream,
+                                               extra_flags=ctx.flags)
                 else:
-                    ctx.plan.backward_fb_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.n_fft, g32.data_ptr(),
-                                             out.data_ptr() if ctx.log else None, gfb.data_ptr(), ctx.log, _stream_ptr(g.device), extra_flags=ctx.flags)
+                    ctx.plan.backward_fb_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.n_fft, g32.data_ptr(), _ptr(out), gfb.data_ptr(),
+                                             ctx.log, stream, extra_flags=ctx.flags)
                 gfb = gfb.to(fb_dtype)
-            if dl is not None and ctx.lambd_dtype != torch.float32:
-                dl = dl.to(ctx.lambd_dtype)
+            if dl is not None:
+                dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
         return gx, dl, None, None, None, None, gfb, None, None, None, None
 
 
@@ -248,35 +289,25 @@ class _DmelLenXFunction(torch.autograd.Function):
     """forward(x, lengths) with a waveform gradient (``MelSpectrogramLayer(lengths_waveform_grad=True)`` and ``x.requires_grad``): the
     launches of torch.ops.dmel.mel_spectrogram_lengths -- dmel_forward_dev_lengths, or dmel_forward_lengths when ``lam_host`` is given
     (lambd_sync) -- with ``x``, ``lengths`` and the fp32 output kept for the backward.  backward: the same dot product for ``lambd`` and
-    dmel_backward_x_lengths for ``x``; with lambd on the device one dmel_backward_x_dev_lengths per n_fft the forward launched for
-    (DMEL_FLAG_CHECK_NFFT) over a NaN-filled grad_x, as _DmelFbDevFunction: no host read, the step can be captured into a HIP graph."""
+    dmel_backward_x_lengths for ``x``; with lambd on the device _tracked_backward_x over what the forward launched for, as
+    _DmelFbDevFunction: no host read, the step can be captured into a HIP graph.  (The lengths path never launches below n_fft 32.)"""
 
     @staticmethod
     def forward(ctx, x, lengths, lambd, plan, lam_host, log, eps, out_dtype):
         B = x.shape[0]
-        want_tangent = ctx.needs_input_grad[2]
-        want_x = ctx.needs_input_grad[0]
-        round_later = out_dtype == torch.bfloat16 and log and want_x       # see _DmelFunction.forward
-        kdtype = torch.float32 if round_later else out_dtype
-        out = torch.empty((B, 1, plan.n_mels, plan.n_time), dtype=kdtype, device=x.device)
-        tangent = torch.empty(out.shape, dtype=torch.float32, device=x.device) if want_tangent else None
-        scratch = torch.empty((plan.scratch_bytes(B),), dtype=torch.uint8, device=x.device)
-        lam = lambd.detach()
-        if lam.dtype != torch.float32:
-            lam = lam.to(torch.float32)
-        flags = capi.DMEL_FLAG_OUT_BF16 if kdtype == torch.bfloat16 else 0
+        want_x, want_tangent = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        out, tangent, scratch, round_later = _alloc(x, (B, 1, plan.n_mels, plan.n_time), out_dtype, want_tangent, log and want_x,
+                                                    plan.scratch_bytes(B))
+        lam = _lambd_f32(lambd)
         ctx.cands = None
         with _on_device(x.device):
             if lam_host is not None:
-                plan.forward_lengths(x.data_ptr(), lengths.data_ptr(), B, lam_host, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
-                                     log, eps, _stream_ptr(x.device), scratch.data_ptr(), extra_flags=flags)
+                plan.forward_lengths(x.data_ptr(), lengths.data_ptr(), B, lam_host, out.data_ptr(), _ptr(tangent), log, eps,
+                                     _stream_ptr(x.device), scratch.data_ptr(), extra_flags=_out_flag(out))
             else:
-                plan.forward_dev_lengths(x.data_ptr(), lengths.data_ptr(), B, lam.data_ptr(), out.data_ptr(),
-                                         tangent.data_ptr() if want_tangent else None, log, eps, _stream_ptr(x.device), scratch.data_ptr(),
-                                         extra_flags=flags)
-                # what that call launched for (host-side bookkeeping of the plan: no device read)
-                n0, guards = plan.info()["n_fft"], plan.lambd_status()["guards"]
-                ctx.cands = [n0] + ([2 * n0] if guards & 2 else []) + ([n0 // 2] if guards & 1 else [])
+                plan.forward_dev_lengths(x.data_ptr(), lengths.data_ptr(), B, lam.data_ptr(), out.data_ptr(), _ptr(tangent), log, eps,
+                                         _stream_ptr(x.device), scratch.data_ptr(), extra_flags=_out_flag(out))
+                ctx.cands = _launched_for(plan)
         ctx.plan, ctx.lam_host, ctx.log = plan, lam_host, bool(log)
         ctx.lambd_shape, ctx.lambd_dtype = lambd.shape, lambd.dtype
         ctx.want_tangent, ctx.want_x = want_tangent, want_x
@@ -294,35 +325,25 @@ class _DmelLenXFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         saved = list(ctx.saved_tensors)
         scratch = saved.pop(0)
-        bf16 = grad_out.dtype == torch.bfloat16
-        g = grad_out
-        if not bf16 and g.dtype != torch.float32:
-            g = g.to(torch.float32)
-        if not g.is_contiguous():
-            g = g.contiguous()
+        g, bf16 = _cotangent(grad_out)
         dl = gx = None
+        stream = _stream_ptr(g.device)
         with _on_device(g.device):
             if ctx.want_tangent:
                 tangent = saved.pop(0)
                 dl = torch.empty(tuple(ctx.lambd_shape), dtype=torch.float32, device=g.device)
-                ctx.plan.backward_scratch(g.data_ptr(), tangent.data_ptr(), g.numel(), dl.data_ptr(), _stream_ptr(g.device), scratch.data_ptr(),
-                                          grad_bf16=bf16)
-                if ctx.lambd_dtype != torch.float32:
-                    dl = dl.to(ctx.lambd_dtype)
+                ctx.plan.backward_scratch(g.data_ptr(), tangent.data_ptr(), g.numel(), dl.data_ptr(), stream, scratch.data_ptr(), grad_bf16=bf16)
+                dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
             if ctx.want_x:
                 x, lengths, lam = saved.pop(0), saved.pop(0), saved.pop(0)
                 out = saved.pop(0) if ctx.log else None
                 g32 = g.to(torch.float32)
-                optr = out.data_ptr() if ctx.log else None
                 if ctx.cands is None:
                     gx = torch.empty_like(x)
-                    ctx.plan.backward_x_lengths(x.data_ptr(), lengths.data_ptr(), x.shape[0], ctx.lam_host, g32.data_ptr(), optr, gx.data_ptr(),
-                                                ctx.log, _stream_ptr(g.device))
+                    ctx.plan.backward_x_lengths(x.data_ptr(), lengths.data_ptr(), x.shape[0], ctx.lam_host, g32.data_ptr(), _ptr(out),
+                                                gx.data_ptr(), ctx.log, stream)
                 else:
-                    gx = torch.full_like(x, float("nan"))
-                    for n in ctx.cands:
-                        ctx.plan.backward_x_dev_lengths(x.data_ptr(), lengths.data_ptr(), x.shape[0], lam.data_ptr(), n, g32.data_ptr(), optr,
-                                                        gx.data_ptr(), ctx.log, _stream_ptr(g.device), extra_flags=capi.DMEL_FLAG_CHECK_NFFT)
+                    gx = _tracked_backward_x(ctx.plan, x, lengths, lam, ctx.cands, g32, out, ctx.log, stream)
         return gx, None, dl, None, None, None, None, None
 
 
@@ -371,28 +392,129 @@ def _len_op():
     return _LEN_OP
 
 
-def _to_f32(x: torch.Tensor) -> torch.Tensor:
-    """The kernels compute in fp32.  The reference removes the clip mean in the INPUT dtype (models.py:38: ``x[idx] - torch.mean(x[idx])``):
+def _as_f32_contiguous(x: torch.Tensor, lengths=None) -> torch.Tensor:
+    """``x`` as the kernels read it: fp32 and contiguous.  Nothing is called on a tensor that already is (each no-op torch call still
+    costs ~2 us of host time on the hot path); when x requires grad its gradient flows back through these torch ops.
+    The kernels compute in fp32.  The reference removes the clip mean in the INPUT dtype (models.py:38: ``x[idx] - torch.mean(x[idx])``):
     for fp64 clips (GaussPulse, datasets.py:33) that subtraction happens here, in fp64, BEFORE the cast -- a DC offset far above the
     signal would otherwise cost the signal its low bits in the rounding to fp32 (tests/golden g13_dc_*_fp64: 1e-2 on the lowest mel
-    band).  The kernels' own DC removal then finds a mean of rounding size.  Narrower dtypes are widened as they are."""
-    if x.dtype == torch.float64:
-        x = x - x.mean(dim=1, keepdim=True)
-    return x.to(torch.float32)
+    band).  The kernels' own DC removal then finds a mean of rounding size.  Narrower dtypes are widened as they are.
+    With ``lengths`` (forward(x, lengths)) an fp64 clip loses its own mean, over ``x[b, :lengths[b]]``: a masked sum divided by the
+    length, on the device (no host read, so a captured step stays capturable).  Samples past a clip are masked out of the sum (NaN or
+    inf there reaches no output); an invalid length changes only its own clip, which the kernel makes NaN."""
+    if x.dtype != torch.float32:
+        if x.dtype == torch.float64 and lengths is None:
+            x = x - x.mean(dim=1, keepdim=True)
+        elif x.dtype == torch.float64:
+            inside = torch.arange(x.shape[1], device=x.device)[None, :] < lengths[:, None]
+            mean = torch.where(inside, x, 0.0).sum(dim=1, keepdim=True) / lengths.clamp(min=1)[:, None].to(torch.float64)
+            x = x - mean
+        x = x.to(torch.float32)
+    return x if x.is_contiguous() else x.contiguous()
 
 
-def _to_f32_lengths(x: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
-    """_to_f32 for forward(x, lengths): an fp64 clip loses its own mean, over ``x[b, :lengths[b]]``, in fp64 before the cast (a masked sum
-    divided by the length, on the device: no host read, so a captured step stays capturable).  Samples past a clip are masked out of the
-    sum (NaN or inf there reaches no output); an invalid length changes only its own clip, which the kernel makes NaN."""
-    if x.dtype == torch.float64:
-        inside = torch.arange(x.shape[1], device=x.device)[None, :] < lengths[:, None]
-        mean = torch.where(inside, x, 0.0).sum(dim=1, keepdim=True) / lengths.clamp(min=1)[:, None].to(torch.float64)
-        x = x - mean
-    return x.to(torch.float32)
+def _lambd_for_op(lam):
+    """lambd as torch.ops.dmel.* take it: the parameter itself (their autograd node returns its gradient), through a cast unless fp32"""
+    return lam if lam.dtype == torch.float32 else lam.to(torch.float32)
 
 
-class MelSpectrogramLayer(nn.Module):
+def _no_lengths(name: str) -> str:
+    return f"{name} does not take per-clip lengths (MelSpectrogramLayer does)"
+
+
+def _check_input(name, x, lambd, lengths=None, *, n_points=None, check_lengths=None, refuse_slot=None, slot_config_ok=None,
+                 refuse_x_grad=None):
+    """Every refusal the ``forward`` of a layer class starts with, in one order (the order decides which error wins when two apply).
+    ``name``: the class, for the messages.  What the class accepts:
+      ``n_points``       the clip length it was built for; None: any (SpectrogramLayer, optimized=False)
+      ``check_lengths``  None: per-clip lengths are refused; else ``(x, lengths) -> lengths`` that validates and converts them
+      ``refuse_slot``    the message a class that takes no SlotInput refuses one with
+      ``slot_config_ok`` ``() -> bool`` of the one class that takes a SlotInput: is this layer configured as a slot needs
+      ``refuse_x_grad``  the message an ``x`` that requires grad is refused with; None: it is accepted
+    Returns the converted ``lengths`` (None without them)."""
+    if lengths is not None and check_lengths is None:
+        raise RuntimeError(_no_lengths(name))
+    if refuse_slot is not None and isinstance(x, SlotInput):
+        raise RuntimeError(refuse_slot)
+    if x.dim() != 2:
+        raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
+    if n_points is not None and x.shape[1] != n_points:
+        # the reference fails here too (RuntimeError from the slice-assign at models.py:54)
+        raise RuntimeError(f"input has {x.shape[1]} points, the layer was built for n_points={n_points}")
+    if lengths is not None:
+        lengths = check_lengths(x, lengths)
+    if slot_config_ok is not None and isinstance(x, SlotInput):
+        # the batch by address: the hot path only (HTK bank, optimized=True, lambd on the device)
+        if not slot_config_ok():
+            raise RuntimeError("a SlotInput needs the default layer: HTK bank, optimized=True, lambd_sync=False")
+        if lambd.device != x.device:
+            raise RuntimeError(f"lambd is on {lambd.device} but the slot is on {x.device}; call layer.to(device)")
+        return lengths
+    if not x.is_cuda:
+        raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
+    if refuse_x_grad is not None and x.requires_grad:
+        raise RuntimeError(refuse_x_grad)
+    if lambd.device != x.device:
+        raise RuntimeError(f"lambd is on {lambd.device} but x is on {x.device}; call layer.to(x.device)")
+    return lengths
+
+
+class _PlanCache(nn.Module):
+    """A module with a cache of capi.Plan objects (device tables), one per device and, where a subclass says so, per shape.  Plans are
+    not state: copies and pickles of the layer start without them and rebuild them on first use."""
+
+    def __init__(self):
+        super().__init__()
+        self._plans = {}                                              # device index [, shape key ...] -> capi.Plan
+
+    def _make_plan(self, *shape_key) -> capi.Plan:
+        """the plan of this layer's mel configuration (called on the plan's device)"""
+        return capi.Plan(self.n_points, self.hop_length, self.n_mels, self.sample_rate, float(self.f_min), float(self.f_max),
+                         bool(self.normalize_window))
+
+    def _plan_for(self, dev: torch.device, *shape_key) -> capi.Plan:
+        idx = dev.index if dev.index is not None else torch.cuda.current_device()
+        key = (idx,) + shape_key if shape_key else idx
+        plan = self._plans.get(key)
+        if plan is None:
+            with torch.cuda.device(idx):
+                plan = self._make_plan(*shape_key)
+            if getattr(self, "_tracking", None) is not None:
+                plan.set_tracking(*self._tracking)
+            self._plans[key] = plan
+        return plan
+
+    def _plan_on(self, device=None) -> capi.Plan:
+        """the plan on ``device`` (default: the current one), for the status calls"""
+        return self._plan_for(torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device))
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_plans"] = {}
+        return state
+
+
+class _PlanCachingModule(_PlanCache):
+    """_PlanCache of a layer whose sync-free path tracks ``lambd`` on the host side of its plans."""
+
+    def resync(self):
+        """Forget what the sync-free path knows about lambd (every channel's; call after rewriting it from outside the optimizer, e.g.
+        ``layer.lambd.data.fill_(v)``); the next forward reads it once.  ``load_state_dict`` does this by itself."""
+        for plan in self._plans.values():
+            plan.lambd_reset()
+
+    def set_tracking(self, max_ahead: int = 8, guard_mode: int = 0):
+        """Run-ahead bound and guard policy of the sync-free path (dmel_plan_set_tracking); applies to plans made later too."""
+        self._tracking = (int(max_ahead), int(guard_mode))
+        for plan in self._plans.values():
+            plan.set_tracking(*self._tracking)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        self.resync()
+
+
+class MelSpectrogramLayer(_PlanCachingModule):
     """Differentiable (log-)Mel spectrogram with a trainable Gaussian window width.
 
     Signature-compatible with the reference (models.py:15):
@@ -468,8 +590,6 @@ class MelSpectrogramLayer(nn.Module):
             raise ValueError("out_dtype must be torch.float32 (the reference's, models.py:36) or torch.bfloat16")
         self.out_dtype = out_dtype
         self.lambd_sync = bool(lambd_sync)
-        self._plans = {}                                              # device index -> capi.Plan (not state)
-        self._fb_synced = {}                                          # device index -> (version, data_ptr) last sent to the plan
         if learnable_fb:
             n0 = capi.n_fft(float(init_lambd)) if optimized else 2 * n_points
             fb0 = capi.mel_fbanks_host(n0 // 2 + 1, float(self.f_min), float(self.f_max), n_mels, sample_rate)   # models.py:42-48
@@ -478,21 +598,8 @@ class MelSpectrogramLayer(nn.Module):
             self.mel_fb = None
 
     # -- plumbing -----------------------------------------------------------------------------
-    def _plan_for(self, dev: torch.device) -> capi.Plan:
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        plan = self._plans.get(idx)
-        if plan is None:
-            with torch.cuda.device(idx):
-                plan = capi.Plan(self.n_points, self.hop_length, self.n_mels, self.sample_rate, float(self.f_min),
-                                 float(self.f_max), bool(self.normalize_window))
-            if getattr(self, "_tracking", None) is not None:
-                plan.set_tracking(*self._tracking)
-            self._plans[idx] = plan
-        return plan
-
     def plan_info(self, device=None) -> dict:
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return self._plan_for(dev).info()
+        return self._plan_on(device).info()
 
     def _lambd_host(self) -> float:
         """Host value of lambd: a device->host read (the reference does one per sample, time_frequency.py:39).  Never
@@ -504,45 +611,34 @@ class MelSpectrogramLayer(nn.Module):
         in the optimized=False branch (time_frequency.py:51).  Reads lambd to the host."""
         return capi.n_fft(self._lambd_host()) if self.optimized else 2 * self.n_points
 
-    def resync(self):
-        """Forget what the sync-free path knows about lambd (call after rewriting it from outside the optimizer, e.g.
-        ``layer.lambd.data.fill_(v)``); the next forward reads it once.  ``load_state_dict`` does this by itself."""
-        for plan in self._plans.values():
-            plan.lambd_reset()
-
     def lambd_status(self, device=None) -> dict:
         """What the kernels last reported (no synchronisation): see dmel_lambd_status in include/dmel.h."""
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return self._plan_for(dev).lambd_status()
-
-    def set_tracking(self, max_ahead: int = 8, guard_mode: int = 0):
-        """Run-ahead bound and guard policy of the sync-free path (dmel_plan_set_tracking); applies to plans made later too."""
-        self._tracking = (int(max_ahead), int(guard_mode))
-        for plan in self._plans.values():
-            plan.set_tracking(*self._tracking)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        super()._load_from_state_dict(*args, **kwargs)
-        self.resync()
-
-    # plans are caches of device tables: copies and pickles of the layer start without them
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state["_plans"] = {}
-        state["_fb_synced"] = {}
-        return state
+        return self._plan_on(device).lambd_status()
 
     def frame_lengths(self, lengths: torch.Tensor) -> torch.Tensor:
         """Valid frames per clip of ``forward(x, lengths)``: ``lengths // hop_length + 1`` (models.py:30 at ``n_points = lengths[b]``),
         on the tensor's own device."""
         return lengths // self.hop_length + 1
 
-    # -- forward ------------------------------------------------------------------------------
-    def _forward_lengths(self, x, lengths):
-        """forward(x, lengths): torch.ops.dmel.mel_spectrogram_lengths (the hot path's C++ autograd node over dmel_forward_dev_lengths, or
-        dmel_forward_lengths with lambd_sync).  Shape, dtype and device of ``lengths`` are checked here; its values never leave the device.
-        With ``lengths_waveform_grad=True`` an ``x`` that requires grad takes _DmelLenXFunction instead: the same launches, and a backward to
-        the waveform."""
+    def _slot_config_ok(self) -> bool:
+        return self.mel_fb is None and self.optimized and not self.lambd_sync
+
+    def _sync_filterbank(self, plan, n, x):
+        """The plan's tables for n_fft ``n`` are refreshed from the parameter's storage by one small kernel on the current stream at
+        every forward (no host copy, no synchronisation: the matrix changes at every optimizer step, and writes through .data leave no
+        trace to ask torch about)."""
+        fb = self.mel_fb
+        if fb.device != x.device:
+            raise RuntimeError(f"mel_fb is on {fb.device} but x is on {x.device}; call layer.to(x.device)")
+        fbd = fb.detach()
+        if fbd.dtype != torch.float32 or not fbd.is_contiguous():
+            fbd = fbd.to(torch.float32).contiguous()
+        with _on_device(x.device):
+            plan.set_filterbank_dev(n, fbd.data_ptr(), _stream_ptr(x.device))
+
+    def _check_lengths(self, x, lengths):
+        """Whether this layer takes per-clip lengths, then shape, dtype and device of ``lengths``; returns them as the kernels read them
+        (int32, contiguous, on x's device).  Their values never leave the device."""
         want_x = self.lengths_waveform_grad and torch.is_grad_enabled() and not isinstance(x, SlotInput) and x.requires_grad
         if self.mel_fb is not None:
             raise RuntimeError("per-clip lengths run the HTK bank only: learnable_fb=True does not take lengths"
@@ -563,74 +659,42 @@ class MelSpectrogramLayer(nn.Module):
         if lengths.dtype != torch.int32:
             # int64 values clamped on the device before the narrowing: a length such as 2**32 + 4000 must stay invalid (NaN), not wrap to 4000
             lengths = lengths.clamp(0, self.n_points + 1).to(torch.int32)
-        if not lengths.is_contiguous():
-            lengths = lengths.contiguous()
+        return lengths if lengths.is_contiguous() else lengths.contiguous()
+
+    # -- forward ------------------------------------------------------------------------------
+    def _forward_lengths(self, x, lengths):
+        """forward(x, lengths), both checked: torch.ops.dmel.mel_spectrogram_lengths (the hot path's C++ autograd node over
+        dmel_forward_dev_lengths, or dmel_forward_lengths with lambd_sync).  With ``lengths_waveform_grad=True`` an ``x`` that requires
+        grad takes _DmelLenXFunction instead: the same launches, and a backward to the waveform."""
         flags = capi.DMEL_FLAG_LOG if self.log else 0
-        lam = self.lambd if self.lambd.dtype == torch.float32 else self.lambd.to(torch.float32)
         bf16 = self.out_dtype == torch.bfloat16
+        plan, lam = self._plan_for(x.device), _lambd_for_op(self.lambd)
         if isinstance(x, SlotInput):
-            if self.lambd_sync:
-                raise RuntimeError("a SlotInput needs the default layer: HTK bank, optimized=True, lambd_sync=False")
-            if self.lambd.device != x.device:
-                raise RuntimeError(f"lambd is on {self.lambd.device} but the slot is on {x.device}; call layer.to(device)")
-            return _len_op()(x.view(), lengths, lam, self._plan_for(x.device).handle, flags | capi.DMEL_FLAG_X_INDIRECT, self.eps, False, bf16)
-        if not x.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
-        if x.requires_grad and not self.lengths_waveform_grad:
-            raise RuntimeError("per-clip lengths have no waveform gradient: pass x.detach()")
-        if self.lambd.device != x.device:
-            raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
-        xf = x if x.dtype == torch.float32 else _to_f32_lengths(x, lengths)
-        if not xf.is_contiguous():
-            xf = xf.contiguous()
+            return _len_op()(x.view(), lengths, lam, plan.handle, flags | capi.DMEL_FLAG_X_INDIRECT, self.eps, False, bf16)
+        xf = _as_f32_contiguous(x, lengths)
         if xf.requires_grad and torch.is_grad_enabled():
             # lengths_waveform_grad=True: the gradient flows back through the conversions above (the fp64 path's masked mean included)
-            return _DmelLenXFunction.apply(xf, lengths, self.lambd, self._plan_for(x.device), self._lambd_host() if self.lambd_sync else None,
-                                           self.log, self.eps, self.out_dtype)
-        return _len_op()(xf, lengths, lam, self._plan_for(x.device).handle, flags, self.eps, self.lambd_sync, bf16)
+            return _DmelLenXFunction.apply(xf, lengths, self.lambd, plan, self._lambd_host() if self.lambd_sync else None, self.log, self.eps,
+                                           self.out_dtype)
+        return _len_op()(xf, lengths, lam, plan.handle, flags, self.eps, self.lambd_sync, bf16)
 
     def forward(self, x, lengths=None):
+        no_x_grad = None if lengths is None or self.lengths_waveform_grad else "per-clip lengths have no waveform gradient: pass x.detach()"
+        lam = self.lambd                # (read once: a parameter is found through nn.Module.__getattr__, a quarter of a microsecond)
+        lengths = _check_input("MelSpectrogramLayer", x, lam, lengths, n_points=self.n_points, check_lengths=self._check_lengths,
+                               slot_config_ok=self._slot_config_ok, refuse_x_grad=no_x_grad)
         if lengths is not None:
-            if x.dim() != 2:
-                raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
-            if x.shape[1] != self.n_points:
-                raise RuntimeError(f"input has {x.shape[1]} points, the layer was built for n_points={self.n_points}")
             return self._forward_lengths(x, lengths)
-        if x.dim() != 2:
-            raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
-        batch_size, n_points = x.shape
-        if n_points != self.n_points:
-            # the reference fails here too (RuntimeError from the slice-assign at models.py:54)
-            raise RuntimeError(f"input has {n_points} points, the layer was built for n_points={self.n_points}")
-        if isinstance(x, SlotInput):
-            # the batch by address: the hot path only (HTK bank, optimized=True, lambd on the device)
-            if self.mel_fb is not None or not self.optimized or self.lambd_sync:
-                raise RuntimeError("a SlotInput needs the default layer: HTK bank, optimized=True, lambd_sync=False")
-            if self.lambd.device != x.device:
-                raise RuntimeError(f"lambd is on {self.lambd.device} but the slot is on {x.device}; call layer.to(device)")
-            lam = self.lambd if self.lambd.dtype == torch.float32 else self.lambd.to(torch.float32)
-            flags = (capi.DMEL_FLAG_LOG if self.log else 0) | capi.DMEL_FLAG_X_INDIRECT
-            return _mel_op()(x.view(), lam, self._plan_for(x.device).handle, flags, self.eps, False, self.out_dtype == torch.bfloat16)
-        if not x.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
-        if self.lambd.device != x.device:
-            raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
-        # dtype / layout conversions only when needed (each no-op torch call still costs ~2 us of host time); when x requires
-        # grad its gradient (dmel_backward_x) flows back through these torch ops
-        xf = x
-        if xf.dtype != torch.float32:
-            xf = _to_f32(xf)
-        if not xf.is_contiguous():
-            xf = xf.contiguous()
         plan = self._plan_for(x.device)
+        if isinstance(x, SlotInput):
+            flags = (capi.DMEL_FLAG_LOG if self.log else 0) | capi.DMEL_FLAG_X_INDIRECT
+            return _mel_op()(x.view(), _lambd_for_op(lam), plan.handle, flags, self.eps, False, self.out_dtype == torch.bfloat16)
+        xf = _as_f32_contiguous(x)
         fb = self.mel_fb
         if fb is None and not x.requires_grad:
             # the hot path: torch-registered op, C++ autograd node, lambd read on the device unless lambd_sync
             flags = (capi.DMEL_FLAG_LOG if self.log else 0) | (0 if self.optimized else capi.DMEL_FLAG_FULL_WINDOW)
-            lam = self.lambd
-            if lam.dtype != torch.float32:
-                lam = lam.to(torch.float32)
-            return _mel_op()(xf, lam, plan.handle, flags, self.eps, self.lambd_sync, self.out_dtype == torch.bfloat16)
+            return _mel_op()(xf, _lambd_for_op(lam), plan.handle, flags, self.eps, self.lambd_sync, self.out_dtype == torch.bfloat16)
         if not self.lambd_sync:
             # sync-free: a trainable filterbank fixes n_fft (its row count; lambd is read and checked on the device: one that has left
             # that n_fft gives NaN now and a RuntimeError at the next forward, as models.py:53 fails on the shape), the optimized=False
@@ -643,14 +707,8 @@ class MelSpectrogramLayer(nn.Module):
                 if fb.shape[0] != n // 2 + 1:
                     raise RuntimeError(f"mel_fb was built for n_fft={2 * (fb.shape[0] - 1)} but this layer runs n_fft={n}; "
                                        "a learnable filterbank is tied to one n_fft")
-                if fb.device != x.device:
-                    raise RuntimeError(f"mel_fb is on {fb.device} but x is on {x.device}; call layer.to(x.device)")
-                fbd = fb.detach()
-                if fbd.dtype != torch.float32 or not fbd.is_contiguous():
-                    fbd = fbd.to(torch.float32).contiguous()
-                with _on_device(x.device):
-                    plan.set_filterbank_dev(n, fbd.data_ptr(), _stream_ptr(x.device))
-            return _DmelFbDevFunction.apply(xf, self.lambd, plan, n, self.log, self.eps, fb, self.out_dtype, full,
+                self._sync_filterbank(plan, n, x)
+            return _DmelFbDevFunction.apply(xf, lam, plan, n, self.log, self.eps, fb, self.out_dtype, full,
                                             capi.DMEL_FLAG_MFMA_BF16X3 if self.mfma == "bf16x3" else 0, self.save_spec)
         lam_host = self._lambd_host()
         if fb is not None:
@@ -658,17 +716,8 @@ class MelSpectrogramLayer(nn.Module):
             if fb.shape[0] != n // 2 + 1:
                 raise RuntimeError(f"mel_fb was built for n_fft={2 * (fb.shape[0] - 1)} but lambd={lam_host} now gives n_fft={n}; "
                                    "a learnable filterbank is tied to one n_fft")
-            if fb.device != x.device:
-                raise RuntimeError(f"mel_fb is on {fb.device} but x is on {x.device}; call layer.to(x.device)")
-            # the plan's tables are refreshed from the parameter's storage by one small kernel on the current stream at every
-            # forward (no host copy, no synchronisation: the matrix changes at every optimizer step, and writes through
-            # .data leave no trace to ask torch about)
-            fbd = fb.detach()
-            if fbd.dtype != torch.float32 or not fbd.is_contiguous():
-                fbd = fbd.to(torch.float32).contiguous()
-            with _on_device(x.device):
-                plan.set_filterbank_dev(n, fbd.data_ptr(), _stream_ptr(x.device))
-        return _DmelFunction.apply(xf, self.lambd, plan, lam_host, self.log, self.eps, not self.optimized, fb, self.out_dtype)
+            self._sync_filterbank(plan, n, x)
+        return _DmelFunction.apply(xf, lam, plan, lam_host, self.log, self.eps, not self.optimized, fb, self.out_dtype)
 
     def extra_repr(self):
         return (f"n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
@@ -685,25 +734,19 @@ class _MultiFunction(torch.autograd.Function):
     def forward(ctx, x, lambd, plan, lam_host, log, eps, out_dtype, want_tangent):
         B, K = x.shape[0], lambd.shape[0]
         want_x = ctx.needs_input_grad[0]
-        # the waveform gradient rebuilds 1 / (mel + eps) from the saved log output: fp32 here, rounded to bf16 afterwards (as _DmelFunction)
-        round_later = out_dtype == torch.bfloat16 and log and want_x
-        kdtype = torch.float32 if round_later else out_dtype
-        out = torch.empty((B, K, plan.n_mels, plan.n_time), dtype=kdtype, device=x.device)
-        tangent = torch.empty(out.shape, dtype=torch.float32, device=x.device) if want_tangent else None
-        scratch = torch.empty((plan.scratch_bytes_multi(B, K),), dtype=torch.uint8, device=x.device)
-        bf16 = kdtype == torch.bfloat16
+        out, tangent, scratch, round_later = _alloc(x, (B, K, plan.n_mels, plan.n_time), out_dtype, want_tangent, log and want_x,
+                                                    plan.scratch_bytes_multi(B, K))
+        bf16 = out.dtype == torch.bfloat16
         lam = None
         with _on_device(x.device):
             if lam_host is not None:
-                plan.forward_multi(x.data_ptr(), B, lam_host, out.data_ptr(), tangent.data_ptr() if want_tangent else None, log, eps,
-                                   _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
+                plan.forward_multi(x.data_ptr(), B, lam_host, out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
+                                   scratch.data_ptr(), out_bf16=bf16)
             else:
-                lam = lambd.detach()
-                if lam.dtype != torch.float32 or not lam.is_contiguous():
-                    lam = lam.to(torch.float32).contiguous()
-                plan.forward_multi_dev(x.data_ptr(), B, lam.data_ptr(), K, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
-                                       log, eps, _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
-        ctx.plan, ctx.K, ctx.lambd_dtype = plan, K, lambd.dtype
+                lam = _lambd_f32(lambd)
+                plan.forward_multi_dev(x.data_ptr(), B, lam.data_ptr(), K, out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
+                                       scratch.data_ptr(), out_bf16=bf16)
+        ctx.plan, ctx.K, ctx.lambd_shape, ctx.lambd_dtype = plan, K, lambd.shape, lambd.dtype
         ctx.want_tangent, ctx.want_x, ctx.log, ctx.lam_host = want_tangent, want_x, bool(log), lam_host
         # what this forward launched for (host bookkeeping of the plan, no device read): a later forward cannot change what the backward covers
         ctx.launches = plan.last_multi_launch() if (want_x and lam_host is None) else None
@@ -716,12 +759,7 @@ class _MultiFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         saved = list(ctx.saved_tensors)
-        bf16 = grad_out.dtype == torch.bfloat16
-        g = grad_out
-        if not bf16 and g.dtype != torch.float32:
-            g = g.to(torch.float32)
-        if not g.is_contiguous():
-            g = g.contiguous()
+        g, bf16 = _cotangent(grad_out)
         dl = gx = None
         with _on_device(g.device):
             if ctx.want_tangent:
@@ -729,8 +767,7 @@ class _MultiFunction(torch.autograd.Function):
                 dl = torch.empty((ctx.K,), dtype=torch.float32, device=g.device)
                 ctx.plan.backward_multi(g.data_ptr(), tangent.data_ptr(), g.shape[0], ctx.K, dl.data_ptr(), _stream_ptr(g.device),
                                         scratch.data_ptr(), grad_bf16=bf16)
-                if ctx.lambd_dtype != torch.float32:
-                    dl = dl.to(ctx.lambd_dtype)
+                dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
             if ctx.want_x:
                 x = saved.pop(0)
                 lam = saved.pop(0) if ctx.lam_host is None else None
@@ -738,15 +775,15 @@ class _MultiFunction(torch.autograd.Function):
                 g32 = g.to(torch.float32)
                 gx = torch.empty_like(x)
                 if lam is None:
-                    ctx.plan.backward_x_multi(x.data_ptr(), x.shape[0], ctx.lam_host, g32.data_ptr(), out.data_ptr() if ctx.log else None,
-                                              gx.data_ptr(), ctx.log, _stream_ptr(g.device))
+                    ctx.plan.backward_x_multi(x.data_ptr(), x.shape[0], ctx.lam_host, g32.data_ptr(), _ptr(out), gx.data_ptr(), ctx.log,
+                                              _stream_ptr(g.device))
                 else:
-                    ctx.plan.backward_x_multi_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.K, ctx.launches, g32.data_ptr(),
-                                                  out.data_ptr() if ctx.log else None, gx.data_ptr(), ctx.log, _stream_ptr(g.device))
+                    ctx.plan.backward_x_multi_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.K, ctx.launches, g32.data_ptr(), _ptr(out),
+                                                  gx.data_ptr(), ctx.log, _stream_ptr(g.device))
         return gx, dl, None, None, None, None, None, None
 
 
-class MultiWindowMelSpectrogram(nn.Module):
+class MultiWindowMelSpectrogram(_PlanCachingModule):
     """K trainable window widths at once, returned as K output channels.
 
         MultiWindowMelSpectrogram(init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1,
@@ -791,69 +828,27 @@ class MultiWindowMelSpectrogram(nn.Module):
         self.n_time = n_points // hop_length + 1
         self.log, self.eps, self.out_dtype, self.lambd_sync = bool(log), float(eps), out_dtype, bool(lambd_sync)
         self.waveform_grad = bool(waveform_grad)
-        self._plans = {}
 
     @property
     def channels(self) -> int:
         return self.lambd.shape[0]
 
-    def _plan_for(self, dev: torch.device) -> capi.Plan:
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        plan = self._plans.get(idx)
-        if plan is None:
-            with torch.cuda.device(idx):
-                plan = capi.Plan(self.n_points, self.hop_length, self.n_mels, self.sample_rate, float(self.f_min), float(self.f_max),
-                                 bool(self.normalize_window))
-            if getattr(self, "_tracking", None) is not None:
-                plan.set_tracking(*self._tracking)
-            self._plans[idx] = plan
-        return plan
-
-    def resync(self):
-        """Forget what the sync-free path knows about every channel's lambd (after writing it through ``.data``)."""
-        for plan in self._plans.values():
-            plan.lambd_reset()
-
     def lambd_status(self, channel: int = 0, device=None) -> dict:
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        return self._plan_for(dev).lambd_status_channel(channel)
+        return self._plan_on(device).lambd_status_channel(channel)
 
-    def set_tracking(self, max_ahead: int = 8, guard_mode: int = 0):
-        self._tracking = (int(max_ahead), int(guard_mode))
-        for plan in self._plans.values():
-            plan.set_tracking(*self._tracking)
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        super()._load_from_state_dict(*args, **kwargs)
-        self.resync()
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state["_plans"] = {}
-        return state
-
-    def forward(self, x, lengths=None):
-        if lengths is not None:
-            raise RuntimeError("MultiWindowMelSpectrogram does not take per-clip lengths (MelSpectrogramLayer does)")
-        if isinstance(x, SlotInput):
-            raise RuntimeError("MultiWindowMelSpectrogram does not take a SlotInput")
-        if x.dim() != 2:
-            raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
-        if x.shape[1] != self.n_points:
-            raise RuntimeError(f"input has {x.shape[1]} points, the layer was built for n_points={self.n_points}")
-        if not x.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
-        if x.requires_grad and not self.waveform_grad:
-            raise RuntimeError("MultiWindowMelSpectrogram has no waveform gradient by default: pass waveform_grad=True, or x.detach()")
-        if self.lambd.device != x.device:
-            raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
-        xf = x if x.dtype == torch.float32 else _to_f32(x)
-        if not xf.is_contiguous():
-            xf = xf.contiguous()
+    def _prepare(self, name, x, lengths, refuse_slot, refuse_x_grad):
+        """the checks and conversions the K-channel forwards share: (x as fp32, lambd's host values or None, whether to carry the tangent)"""
+        _check_input(name, x, self.lambd, lengths, n_points=self.n_points, refuse_slot=refuse_slot, refuse_x_grad=refuse_x_grad)
+        xf = _as_f32_contiguous(x)
         lam_host = [float(v) for v in self.lambd.detach().cpu().tolist()] if self.lambd_sync else None
         # the tangent only when a gradient will be asked for (as torch.ops.dmel.mel_spectrogram: grad mode and lambd.requires_grad);
         # otherwise the inference kernels, which pair two frames per FFT
-        want = torch.is_grad_enabled() and self.lambd.requires_grad
+        return xf, lam_host, torch.is_grad_enabled() and self.lambd.requires_grad
+
+    def forward(self, x, lengths=None):
+        no_x_grad = None if self.waveform_grad else ("MultiWindowMelSpectrogram has no waveform gradient by default: pass waveform_grad=True, "
+                                                     "or x.detach()")
+        xf, lam_host, want = self._prepare("MultiWindowMelSpectrogram", x, lengths, "MultiWindowMelSpectrogram does not take a SlotInput", no_x_grad)
         return _MultiFunction.apply(xf, self.lambd, self._plan_for(x.device), lam_host, self.log, self.eps, self.out_dtype, want)
 
     def extra_repr(self):
@@ -869,42 +864,31 @@ class _BandFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, lambd, plan, lam_host, edges, log, eps, out_dtype, want_tangent):
         B, K = x.shape[0], lambd.shape[0]
-        out = torch.empty((B, 1, plan.n_mels, plan.n_time), dtype=out_dtype, device=x.device)
-        tangent = torch.empty(out.shape, dtype=torch.float32, device=x.device) if want_tangent else None
-        scratch = torch.empty((plan.scratch_bytes_multi(B, K),), dtype=torch.uint8, device=x.device)
+        out, tangent, scratch, _ = _alloc(x, (B, 1, plan.n_mels, plan.n_time), out_dtype, want_tangent, False, plan.scratch_bytes_multi(B, K))
         bf16 = out_dtype == torch.bfloat16
         with _on_device(x.device):
             if lam_host is not None:
-                plan.forward_band(x.data_ptr(), B, lam_host, edges, out.data_ptr(), tangent.data_ptr() if want_tangent else None, log, eps,
-                                  _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
+                plan.forward_band(x.data_ptr(), B, lam_host, edges, out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
+                                  scratch.data_ptr(), out_bf16=bf16)
             else:
-                lam = lambd.detach()
-                if lam.dtype != torch.float32 or not lam.is_contiguous():
-                    lam = lam.to(torch.float32).contiguous()
-                plan.forward_band_dev(x.data_ptr(), B, lam.data_ptr(), edges, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
-                                      log, eps, _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
-        ctx.plan, ctx.K, ctx.lambd_dtype, ctx.edges, ctx.want_tangent = plan, K, lambd.dtype, edges, want_tangent
+                plan.forward_band_dev(x.data_ptr(), B, _lambd_f32(lambd).data_ptr(), edges, out.data_ptr(), _ptr(tangent), log, eps,
+                                      _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
+        ctx.plan, ctx.lambd_shape, ctx.lambd_dtype, ctx.edges, ctx.want_tangent = plan, lambd.shape, lambd.dtype, edges, want_tangent
         if want_tangent:
             ctx.save_for_backward(tangent, scratch)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        bf16 = grad_out.dtype == torch.bfloat16
-        g = grad_out
-        if not bf16 and g.dtype != torch.float32:
-            g = g.to(torch.float32)
-        if not g.is_contiguous():
-            g = g.contiguous()
+        g, bf16 = _cotangent(grad_out)
         dl = None
         if ctx.want_tangent:
             tangent, scratch = ctx.saved_tensors
             with _on_device(g.device):
-                dl = torch.empty((ctx.K,), dtype=torch.float32, device=g.device)
+                dl = torch.empty((len(ctx.edges) - 1,), dtype=torch.float32, device=g.device)
                 ctx.plan.backward_band(g.data_ptr(), tangent.data_ptr(), g.shape[0], ctx.edges, dl.data_ptr(), _stream_ptr(g.device),
                                        scratch.data_ptr(), grad_bf16=bf16)
-                if ctx.lambd_dtype != torch.float32:
-                    dl = dl.to(ctx.lambd_dtype)
+                dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
         return None, dl, None, None, None, None, None, None, None
 
 
@@ -956,26 +940,10 @@ class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
         self.band_edges = tuple(edges)
 
     def forward(self, x, lengths=None):
-        if lengths is not None:
-            raise RuntimeError("BandSplitMelSpectrogram does not take per-clip lengths (MelSpectrogramLayer does)")
-        if isinstance(x, SlotInput):
-            raise RuntimeError("BandSplitMelSpectrogram does not take a SlotInput: pass the batch tensor (MelSpectrogramLayer takes slots)")
-        if x.dim() != 2:
-            raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
-        if x.shape[1] != self.n_points:
-            raise RuntimeError(f"input has {x.shape[1]} points, the layer was built for n_points={self.n_points}")
-        if not x.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
-        if x.requires_grad:
-            raise RuntimeError("BandSplitMelSpectrogram has no waveform gradient: pass x.detach() (MelSpectrogramLayer and "
-                               "MultiWindowMelSpectrogram(waveform_grad=True) have one)")
-        if self.lambd.device != x.device:
-            raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
-        xf = x if x.dtype == torch.float32 else _to_f32(x)
-        if not xf.is_contiguous():
-            xf = xf.contiguous()
-        lam_host = [float(v) for v in self.lambd.detach().cpu().tolist()] if self.lambd_sync else None
-        want = torch.is_grad_enabled() and self.lambd.requires_grad
+        xf, lam_host, want = self._prepare("BandSplitMelSpectrogram", x, lengths,
+                                           "BandSplitMelSpectrogram does not take a SlotInput: pass the batch tensor (MelSpectrogramLayer takes slots)",
+                                           "BandSplitMelSpectrogram has no waveform gradient: pass x.detach() (MelSpectrogramLayer and "
+                                           "MultiWindowMelSpectrogram(waveform_grad=True) have one)")
         return _BandFunction.apply(xf, self.lambd, self._plan_for(x.device), lam_host, self.band_edges, self.log, self.eps, self.out_dtype, want)
 
     def extra_repr(self):
@@ -991,21 +959,16 @@ class _DspecFunction(torch.autograd.Function):
     def forward(ctx, x, lambd, plan, lam_host, n_fft, half_window):
         """lam_host None: lambd is read by the kernels from the parameter's storage (no host read: capturable)"""
         B = x.shape[0]
-        out = torch.empty((B, 1, n_fft // 2 + 1, plan.n_time), dtype=torch.float32, device=x.device)
         want_tangent = ctx.needs_input_grad[1]
-        tangent = torch.empty_like(out) if want_tangent else None
-        lam = None
-        if lam_host is None:
-            lam = lambd.detach()
-            if lam.dtype != torch.float32:
-                lam = lam.to(torch.float32)
+        out, tangent, _, _ = _alloc(x, (B, 1, n_fft // 2 + 1, plan.n_time), torch.float32, want_tangent)
+        lam = _lambd_f32(lambd) if lam_host is None else None
         with _on_device(x.device):
             if lam is None:
-                plan.spectrogram_ex(x.data_ptr(), B, lam_host, n_fft, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
-                                    _stream_ptr(x.device), remove_dc=True, half_window=half_window)
+                plan.spectrogram_ex(x.data_ptr(), B, lam_host, n_fft, out.data_ptr(), _ptr(tangent), _stream_ptr(x.device), remove_dc=True,
+                                    half_window=half_window)
             else:
-                plan.spectrogram_ex_dev(x.data_ptr(), B, lam.data_ptr(), n_fft, out.data_ptr(), tangent.data_ptr() if want_tangent else None,
-                                        _stream_ptr(x.device), remove_dc=True, half_window=half_window)
+                plan.spectrogram_ex_dev(x.data_ptr(), B, lam.data_ptr(), n_fft, out.data_ptr(), _ptr(tangent), _stream_ptr(x.device),
+                                        remove_dc=True, half_window=half_window)
         ctx.plan, ctx.lambd_shape, ctx.lambd_dtype = plan, lambd.shape, lambd.dtype
         ctx.want_tangent, ctx.want_x = want_tangent, ctx.needs_input_grad[0]
         ctx.args = (lam_host, n_fft, half_window)
@@ -1016,14 +979,14 @@ class _DspecFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         saved = list(ctx.saved_tensors)
-        g = grad_out.to(torch.float32).contiguous()
+        g = _cotangent(grad_out)[0].to(torch.float32)            # the spectrogram is fp32 only
         dl = gx = None
         with _on_device(g.device):
             if ctx.want_tangent:
                 tangent = saved.pop(0)
                 dl = torch.empty((1,), dtype=torch.float32, device=g.device)
                 ctx.plan.backward(g.data_ptr(), tangent.data_ptr(), g.numel(), dl.data_ptr(), _stream_ptr(g.device))
-                dl = dl.reshape(ctx.lambd_shape).to(ctx.lambd_dtype)
+                dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
             if ctx.want_x:
                 x = saved.pop(0)
                 lam_host, n_fft, half_window = ctx.args
@@ -1038,7 +1001,7 @@ class _DspecFunction(torch.autograd.Function):
         return gx, dl, None, None, None, None
 
 
-class SpectrogramLayer(nn.Module):
+class SpectrogramLayer(_PlanCache):
     """DSPEC: differentiable spectrogram with a trainable Gaussian window width.
 
     Signature-compatible with the reference (models.py:171-200):
@@ -1060,23 +1023,14 @@ class SpectrogramLayer(nn.Module):
         self.size = size
         self.optimized = optimized
         self.normalize_window = normalize_window
-        self._plans = {}
 
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state["_plans"] = {}
-        return state
+    def _make_plan(self, n_points) -> capi.Plan:
+        """one plan per (device, clip length); the mel stage is never run: a fixed dummy mel configuration, and no lambd tracking"""
+        return capi.Plan(n_points, self.hop_length, 1, 2, 0.0, 1.0, bool(self.normalize_window))
 
     def forward(self, x, lengths=None):
-        if lengths is not None:
-            raise RuntimeError("SpectrogramLayer does not take per-clip lengths (MelSpectrogramLayer does)")
-        if x.dim() != 2:
-            raise ValueError(f"expected x of shape (batch, n_points), got {tuple(x.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: x must be a CUDA/HIP tensor (no CPU fallback)")
-        batch_size, n_points = x.shape
-        if self.lambd.device != x.device:
-            raise RuntimeError(f"lambd is on {self.lambd.device} but x is on {x.device}; call layer.to(x.device)")
+        _check_input("SpectrogramLayer", x, self.lambd, lengths)
+        n_points = x.shape[1]
         # optimized=False (the reference's only DSPEC configuration, search_spaces.py:71-91): n_fft = 2 n_points whatever lambd is, so
         # lambd stays on the device -- no host read, the step is HIP-graph capturable.  optimized=True derives n_fft from lambd on the
         # host like the reference (time_frequency.py:39): the output SHAPE depends on it.
@@ -1088,14 +1042,7 @@ class SpectrogramLayer(nn.Module):
                 raise RuntimeError(f"size={tuple(self.size)} but the spectrogram is {expect}")
         else:
             n_fft, half = 2 * n_points, True      # any clip length: powers of two on the FFT kernels, the rest through Bluestein
-        key = (x.device.index, n_points)
-        plan = self._plans.get(key)
-        if plan is None:
-            with torch.cuda.device(x.device):
-                plan = capi.Plan(n_points, self.hop_length, 1, 2, 0.0, 1.0, bool(self.normalize_window))
-            self._plans[key] = plan
-        xf = x if x.dtype == torch.float32 else _to_f32(x)
-        return _DspecFunction.apply(xf.contiguous(), self.lambd, plan, lam_host, n_fft, half)
+        return _DspecFunction.apply(_as_f32_contiguous(x), self.lambd, self._plan_for(x.device, n_points), lam_host, n_fft, half)
 
 
 # BASELINE.json's north_star calls the layer by this name; the reference has no such symbol.
@@ -1106,7 +1053,7 @@ def dmel_log_mel(x, lambd, n_mels, sample_rate, hop_length, f_min=0.0, f_max=Non
                  log=True, eps=1e-10, _plan_cache={}, *, lengths=None):
     """Functional form: log-mel (or mel) of x with window width ``lambd`` (a tensor that may require grad)."""
     if lengths is not None:
-        raise RuntimeError("dmel_log_mel does not take per-clip lengths (MelSpectrogramLayer does)")
+        raise RuntimeError(_no_lengths("dmel_log_mel"))
     key = (x.device.index, x.shape[1], hop_length, n_mels, sample_rate, float(f_min), f_max, bool(normalize_window))
     plan = _plan_cache.get(key)
     if plan is None:
@@ -1114,4 +1061,4 @@ def dmel_log_mel(x, lambd, n_mels, sample_rate, hop_length, f_min=0.0, f_max=Non
             plan = capi.Plan(x.shape[1], hop_length, n_mels, sample_rate, float(f_min),
                              None if f_max is None else float(f_max), bool(normalize_window))
         _plan_cache[key] = plan
-    return _DmelFunction.apply(_to_f32(x.detach()).contiguous(), lambd, plan, float(lambd.detach()), log, eps)
+    return _DmelFunction.apply(_as_f32_contiguous(x.detach()), lambd, plan, float(lambd.detach()), log, eps)

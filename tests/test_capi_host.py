@@ -25,6 +25,25 @@ def test_library_exports_every_declared_symbol():
     assert L.dmel_abi_version() == 5
 
 
+def test_signature_table_has_the_headers_parameter_counts():
+    """capi's one table name -> (restype, argtypes) against include/dmel.h: an entry for every declared function with as many argtypes
+    as the declaration has parameters ((void) is none), and after load() every symbol carries them -- an entry point without argtypes
+    would receive its pointers as C int."""
+    from dmel_amd import capi
+    L = capi.load()
+    header = open(os.path.join(ROOT, "include", "dmel.h")).read()
+    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
+    decls = re.findall(r"\b(dmel_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code)
+    assert sorted(n for n, _ in decls) == sorted(capi.SYMBOLS)
+    for name, params in decls:
+        count = 0 if params.strip() == "void" else params.count(",") + 1
+        restype, argtypes = capi._SIGNATURES[name]
+        assert len(argtypes) == count, (name, count, argtypes)
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes), name
+        assert fn.restype is restype, name
+
+
 def test_n_fft_rule_matches_oracle_and_fixtures():
     from dmel_amd import capi
     for case in C.CASES:
