@@ -148,6 +148,8 @@ _SIGNATURES = {
     "dmel_forward_band": (status, [vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_band_dev": (status, [vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
     "dmel_backward_band": (status, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "dmel_backward_x_band": (status, [vp, vp, i32, fp, i32, vp, u32, vp, vp, vp, vp]),
+    "dmel_backward_x_band_dev": (status, [vp, vp, i32, vp, i32, vp, i32p, u32p, i32, u32, vp, vp, vp, vp]),
     "dmel_plan_get_info": (status, [vp, P(DmelPlanInfo)]),
     "dmel_plan_set_profiling": (status, [vp, i32]),
     "dmel_plan_get_profile": (status, [vp, P(DmelProfile)]),
@@ -471,25 +473,46 @@ class Plan:
         _check(load().dmel_backward_band(self._h, grad_ptr, DMEL_DTYPE_BF16 if grad_bf16 else DMEL_DTYPE_F32, tangent_ptr, int(batch),
                                          len(edges) - 1, ed, int(accumulate), dlambd_ptr, scratch_ptr, stream))
 
-    def backward_x_multi(self, x_ptr: int, batch: int, lambd, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int, log: bool, stream: int):
+    def backward_x_multi(self, x_ptr: int, batch: int, lambd, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int, log: bool, stream: int,
+                         edges=None):
         """dmel_backward_x_multi: grad_x = sum over channels (ascending) of the scalar layer's waveform gradient; lambd: the K host values;
-        grad_ptr / out_ptr: (B, K, M, T) fp32"""
+        grad_ptr / out_ptr: (B, K, M, T) fp32.  With ``edges`` (K + 1 host integers) dmel_backward_x_band: grad_ptr / out_ptr are ONE
+        (B, 1, M, T) image and channel k's cotangent is its rows edges[k] ... edges[k + 1] - 1, +0.0 elsewhere."""
         lam = _floats(lambd)
-        _check(load().dmel_backward_x_multi(self._h, x_ptr, batch, lam, len(lambd), DMEL_FLAG_LOG if log else 0, grad_ptr, out_ptr, grad_x_ptr,
-                                            stream))
+        flags = DMEL_FLAG_LOG if log else 0
+        if edges is None:
+            _check(load().dmel_backward_x_multi(self._h, x_ptr, batch, lam, len(lambd), flags, grad_ptr, out_ptr, grad_x_ptr, stream))
+        else:
+            _check(load().dmel_backward_x_band(self._h, x_ptr, batch, lam, len(lambd), _ints(edges), flags, grad_ptr, out_ptr, grad_x_ptr, stream))
 
     def backward_x_multi_dev(self, x_ptr: int, batch: int, lambd_ptr: int, channels: int, launches, grad_ptr: int, out_ptr: int | None,
-                             grad_x_ptr: int, log: bool, stream: int):
+                             grad_x_ptr: int, log: bool, stream: int, edges=None):
         """dmel_backward_x_multi_dev: lambd read on the device; launches: [(n_fft, channel mask), ...] of the forward whose gradient
-        this is (last_multi_launch() right after it)"""
+        this is (last_multi_launch() right after it).  With ``edges``: dmel_backward_x_band_dev (see backward_x_multi)."""
         k = max(len(launches), 1)
         ns = (C.c_int32 * k)(*[int(n) for n, _ in launches])
         masks = (C.c_uint32 * k)(*[int(m) for _, m in launches])
-        _check(load().dmel_backward_x_multi_dev(self._h, x_ptr, batch, lambd_ptr, int(channels), ns, masks, len(launches),
-                                                DMEL_FLAG_LOG if log else 0, grad_ptr, out_ptr, grad_x_ptr, stream))
+        flags = DMEL_FLAG_LOG if log else 0
+        if edges is None:
+            _check(load().dmel_backward_x_multi_dev(self._h, x_ptr, batch, lambd_ptr, int(channels), ns, masks, len(launches), flags,
+                                                    grad_ptr, out_ptr, grad_x_ptr, stream))
+        else:
+            _check(load().dmel_backward_x_band_dev(self._h, x_ptr, batch, lambd_ptr, int(channels), _ints(edges), ns, masks, len(launches),
+                                                   flags, grad_ptr, out_ptr, grad_x_ptr, stream))
+
+    def backward_x_band(self, x_ptr: int, batch: int, lambd, edges, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int, log: bool, stream: int):
+        """dmel_backward_x_band: the band-split layer's waveform gradient, lambd as K host values"""
+        self.backward_x_multi(x_ptr, batch, lambd, grad_ptr, out_ptr, grad_x_ptr, log, stream, edges=edges)
+
+    def backward_x_band_dev(self, x_ptr: int, batch: int, lambd_ptr: int, edges, launches, grad_ptr: int, out_ptr: int | None,
+                            grad_x_ptr: int, log: bool, stream: int):
+        """dmel_backward_x_band_dev: lambd read on the device; launches: last_multi_launch() right after the forward_band_dev whose
+        gradient this is"""
+        self.backward_x_multi_dev(x_ptr, batch, lambd_ptr, len(edges) - 1, launches, grad_ptr, out_ptr, grad_x_ptr, log, stream, edges=edges)
 
     def last_multi_launch(self) -> list[tuple[int, int]]:
-        """[(n_fft, channel mask), ...] in ascending n_fft: what the most recent forward_multi(_dev) on this plan issued (host bookkeeping)"""
+        """[(n_fft, channel mask), ...] in ascending n_fft: what the most recent forward_multi(_dev) / forward_band(_dev) on this plan issued
+        (host bookkeeping)"""
         ns, masks, cnt = (C.c_int32 * 24)(), (C.c_uint32 * 24)(), C.c_int32(0)
         _check(load().dmel_plan_last_multi_launch(self._h, ns, masks, C.byref(cnt)))
         return [(int(ns[i]), int(masks[i])) for i in range(cnt.value)]

@@ -2592,12 +2592,15 @@ dmel_status check_x_multi_args(dmel_plan* pl, const float* x, int batch, int cha
     return DMEL_OK;
 }
 
-// ns / mask / nl: the launch list (checked by the caller); lam_host (K values) or lam_dev (K device words) -- exactly one of them
+// ns / mask / nl: the launch list (checked by the caller); lam_host (K values) or lam_dev (K device words) -- exactly one of them.
+// edges (K + 1 validated band edges) or nullptr: the band-split layer, whose grad_out / out are ONE (B, 1, M, T) image -- channel c's mel
+// gradient is its rows [edges[c], edges[c + 1]) and +0.0 elsewhere -- or the multi-window layer's (B, K, M, T)
 dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, const float* lam_host, const float* lam_dev, int channels,
                                   const int* ns, const uint32_t* mask, int nl, bool log, const float* grad_out, const float* out,
-                                  float* grad_x, void* stream)
+                                  float* grad_x, void* stream, const int32_t* edges = nullptr)
 {
-    { dmel_status sa = check_store_aligned("dmel_backward_x_multi", {{"grad_x", grad_x}}); if (sa != DMEL_OK) return sa; }
+    const std::string who = edges ? "dmel_backward_x_band" : "dmel_backward_x_multi";
+    { dmel_status sa = check_store_aligned(who.c_str(), {{"grad_x", grad_x}}); if (sa != DMEL_OK) return sa; }
     { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2638,7 +2641,7 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
     const size_t stage_floats = any_lds ? (2 * bmt + 63) / 64 * 64 : 0;
     const size_t need = (size_t)channels * region + win_floats + stage_floats + 16;
     if (need > plan->xmw_floats) {
-        if (capturing) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi: the workspace must grow but the stream is capturing: run one call eagerly first");
+        if (capturing) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": the workspace must grow but the stream is capturing: run one call eagerly first");
         DMEL_HIP(hipStreamSynchronize(s));
         (void)hipFree(plan->xmw); plan->xmw = nullptr; plan->xmw_floats = 0;
         DMEL_HIP(hipMalloc(&plan->xmw, need * sizeof(float)));
@@ -2685,23 +2688,32 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
         xp.win_n = N / 2 + 1; xp.tiles = sh.tiles; xp.span = sh.span; xp.tile_step = sh.ts;
         if (sh.wave) {
             // one launch for every channel of this n_fft
-            dmel::XgradMultiParams mp{};
+            dmel::XgradBandParams mp{};                                       // (the multi-window layer launches its XgradMultiParams part)
             mp.p = xp;
             for (int c = 0; c < channels; ++c) {
                 mp.win2[c] = table(c, N); mp.frames[c] = frames[c]; mp.csum[c] = csum[c];
                 mp.win_denom[c] = lam_host ? std::fabs(lam_host[c]) + 1e-15f : 0.f;
                 if (mask[i] >> c & 1u) { mp.ch_list |= (unsigned)c << (4 * mp.count); ++mp.count; }
             }
-            mp.ch_grid = batch * sh.tiles; mp.ch_out = channels;
+            mp.ch_grid = batch * sh.tiles; mp.ch_out = edges ? 1 : channels;
+            for (int c = 0; edges && c <= dmel::kMaxChannels; ++c) mp.band_edges[c] = edges[std::min(c, channels)];
             if ((long long)batch * sh.tiles * mp.count > 0x7fffffffLL) return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: grid too large");
-            DMEL_HIP(dmel::launch_xgrad_wave_multi(mp, s));
+            DMEL_HIP(edges ? dmel::launch_xgrad_wave_band(mp, s) : dmel::launch_xgrad_wave_multi(mp, s));
         } else {
-            // the LDS path (cold): per channel, its rows of grad_out / out staged as (B, M, T), then the scalar frames kernel
+            // the LDS path (cold): per channel, its rows of grad_out / out staged as (B, M, T) -- a strided copy of its image, or the
+            // band-split layer's masking kernel over the one image -- then the scalar frames kernel
             for (int c = 0; c < channels; ++c) {
                 if (!(mask[i] >> c & 1u)) continue;
                 const size_t row = (size_t)M * T * sizeof(float);
-                DMEL_HIP(hipMemcpy2DAsync(stage, row, grad_out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
-                if (log) DMEL_HIP(hipMemcpy2DAsync(stage + bmt, row, out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
+                if (edges) {
+                    dmel::XgradBandStageParams sp{};
+                    sp.grad_out = grad_out; sp.out = log ? out : nullptr; sp.stage_grad = stage; sp.stage_out = stage + bmt;
+                    sp.M = M; sp.T = T; sp.e_lo = edges[c]; sp.e_hi = edges[c + 1]; sp.n = (long long)bmt;
+                    DMEL_HIP(dmel::launch_xgrad_band_stage(sp, s));
+                } else {
+                    DMEL_HIP(hipMemcpy2DAsync(stage, row, grad_out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
+                    if (log) DMEL_HIP(hipMemcpy2DAsync(stage + bmt, row, out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
+                }
                 dmel::XgradParams q = xp;
                 q.grad_out = stage; q.out = log ? stage + bmt : nullptr;
                 q.win2 = table(c, N); q.frames = frames[c]; q.csum = csum[c];
@@ -2728,12 +2740,16 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
 
 extern "C" {
 
-dmel_status dmel_backward_x_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels,
-                                  uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
+}  // extern "C"
+
+namespace {
+// dmel_backward_x_multi / dmel_backward_x_band (edges: validated, or nullptr)
+dmel_status backward_x_multi_host(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, const int32_t* edges,
+                                  uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream, const std::string& who)
 {
-    dmel_status st = check_x_multi_args(plan, x, batch, channels, flags, grad_out, out, grad_x, "dmel_backward_x_multi");
+    dmel_status st = check_x_multi_args(plan, x, batch, channels, flags, grad_out, out, grad_x, who.c_str());
     if (st != DMEL_OK) return st;
-    if (!lambd_host) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi: lambd_host is NULL");
+    if (!lambd_host) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": lambd_host is NULL");
     std::map<int, uint32_t> u;
     for (int c = 0; c < channels; ++c) {
         if (!std::isfinite(lambd_host[c])) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd of channel " + std::to_string(c) + " is not finite");
@@ -2747,37 +2763,81 @@ dmel_status dmel_backward_x_multi(dmel_plan* plan, const float* x, int32_t batch
     int ns[dmel::kMaxChannels]; uint32_t mask[dmel::kMaxChannels]; int nl = 0;
     for (const auto& kv : u) { ns[nl] = kv.first; mask[nl] = kv.second; ++nl; }
     return backward_x_multi_impl(plan, x, batch, lambd_host, nullptr, channels, ns, mask, nl, (flags & DMEL_FLAG_LOG) != 0, grad_out, out,
-                                 grad_x, stream);
+                                 grad_x, stream, edges);
+}
+
+// dmel_backward_x_multi_dev / dmel_backward_x_band_dev (edges: validated, or nullptr)
+dmel_status backward_x_multi_devlist(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, const int32_t* edges,
+                                     const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count, uint32_t flags,
+                                     const float* grad_out, const float* out, float* grad_x, void* stream, const std::string& who)
+{
+    dmel_status st = check_x_multi_args(plan, x, batch, channels, flags, grad_out, out, grad_x, who.c_str());
+    if (st != DMEL_OK) return st;
+    if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": lambd_dev is NULL");
+    if (!n_ffts || !channel_masks || count < 1 || count > 3 * dmel::kMaxChannels)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": the launch list (n_ffts, channel_masks, count) is missing or empty");
+    uint32_t seen = 0;
+    int per[dmel::kMaxChannels] = {};
+    for (int i = 0; i < count; ++i) {
+        const int n = n_ffts[i];
+        if (!multi_in_range(n) || (n & (n - 1)))
+            return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": n_ffts[" + std::to_string(i) + "] = " + std::to_string(n) +
+                        " is not a power of two in 32 ... 16384");
+        if (i > 0 && n <= n_ffts[i - 1]) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": n_ffts must be strictly ascending");
+        if (channel_masks[i] == 0 || (channels < 32 && (channel_masks[i] >> channels) != 0))
+            return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": channel_masks[" + std::to_string(i) + "] is empty or names a channel >= channels");
+        seen |= channel_masks[i];
+        for (int c = 0; c < channels; ++c)
+            if ((channel_masks[i] >> c & 1u) && ++per[c] > dmel::kXgMaxCand)
+                return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": channel " + std::to_string(c) + " is in more than 3 launches");
+    }
+    if (seen != (1u << channels) - 1u) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": a channel is in no launch");
+    if (batch == 0) return DMEL_OK;
+    return backward_x_multi_impl(plan, x, batch, nullptr, lambd_dev, channels, n_ffts, channel_masks, count, (flags & DMEL_FLAG_LOG) != 0,
+                                 grad_out, out, grad_x, stream, edges);
+}
+}  // namespace
+
+extern "C" {
+
+dmel_status dmel_backward_x_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels,
+                                  uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    return backward_x_multi_host(plan, x, batch, lambd_host, channels, nullptr, flags, grad_out, out, grad_x, stream, "dmel_backward_x_multi");
 }
 
 dmel_status dmel_backward_x_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
                                       const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count, uint32_t flags,
                                       const float* grad_out, const float* out, float* grad_x, void* stream)
 {
-    dmel_status st = check_x_multi_args(plan, x, batch, channels, flags, grad_out, out, grad_x, "dmel_backward_x_multi_dev");
+    return backward_x_multi_devlist(plan, x, batch, lambd_dev, channels, nullptr, n_ffts, channel_masks, count, flags, grad_out, out, grad_x,
+                                    stream, "dmel_backward_x_multi_dev");
+}
+
+// the band-split layer's gradient w.r.t. the waveform: dmel_backward_x_multi(_dev) over ONE (B, 1, M, T) cotangent (and saved log output),
+// channel c taking its rows [band_edges[c], band_edges[c + 1]) of it.  Pass the launch list of the dmel_forward_band_dev whose gradient this is.
+dmel_status dmel_backward_x_band(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels,
+                                 const int32_t* band_edges, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    dmel_status st = check_band_edges(band_edges, channels, "dmel_backward_x_band");
     if (st != DMEL_OK) return st;
-    if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: lambd_dev is NULL");
-    if (!n_ffts || !channel_masks || count < 1 || count > 3 * dmel::kMaxChannels)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: the launch list (n_ffts, channel_masks, count) is missing or empty");
-    uint32_t seen = 0;
-    int per[dmel::kMaxChannels] = {};
-    for (int i = 0; i < count; ++i) {
-        const int n = n_ffts[i];
-        if (!multi_in_range(n) || (n & (n - 1)))
-            return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: n_ffts[" + std::to_string(i) + "] = " + std::to_string(n) +
-                        " is not a power of two in 32 ... 16384");
-        if (i > 0 && n <= n_ffts[i - 1]) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: n_ffts must be strictly ascending");
-        if (channel_masks[i] == 0 || (channels < 32 && (channel_masks[i] >> channels) != 0))
-            return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: channel_masks[" + std::to_string(i) + "] is empty or names a channel >= channels");
-        seen |= channel_masks[i];
-        for (int c = 0; c < channels; ++c)
-            if ((channel_masks[i] >> c & 1u) && ++per[c] > dmel::kXgMaxCand)
-                return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: channel " + std::to_string(c) + " is in more than 3 launches");
-    }
-    if (seen != (1u << channels) - 1u) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_multi_dev: a channel is in no launch");
-    if (batch == 0) return DMEL_OK;
-    return backward_x_multi_impl(plan, x, batch, nullptr, lambd_dev, channels, n_ffts, channel_masks, count, (flags & DMEL_FLAG_LOG) != 0,
-                                 grad_out, out, grad_x, stream);
+    if ((st = check_band_plan(plan, band_edges, channels, "dmel_backward_x_band")) != DMEL_OK) return st;
+    int32_t edges[dmel::kMaxChannels + 1];
+    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
+    return backward_x_multi_host(plan, x, batch, lambd_host, channels, edges, flags, grad_out, out, grad_x, stream, "dmel_backward_x_band");
+}
+
+dmel_status dmel_backward_x_band_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
+                                     const int32_t* band_edges, const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count,
+                                     uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    dmel_status st = check_band_edges(band_edges, channels, "dmel_backward_x_band_dev");
+    if (st != DMEL_OK) return st;
+    if ((st = check_band_plan(plan, band_edges, channels, "dmel_backward_x_band_dev")) != DMEL_OK) return st;
+    int32_t edges[dmel::kMaxChannels + 1];
+    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
+    return backward_x_multi_devlist(plan, x, batch, lambd_dev, channels, edges, n_ffts, channel_masks, count, flags, grad_out, out, grad_x,
+                                    stream, "dmel_backward_x_band_dev");
 }
 
 dmel_status dmel_plan_last_multi_launch(dmel_plan* plan, int32_t* n_ffts, uint32_t* channel_masks, int32_t* count)

@@ -571,6 +571,23 @@ struct XgradCombineMultiParams {
 hipError_t launch_xgrad_wave_multi(const XgradMultiParams& p, hipStream_t s);
 hipError_t launch_xgrad_combine_multi(const XgradCombineMultiParams& p, int batch, hipStream_t s);
 
+// dmel_xgrad_band.hip: the band-split layer's gradient w.r.t. the waveform.  The multi-window layer's launch with ONE (B, 1, M, T) image
+// behind grad_out / out: channel c reads its rows [band_edges[c], band_edges[c + 1]) of it and takes every other row of its mel gradient
+// as +0.0 -- dmel_xgrad_wave_band_kernel<N> never loads them.  Segments, fp64 sums and the combine pass are the multi-window layer's.
+struct XgradBandParams : XgradMultiParams {
+    int band_edges[kMaxChannels + 1];   // 0 = e_0 < e_1 < ... < e_K = M (validated by the host)
+};
+hipError_t launch_xgrad_wave_band(const XgradBandParams& p, hipStream_t s);
+// LDS path: dmel_xgrad_band_stage_kernel writes one channel's (B, M, T) mel gradient for the scalar frames kernel: rows [e_lo, e_hi) of
+// grad_out, +0.0 elsewhere; with `out` (the log output) the same rows of it into stage_out, 0.f elsewhere (exp(-0) = 1: the product stays +0.0)
+struct XgradBandStageParams {
+    const float* grad_out; const float* out;      // (B, M, T); out or nullptr
+    float* stage_grad; float* stage_out;
+    int M, T, e_lo, e_hi;
+    long long n;                                  // B M T
+};
+hipError_t launch_xgrad_band_stage(const XgradBandStageParams& p, hipStream_t s);
+
 // gradient w.r.t. the filterbank matrix of models.py:53 (adjoint of  mel = spec^T @ fb):
 //   grad_fb[f][m] = sum_{b,t} spec[b][f][t] * gm[b][m][t],   gm = grad_out            (linear output)
 //                                                            gm = grad_out * exp(-out) (log output: d log(s+eps) = ds / (s+eps))
@@ -675,11 +692,12 @@ hipError_t forward_len_prepare_attributes();
 hipError_t forward_band_prepare_attributes();
 hipError_t xgrad_prepare_attributes();
 hipError_t xgrad_len_prepare_attributes();
+hipError_t xgrad_band_prepare_attributes();
 hipError_t big_prepare_attributes();
 inline hipError_t prepare_attributes()
 {
     for (auto unit : {forward_prepare_attributes, forward_len_prepare_attributes, forward_band_prepare_attributes, xgrad_prepare_attributes,
-                      xgrad_len_prepare_attributes, big_prepare_attributes})
+                      xgrad_len_prepare_attributes, xgrad_band_prepare_attributes, big_prepare_attributes})
         if (const hipError_t e = unit(); e != hipSuccess) return e;
     return hipSuccess;
 }

@@ -3,7 +3,13 @@
 // the relabelled workgroup index, as in dmel_fwd_multi_kernel).  dmel_xgrad_len.hip includes it a third time with DMEL_XG_LEN = 1:
 // dmel_xgrad_wave_len_kernel, the scalar layer over clips of per-clip lengths (XgradLenParams).  The XG_* names below expand, for the two
 // kernels of dmel_xgrad.hip, to exactly the tokens they were written with, so that their code does not change.
-#if DMEL_XG_MULTI
+// dmel_xgrad_band.hip includes it a fourth time with DMEL_XG_MULTI = 1 and DMEL_XG_BAND = 1: dmel_xgrad_wave_band_kernel, the multi kernel's
+// channel slot with ONE image behind grad_out / out (XgradBandParams): a channel stages only its own rows of it, every other row of gm is +0.0.
+#if DMEL_XG_BAND
+#define XG_KERNEL dmel_xgrad_wave_band_kernel
+#define XG_PARAMS XgradBandParams mp
+#define XG_BO b
+#elif DMEL_XG_MULTI
 #define XG_KERNEL dmel_xgrad_wave_multi_kernel
 #define XG_PARAMS XgradMultiParams mp
 #define XG_BO bo
@@ -28,6 +34,15 @@
 #define XG_PSUM_L p.L
 #define XG_INV_L p.inv_L
 #define XG_TC T
+#endif
+// the indices of gm (M, FPT) that are staged from memory end here: all of it, or the channel's rows [e_lo, e_hi) (dmel_xgrad_wave_band_kernel)
+// (and the element a masked-off request reads instead: one of the channel's own)
+#if DMEL_XG_BAND
+#define XG_GM_END g_end
+#define XG_GM_SAFE (unsigned)(e_lo * T)
+#else
+#define XG_GM_END total
+#define XG_GM_SAFE 0u
 #endif
 template <int N>
 __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KERNEL(XG_PARAMS)
@@ -87,7 +102,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
     const float inv_Lc = 1.0f / (float)Lc;
     if (!cl.ok || tile * FPT >= Tc) return;
 #endif
-#if DMEL_XG_MULTI
+#if DMEL_XG_MULTI && !DMEL_XG_BAND
     const int bo = b * mp.ch_out + ch;                            // the clip's row of grad_out / out: (B, K, M, T)
 #endif
     const int t0 = tile * FPT;
@@ -122,12 +137,19 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
     // (requests only: nothing here touches what was loaded -- a select on a loaded value, or a branch around a load, makes the
     // compiler wait for it on the spot, and vector loads return in order: that wait would also sit out the 2 R sample loads above)
     const float* ysrc = yb ? yb : gb;                                             // always a valid address; ignored without the log
+#if DMEL_XG_BAND
+    // the channel's rows of the image (uniform: scalar registers, as dmel_fwd_band_kernel): indices g_lo ... g_end - 1 of gm come from
+    // memory, in as many round trips as the group's share of the rows needs; the other rows are never requested -- in log mode they hold
+    // other channels' output, which must not reach exp(-y) -- and are written as +0.0 below
+    const int e_lo = __builtin_amdgcn_readfirstlane(mp.band_edges[ch]), e_hi = __builtin_amdgcn_readfirstlane(mp.band_edges[ch + 1]);
+    const int g_lo = e_lo * FPT, g_end = e_hi * FPT;
+#endif
     auto gm_fetch = [&](int base, float (&v)[4], float (&y)[4]) {
         static_for<0, 4>([&](auto uu) {
             constexpr int u = decltype(uu)::value;
             const int idx = base + u * THREADS, m = idx / FPT, t = t0 + idx % FPT;
-            const bool ok = idx < total && t < XG_TC;
-            const unsigned o = ok ? (unsigned)(m * T + t) : 0u;
+            const bool ok = idx < XG_GM_END && t < XG_TC;
+            const unsigned o = ok ? (unsigned)(m * T + t) : XG_GM_SAFE;
             v[u] = gb[o];
             y[u] = ysrc[o];
         });
@@ -136,14 +158,18 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
         static_for<0, 4>([&](auto uu) {
             constexpr int u = decltype(uu)::value;
             const int idx = base + u * THREADS, t = t0 + idx % FPT;
-            if (idx < total) {
+            if (idx < XG_GM_END) {
                 const float val = yb ? v[u] * expf(-y[u]) : v[u];
                 gm[idx] = t < XG_TC ? val : 0.f;
             }
         });
     };
     float gv[4], gy[4];
+#if DMEL_XG_BAND
+    gm_fetch(g_lo + tid, gv, gy);
+#else
     if (total > 0) gm_fetch(tid, gv, gy);
+#endif
     constexpr int WPT = (N + THREADS - 1) / THREADS;
     float mean = 0.f;
     if (p.own_prep) {
@@ -199,11 +225,22 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
         mean = clip_mean_psum(p.psum, p.nchunks, b, XG_PSUM_L);
         static_for<0, WPT>([&](auto ww) { constexpr int wi = decltype(ww)::value; const int n = tid + THREADS * wi; if (n < WN) win[n] = wv[wi]; });
     }
+#if DMEL_XG_BAND
+    {
+        gm_store(g_lo + tid, gv, gy);
+        for (int base = g_lo + tid + 4 * THREADS; base < g_end; base += 4 * THREADS) { gm_fetch(base, gv, gy); gm_store(base, gv, gy); }
+        // the rows of the other channels, and row M (zeros, read as "the next row" of row M - 1): +0.0, what the scalar kernel forms
+        // from a cotangent whose rows outside [e_lo, e_hi) are +0.0
+        for (int i = tid; i < g_lo; i += THREADS) gm[i] = 0.f;
+        for (int i = g_end + tid; i < total + FPT; i += THREADS) gm[i] = 0.f;
+    }
+#else
     if (total > 0) {
         gm_store(tid, gv, gy);
         for (int base = tid + 4 * THREADS; base < total; base += 4 * THREADS) { gm_fetch(base, gv, gy); gm_store(base, gv, gy); }
         if (tid < FPT) gm[total + tid] = 0.f;                                     // row M: zeros, read as "the next row" of row M - 1
     }
+#endif
     // the radix-C twiddles through LDS (R x C entries: a wave-wide global load of them would still move 512 B per p1)
     float2* tw2l = reinterpret_cast<float2*>(smem_raw + p.tw2_off);
     if (C > 1 && tid < R * C) tw2l[tid] = p.tw2[tid];
@@ -410,3 +447,5 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
 #undef XG_PSUM_L
 #undef XG_INV_L
 #undef XG_TC
+#undef XG_GM_END
+#undef XG_GM_SAFE

@@ -859,44 +859,68 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
 
 class _BandFunction(torch.autograd.Function):
     """forward: dmel_forward_band(_dev) -- one launch per distinct n_fft for all K channels, every channel writing its own rows of ONE
-    (B, 1, M, T) image and of its tangent; backward: dmel_backward_band (the K row-group dot products in one launch)."""
+    (B, 1, M, T) image and of its tangent; backward: dmel_backward_band (the K row-group dot products in one launch) and, for a waveform
+    that requires grad (waveform_grad=True), dmel_backward_x_band(_dev): every channel's x-gradient from its own rows of the ONE cotangent,
+    summed in ascending channel order (what _MultiFunction saves for it, this one saves too)."""
 
     @staticmethod
     def forward(ctx, x, lambd, plan, lam_host, edges, log, eps, out_dtype, want_tangent):
         B, K = x.shape[0], lambd.shape[0]
-        out, tangent, scratch, _ = _alloc(x, (B, 1, plan.n_mels, plan.n_time), out_dtype, want_tangent, False, plan.scratch_bytes_multi(B, K))
-        bf16 = out_dtype == torch.bfloat16
+        want_x = ctx.needs_input_grad[0]
+        out, tangent, scratch, round_later = _alloc(x, (B, 1, plan.n_mels, plan.n_time), out_dtype, want_tangent, log and want_x,
+                                                    plan.scratch_bytes_multi(B, K))
+        bf16 = out.dtype == torch.bfloat16
+        lam = None
         with _on_device(x.device):
             if lam_host is not None:
                 plan.forward_band(x.data_ptr(), B, lam_host, edges, out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
                                   scratch.data_ptr(), out_bf16=bf16)
             else:
-                plan.forward_band_dev(x.data_ptr(), B, _lambd_f32(lambd).data_ptr(), edges, out.data_ptr(), _ptr(tangent), log, eps,
+                lam = _lambd_f32(lambd)
+                plan.forward_band_dev(x.data_ptr(), B, lam.data_ptr(), edges, out.data_ptr(), _ptr(tangent), log, eps,
                                       _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
         ctx.plan, ctx.lambd_shape, ctx.lambd_dtype, ctx.edges, ctx.want_tangent = plan, lambd.shape, lambd.dtype, edges, want_tangent
-        if want_tangent:
-            ctx.save_for_backward(tangent, scratch)
-        return out
+        ctx.want_x, ctx.log, ctx.lam_host = want_x, bool(log), lam_host
+        # what this forward launched for (host bookkeeping of the plan, no device read): a later forward cannot change what the backward covers
+        ctx.launches = plan.last_multi_launch() if (want_x and lam_host is None) else None
+        saved = [tangent, scratch] if want_tangent else []
+        if want_x:
+            saved += [x] + ([lam] if lam is not None else []) + ([out] if log else [])
+        ctx.save_for_backward(*saved)
+        return out.to(torch.bfloat16) if round_later else out
 
     @staticmethod
     def backward(ctx, grad_out):
+        saved = list(ctx.saved_tensors)
         g, bf16 = _cotangent(grad_out)
-        dl = None
-        if ctx.want_tangent:
-            tangent, scratch = ctx.saved_tensors
-            with _on_device(g.device):
+        dl = gx = None
+        with _on_device(g.device):
+            if ctx.want_tangent:
+                tangent, scratch = saved.pop(0), saved.pop(0)
                 dl = torch.empty((len(ctx.edges) - 1,), dtype=torch.float32, device=g.device)
                 ctx.plan.backward_band(g.data_ptr(), tangent.data_ptr(), g.shape[0], ctx.edges, dl.data_ptr(), _stream_ptr(g.device),
                                        scratch.data_ptr(), grad_bf16=bf16)
                 dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
-        return None, dl, None, None, None, None, None, None, None
+            if ctx.want_x:
+                x = saved.pop(0)
+                lam = saved.pop(0) if ctx.lam_host is None else None
+                out = saved.pop(0) if ctx.log else None
+                g32 = g.to(torch.float32)
+                gx = torch.empty_like(x)
+                if lam is None:
+                    ctx.plan.backward_x_band(x.data_ptr(), x.shape[0], ctx.lam_host, ctx.edges, g32.data_ptr(), _ptr(out), gx.data_ptr(), ctx.log,
+                                             _stream_ptr(g.device))
+                else:
+                    ctx.plan.backward_x_band_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.edges, ctx.launches, g32.data_ptr(), _ptr(out),
+                                                 gx.data_ptr(), ctx.log, _stream_ptr(g.device))
+        return gx, dl, None, None, None, None, None, None, None
 
 
 class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
     """A trainable window width per GROUP OF MEL BANDS inside one image: the scalar layer's output shape, K resolutions.
 
         BandSplitMelSpectrogram(init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
-                                band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False)
+                                band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False)
         forward(x: (B, n_points)) -> (B, 1, n_mels, n_points // hop_length + 1)
 
     ``band_edges`` are K + 1 integers ``0 = e_0 < e_1 < ... < e_K = n_mels`` (default ``e_k = (k * n_mels) // K``).  Rows
@@ -916,13 +940,20 @@ class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
     ``lambd_sync=False`` keeps the K values on the device with one host picture per channel exactly as the multi-window layer
     (``resync()``, ``lambd_status(channel)``, ``set_tracking``); a channel no launch covered makes ITS rows NaN, leaves the other
     groups' rows untouched, and the next forward raises naming the channel.  The sync-free step can be captured with ``torch.cuda.graph``.
-    Out of scope, not forgotten (each raises and says what to use instead): a waveform gradient (``x.requires_grad``), per-clip
-    ``lengths``, ``SlotInput``, ``GraphedStep`` and ``LambdAdam(fused_into_backward=...)``; band edges and the filterbank are not trainable."""
+
+    ``waveform_grad=True`` accepts an ``x`` that requires grad.  With ``G_k`` the cotangent whose rows outside ``e_k ... e_{k+1} - 1`` are
+    ``+0.0``, ``x.grad`` is ``0 + gx_0 + ... + gx_{K-1}`` in ascending channel order, ``gx_k`` what
+    ``MelSpectrogramLayer(lambd[k], ..., optimized=True)`` gives for ``G_k``, bit for bit -- ``MultiWindowMelSpectrogram(waveform_grad=True)``'s
+    ``x.grad`` for the stacked ``G_k`` without the ``(B, K, M, T)`` tensors: every channel loads only its own rows of the one cotangent.
+    The forward output and ``lambd.grad`` do not change; the forward then keeps ``x`` and the fp32 output alive until the backward.  A
+    channel no launch covered makes ``x.grad`` NaN.  Without the flag ``x.requires_grad`` raises.
+    Out of scope, not forgotten (each raises and says what to use instead): per-clip ``lengths``, ``SlotInput``, ``GraphedStep`` and
+    ``LambdAdam(fused_into_backward=...)``; band edges and the filterbank are not trainable."""
 
     def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
-                 band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False):
+                 band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False):
         super().__init__(init_lambd, n_mels, n_points, sample_rate, f_min, f_max, hop_length, normalize_window, log=log, eps=eps,
-                         out_dtype=out_dtype, lambd_sync=lambd_sync)
+                         out_dtype=out_dtype, lambd_sync=lambd_sync, waveform_grad=waveform_grad)
         K = self.lambd.shape[0]
         if band_edges is None:
             if K > n_mels:
@@ -940,15 +971,17 @@ class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
         self.band_edges = tuple(edges)
 
     def forward(self, x, lengths=None):
+        no_x_grad = None if self.waveform_grad else ("BandSplitMelSpectrogram has no waveform gradient: pass x.detach() (MelSpectrogramLayer and "
+                                                     "MultiWindowMelSpectrogram(waveform_grad=True) have one)")
         xf, lam_host, want = self._prepare("BandSplitMelSpectrogram", x, lengths,
                                            "BandSplitMelSpectrogram does not take a SlotInput: pass the batch tensor (MelSpectrogramLayer takes slots)",
-                                           "BandSplitMelSpectrogram has no waveform gradient: pass x.detach() (MelSpectrogramLayer and "
-                                           "MultiWindowMelSpectrogram(waveform_grad=True) have one)")
+                                           no_x_grad)
         return _BandFunction.apply(xf, self.lambd, self._plan_for(x.device), lam_host, self.band_edges, self.log, self.eps, self.out_dtype, want)
 
     def extra_repr(self):
         return (f"band_edges={list(self.band_edges)}, n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
-                f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}")
+                f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}, "
+                f"waveform_grad={self.waveform_grad}")
 
 
 class _DspecFunction(torch.autograd.Function):

@@ -505,8 +505,8 @@ dmel_status dmel_backward_x_multi(dmel_plan* plan, const float* x, int32_t batch
 dmel_status dmel_backward_x_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
                                       const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count, uint32_t flags,
                                       const float* grad_out, const float* out, float* grad_x, void* stream);
-/* What the most recent dmel_forward_multi(_dev) on this plan issued (host bookkeeping, captured calls included): count entries in
- * ascending n_fft with their channel masks; arrays of 24 (3 x 8) entries.  count = 0 before the first such call. */
+/* What the most recent dmel_forward_multi(_dev) or dmel_forward_band(_dev) on this plan issued (host bookkeeping, captured calls included):
+ * count entries in ascending n_fft with their channel masks; arrays of 24 (3 x 8) entries.  count = 0 before the first such call. */
 dmel_status dmel_plan_last_multi_launch(dmel_plan* plan, int32_t* n_ffts, uint32_t* channel_masks, int32_t* count);
 
 /* ---- the band-split layer: a trainable window width per GROUP OF MEL BANDS inside one image (dmel_amd.BandSplitMelSpectrogram) ----------
@@ -526,6 +526,19 @@ dmel_status dmel_forward_band_dev(dmel_plan* plan, const float* x, int32_t batch
  * gradients widened exactly).  Not with an attached mailbox or fused Adam. */
 dmel_status dmel_backward_band(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int32_t batch, int32_t channels,
                                const int32_t* band_edges, int32_t accumulate, float* dlambd, void* scratch, void* stream);
+/* Gradient w.r.t. the waveform of the band-split layer.  grad_out and out are ONE (batch, 1, n_mels, n_time) fp32 image; with G_k = grad_out
+ * whose rows outside e_k ... e_{k+1} - 1 are +0.0, grad_x (batch, n_points, 16-byte aligned) = 0 + gx_0 + ... + gx_{K-1} in ascending
+ * channel order, gx_k what dmel_backward_x(_dev) gives for lambd[k] and G_k, bit for bit -- dmel_backward_x_multi(_dev) for the
+ * (batch, K, M, T) cotangent whose channel k is G_k, without that tensor: a channel loads only its own rows (dmel_xgrad_wave_band_kernel; on
+ * the LDS path, n_fft 4096 ... 16384, dmel_xgrad_band_stage_kernel writes the masked rows out for the scalar frames kernel).  Rows outside a
+ * channel's range are never read: in log mode they hold other channels' output.  Arguments, launch list (dmel_plan_last_multi_launch right
+ * after the dmel_forward_band_dev whose gradient this is), NaN for a channel no launch matched, plan-owned workspace and the capture rule are
+ * dmel_backward_x_multi(_dev)'s; band_edges as dmel_forward_band's.  NULL / invalid arguments: DMEL_ERR_INVALID_ARGUMENT before any device work. */
+dmel_status dmel_backward_x_band(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels,
+                                 const int32_t* band_edges, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream);
+dmel_status dmel_backward_x_band_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
+                                     const int32_t* band_edges, const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count,
+                                     uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream);
 
 /* Introspection for tests / benchmarks */
 typedef struct dmel_plan_info {
