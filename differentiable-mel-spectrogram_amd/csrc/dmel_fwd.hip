@@ -39,8 +39,9 @@ __global__ void __launch_bounds__(kThreads) dmel_prep_kernel(PrepParams p)
         // window block: time_frequency.py:21-30 in fp32; second entry = w d^2 2^(-2e), the tangent window up to the
         // factor lam_tangent_scale() that the forward kernels apply in their epilogue (fp64 here: d^2 needs 30 bits)
         if (blockIdx.x != 0) return;
-        const LamState ls = lam_prologue(p.lam, p.N, false);
+        LamState ls = lam_prologue(p.lam, p.N, false);
         if (ls.action != kLamRun) return;
+        if (p.N >= kMinFastNfft && p.N <= kMaxFastNfft && (p.N & (p.N - 1)) == 0 && !p.normalize) ls = lam_clip_scale(ls, p.L);      // the fused kernel's table (n_fft 8192 / 16384): as its epilogue
         const float denom = ls.denom;
         const double s2 = (double)ls.s2;
         double s_ww = 0.0, s_wd = 0.0;

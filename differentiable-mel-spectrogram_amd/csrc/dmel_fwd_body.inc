@@ -391,7 +391,11 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
         if (p.remove_dc && p.psum != nullptr) ps_early = (lane < p.nchunks) ? p.psum[(size_t)b * p.nchunks + lane] : 0.f;
         STAMP(1);   // loads issued
         // lambd (device scalar or by value) and the check that this launch is the n_fft the device value asks for
-        const LamState ls = lam_prologue(FWD_LAM, N, FWD_LEADER && tid == 0, lam_raw);
+        // (lam_clip_scale: a clip no longer than |lambd| -- dmel_kernels.h; the table of n_fft 8192 / 16384 is dmel_prep_kernel's, scaled by the row length)
+        const LamState ls0 = lam_prologue(FWD_LAM, N, FWD_LEADER && tid == 0, lam_raw);
+        LamState ls1 = ls0;
+        if constexpr (TRAINLIKE || MODE == kSpecTrain) { if (!p.normalize) ls1 = lam_clip_scale(ls0, g.WIN_LDS ? FWD_LC : p.L); }      // (the modes that write a tangent)
+        const LamState ls = ls1;
         if (ls.action != kLamRun) {
             if (ls.action == kLamPoison) {
                 // no launch of this forward matched the device lambd: NaN instead of stale memory (the host raises too)

@@ -218,6 +218,26 @@ __device__ __forceinline__ LamState lam_prologue(const LamArgs& la, int n_launch
     return lam_prologue(la, n_launch, leader, lam_load(la));
 }
 
+// A clip of L samples puts no sample further than L from the centre of any of its frames.  With L <= 2^(e-1) (a clip no longer than |lambd|)
+// the scaled tangent window w d^2 2^(-2e) is (L / 2^e)^2 below w on EVERY sample of EVERY frame, and the frame's transform -- one complex
+// FFT of x~ (w + i w'), taken apart afterwards -- loses the tangent spectrum in the rounding of the other: 2^-24 (2^e / L)^2 of its own size
+// (2 samples, lambd 128: 5e-3 of every tangent element's scale; tests/test_hip_tangent.py: tiny_L2_n1024).  For such a clip the exponent is
+// lowered to ceil(log2 L): w d^2 2^(-2e) <= w still, the same power of two goes into the table and into lam_tangent_scale, and a longer
+// clip keeps its bits.  Not with the normalised window: its derivative carries -w sum(w w') / sum(w w)^(3/2), which does not vanish at the
+// centre -- the tangent spectrum is then as large as the other at the usual scale (measured: 1.7e-5 at 7 samples, lambd 150), and a larger
+// scale would bury the spectrum itself.  `L` must be what every consumer of the window table uses: the clip's own length where the workgroup builds its
+// table (n_fft <= 4096), the row length where dmel_prep_kernel builds one for all (n_fft 8192 / 16384).
+__device__ __forceinline__ LamState lam_clip_scale(LamState st, int L)
+{
+    const int l = __builtin_amdgcn_readfirstlane(L);
+    const int el = l > 1 ? 32 - __builtin_clz((unsigned)(l - 1)) : 0;      // ceil(log2 L)
+    if (2 * el < st.e2) {
+        st.e2 = 2 * el;
+        st.s2 = __builtin_bit_cast(float, (127 - 2 * el) << 23);
+    }
+    return st;
+}
+
 // sign(lambd) 2^(2e) / (|lambd| + 1e-15)^3: what turns the contraction of the scaled tangent window into d / d lambd
 // (fp64, rounded once; lambd == 0 gives 0, an overflow gives 0: w' vanishes wherever w does not)
 __device__ __forceinline__ float lam_tangent_scale(const LamState& st)

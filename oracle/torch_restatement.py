@@ -9,6 +9,10 @@ per-sample Python loop of models.py:37-54.  It exists for two reasons:
     BASELINE.md section 2 (the reference's own loop spends 70 % of its time in a CopySlices artefact).
 Only tests/ and bench.py's cpu_baseline leg may import this module.
 
+tangent_fp64 / tangent_fp32 evaluate the forward-mode tangent d out / d lambd element by element by a third route (the window's
+derivative from torch.autograd.functional.jacobian, then a second stft with it), together with the cancellation-free magnitude of
+every tangent element: what tests/tangent_cases.py measures the oracle's and the kernels' tangents against.
+
 Reference lines followed: time_frequency.py:21-30 (window), :39,:60-65 (n_fft), :48 (stft),
 :53 (power); models.py:38 (DC removal, abs), :42-53 (filterbank, contraction), :73 (log).
 """
@@ -63,3 +67,68 @@ def step(x: torch.Tensor, g: torch.Tensor, lambd_value: float, hop: int, n_mels:
     out = forward(x, lam, hop, n_mels, sample_rate, log=log, fb=fb)
     (dl,) = torch.autograd.grad((out * g).sum(), lam)
     return out.detach(), float(dl)
+
+
+def _window_of(lam: torch.Tensor, n: int, normalize_window: bool) -> torch.Tensor:
+    """the Gaussian window of n points as a function of lambd, in lambd's dtype"""
+    m = torch.arange(0, n, dtype=lam.dtype)
+    window = torch.exp(-0.5 * torch.pow((m - n / 2) / (torch.abs(lam) + 1e-15), 2))
+    if normalize_window:
+        window = window / torch.sqrt(torch.sum(torch.pow(window, 2)))
+    return window
+
+
+def _tangent(dtype, x, lambd, hop, n_mels, sample_rate, f_min, f_max, normalize_window, log, eps, optimized, mean, fb, spectrogram):
+    import numpy as np
+    x32 = np.ascontiguousarray(x, dtype=np.float32)
+    B, L = x32.shape
+    lam32 = np.float32(lambd)
+    lam = torch.tensor(float(lam32), dtype=dtype)
+    n_win = n_fft_of(torch.tensor(float(lam32))) if optimized else L
+    n = n_win if optimized else 2 * L
+    w = _window_of(lam, n_win, normalize_window)
+    dw = torch.autograd.functional.jacobian(lambda l: _window_of(l, n_win, normalize_window), lam, vectorize=True,
+                                            strategy="forward-mode").reshape(n_win)
+    if mean is None:
+        mean = np.float32(x32.astype(np.float64).mean(axis=1))              # the correctly rounded fp32 mean (models.py:38)
+    mean = np.asarray(mean, dtype=np.float32).reshape(B, 1)
+    xc = torch.tensor(x32).to(dtype) - torch.tensor(mean).to(dtype)
+    kw = dict(n_fft=n, hop_length=hop, win_length=n_win, return_complex=True, pad_mode="constant")
+    S = torch.stft(xc, window=w, **kw)                                        # (B, F, T)
+    D = torch.stft(xc, window=dw, **kw)
+    p = S.real * S.real + S.imag * S.imag
+    dp = 2.0 * (S.real * D.real + S.imag * D.imag)
+    sc = 2.0 * torch.abs(S) * torch.abs(D)
+    if not spectrogram:
+        if fb is None:
+            from oracle import dmel_oracle as O
+            fb = O.mel_fbanks(n // 2 + 1, f_min, float(sample_rate // 2) if f_max is None else f_max, n_mels, sample_rate)
+        fbt = torch.tensor(np.asarray(fb, dtype=np.float32)).to(dtype)      # (F, M)
+        p = torch.einsum("fm,bft->bmt", fbt, p)
+        dp = torch.einsum("fm,bft->bmt", fbt, dp)
+        sc = torch.einsum("fm,bft->bmt", fbt.abs(), sc)
+    if log:
+        dp, sc = dp / (p + eps), sc / torch.abs(p + eps)
+        p = torch.log(p + eps)
+    return tuple(v.unsqueeze(1).to(torch.float64).numpy() for v in (p, dp, sc))
+
+
+def tangent_fp64(x, lambd, hop, n_mels, sample_rate, f_min=0.0, f_max=None, normalize_window=False, log=False, eps=1e-10,
+                 optimized=True, mean=None, fb=None, spectrogram=False):
+    """(out, tangent, scale), each (B, 1, n_mels, L//hop+1) fp64 -- with ``spectrogram`` (B, 1, n_fft/2+1, L//hop+1), no bank: the
+    SpectrogramLayer.  Everything in torch.float64 from the fp32 clip ``x`` (B, L) and ``lambd`` rounded to fp32:
+      window(lambd) of n_fft points (``optimized``) or of L points inside n_fft = 2L, and dw = d window / d lambd by autograd's jacobian
+      of that very function (so the normalised window and the sign of a negative lambd come with it);
+      S = stft(x - mean, window), D = stft(x - mean, dw);  p = |S|^2,  dp = 2 Re(conj(S) D),  sc = 2 |S| |D|;
+      the three contracted with the bank (``fb`` (F, M), else the HTK bank; sc with |fb|), and for ``log`` tangent and scale over mel + eps.
+    ``scale`` bounds |tangent| element by element and is free of cancellation: the magnitude an fp32 evaluation of that element can be
+    asked to be accurate against.  ``mean``: fp32 clip means given instead of computed, as dmel_oracle.forward(mean=...) takes them."""
+    return _tangent(torch.float64, x, lambd, hop, n_mels, sample_rate, f_min, f_max, normalize_window, log, eps, optimized, mean, fb,
+                    spectrogram)
+
+
+def tangent_fp32(x, lambd, hop, n_mels, sample_rate, f_min=0.0, f_max=None, normalize_window=False, log=False, eps=1e-10,
+                 optimized=True, mean=None, fb=None, spectrogram=False):
+    """tangent_fp64's construction in the reference's own arithmetic: fp32 window, fp32 stft, fp32 contraction (returned as fp64 arrays)"""
+    return _tangent(torch.float32, x, lambd, hop, n_mels, sample_rate, f_min, f_max, normalize_window, log, eps, optimized, mean, fb,
+                    spectrogram)

@@ -10,6 +10,8 @@ import torch
 import cases as C
 from dmel_amd import synth
 from oracle import dmel_oracle as O
+from oracle import torch_restatement as R
+from tangent_cases import assert_tangent
 from test_hip_parity import TOL, _dlam_tol, _log_err, _rel_err, assert_parity, explain_by_clip_mean, parity_stats, record_parity
 from test_hip_random_shapes import _assert_dlam
 
@@ -272,13 +274,11 @@ def test_sweep_clip_by_clip_against_the_oracle(c):
         t_real = np.concatenate([refs[b][1].reshape(-1) for b in range(B)])
         exp_d = sum(O.backward(g_np[b:b + 1, :, :, :tc[b]], refs[b][1]) for b in range(B))
         d32 = sum(_reference_fp32_dlam(c, x_np[b:b + 1, :lens[b]], g_np[b:b + 1, :, :, :tc[b]], log) for b in range(B))
-        # d lambd: _assert_dlam (the plain 1e-4 wherever the sum does not cancel) on the linear output; out of reach of fp32 arithmetic are
-        #  * the log output's, where t / (mel + eps) amplifies the rounding of small bands: the reference's own fp32 result misses that bar
-        #    (measured: l2, lengths 184 / 182 / 516, 1.3e-4 off the oracle, by an amount that varies with the CPU that runs it);
-        #  * a clip of 2 ... 15 samples: the fused kernel's tangent of such a clip is 1e-3 (linear) to 7e-2 (log) off the oracle's relative to
-        #    its scale, on the default path too (measured: n_points = 2 gives the lengths path's d lambd bit for bit; 17 samples: 8e-6)
-        # -- there the bar of _dlam_tol, widened by twice the reference's own distance from the oracle
-        strict = not log and not any(1 < lb < 16 for lb in lens)
+        # d lambd: _assert_dlam (the plain 1e-4 wherever the sum does not cancel) on the linear output; out of reach of fp32 arithmetic is the
+        # log output's, where t / (mel + eps) amplifies the rounding of small bands: the reference's own fp32 result misses that bar
+        # (measured: l2, lengths 184 / 182 / 516, 1.3e-4 off the oracle, by an amount that varies with the CPU that runs it) -- there the bar
+        # of _dlam_tol, widened by twice the reference's own distance from the oracle
+        strict = not log
         for train in (True, False):
             lay = _mk(c, W, log=log)
             y, d = _run(lay, x, lengths, g if train else None)
@@ -347,6 +347,9 @@ def test_c_abi_tangent_at_partial_lengths(name, W, lens):
                 assert_parity(f"lengths_capi/{name}/b{b}/mel", o[b:b + 1, :, :, :tc[b]], o_ref, allow_floor=False)
             tscale = np.abs(t_ref).max() + 1e-30
             assert float(np.abs(t[b:b + 1, :, :, :tc[b]] - t_ref).max()) / tscale <= TOL, (name, b, log)
+            # ... and every element against its own cancellation-free magnitude (tests/tangent_cases.py)
+            _, _, sc = R.tangent_fp64(x_np[b:b + 1, :lb], c["lambd"], hop, M, c["sr"], c["f_min"], c["f_max"], c["normalize_window"], log=log)
+            assert_tangent(f"tangent/lengths_capi/{name}/b{b}_L{lb}/{'log' if log else 'lin'}", t[b:b + 1, :, :, :tc[b]], t_ref, sc, shape=t_ref.shape)
             assert (t[b, :, :, tc[b]:] == 0.0).all(), (name, b, log)
         # an invalid length: its own clip's output and tangent are NaN, the other clips keep their bits
         bad = lengths.clone()

@@ -257,6 +257,16 @@ def test_matches_oracle_elementwise(name):
         # tangent: signed sums cancel, so measure against the frame's own scale
         tscale = np.abs(t_ref).max() + 1e-30
         assert float(np.abs(t - t_ref).max()) / tscale <= TOL
+        # ... and every element against its own cancellation-free magnitude (tests/tangent_cases.py): the measure above accepts anything
+        # for the elements below 1e-4 of the largest.  Not g6_tone_dc (tones and an offset, bins 120 dB down between the tones): there the
+        # references themselves leave less room than that bar needs -- oracle 2.5e-5, the reference's fp32 arithmetic 4.3e-5 off the fp64
+        # evaluation, TOL / 4 asked -- and tests/test_hip_tangent.py holds a loud tone without an offset to it (loud_tone_n1024)
+        if name != "g6_tone_dc":
+            from oracle import torch_restatement as R
+            from tangent_cases import assert_tangent
+            _, _, sc = R.tangent_fp64(x_np, case["lambd"], case["hop"], case["n_mels"], case["sr"], case["f_min"], case["f_max"],
+                                      case["normalize_window"], log=log)
+            assert_tangent(f"tangent/elementwise/{name}/{'log' if log else 'lin'}", t, t_ref, sc, shape=t.shape)
 
 
 @pytest.mark.parametrize("name", ["g1_c1", "g2_c2", "g6_n256_ragged", "g5_n128", "g6_n32", "g6_n2048_short", "g3_c3", "g5_n4096"])
@@ -1443,9 +1453,14 @@ def test_wave_local_contraction_with_empty_quads(n_mels, lam):
     Round 6 issues every load of the B ring (a group past the end of its phase re-reads the last one): with a phase of no groups at all the index
     must still stay inside the table.  Every element and the tangent against the oracle; zero-width bands are exact zeros (log: log(eps))."""
     from dmel_amd import capi
+    from oracle import torch_restatement as R
+    from tangent_cases import assert_tangent
     L, hop, sr, B = 6000, 128, 16000, 3
+    # (the seeds: clips on which the oracle and the reference's fp32 arithmetic are within TOL / 4 of the fp64 evaluation in the element-wise
+    # tangent metric -- bands of one bin have near-nulls that no fp32 transform resolves, tests/tangent_cases.py: "single bins"; seed 91, used
+    # until the tangent was compared element by element, has one at each of the three sizes)
     case = dict(name=f"emptyq_m{n_mels}", B=B, L=L, sr=sr, lambd=lam, hop=hop, n_mels=n_mels, kind="noise", normalize_window=False, dtype="float32",
-                seed=91, f_min=0.0, f_max=None, optimized=True)
+                seed={512: 391, 400: 391, 509: 591}[n_mels], f_min=0.0, f_max=None, optimized=True)
     x_np = C.make_input(case)
     x = torch.from_numpy(x_np).to("cuda:0")
     plan = capi.Plan(L, hop, n_mels, sr)
@@ -1464,4 +1479,6 @@ def test_wave_local_contraction_with_empty_quads(n_mels, lam):
             assert _rel_err(o, o_ref) <= TOL
             assert (o[o_ref == 0] == 0).all() and (o_ref == 0).any(), "the case must hold empty bands, and they must be exact zeros"
         assert float(np.abs(t - t_ref).max()) / (np.abs(t_ref).max() + 1e-30) <= TOL
+        _, _, sc = R.tangent_fp64(x_np, lam, hop, n_mels, sr, log=log)
+        assert_tangent(f"tangent/{case['name']}/{'log' if log else 'lin'}", t, t_ref, sc, shape=t.shape)
     assert info["n_fft"] in (1024, 2048)
