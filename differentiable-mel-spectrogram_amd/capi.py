@@ -139,6 +139,8 @@ _SIGNATURES = {
     "dmel_scratch_bytes_multi": (C.c_size_t, [vp, i32, i32]),
     "dmel_forward_multi": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_multi_dev": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_multi_lengths": (status, [vp, vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_multi_dev_lengths": (status, [vp, vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
     "dmel_backward_multi": (status, [vp, vp, i32, vp, i32, i32, i32, vp, vp, vp]),
     "dmel_plan_lambd_status_channel": (status, [vp, i32, P(DmelLambdStatus)]),
     "dmel_decide_launch_multi": (status, [fp, fp, i32, f32, i32p, u32p, i32p]),
@@ -147,6 +149,8 @@ _SIGNATURES = {
     "dmel_plan_last_multi_launch": (status, [vp, i32p, u32p, i32p]),
     "dmel_forward_band": (status, [vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_band_dev": (status, [vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_band_lengths": (status, [vp, vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_band_dev_lengths": (status, [vp, vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
     "dmel_backward_band": (status, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp]),
     "dmel_backward_x_band": (status, [vp, vp, i32, fp, i32, vp, u32, vp, vp, vp, vp]),
     "dmel_backward_x_band_dev": (status, [vp, vp, i32, vp, i32, vp, i32p, u32p, i32, u32, vp, vp, vp, vp]),
@@ -433,18 +437,26 @@ class Plan:
     def scratch_bytes_multi(self, batch: int, channels: int) -> int:
         return int(load().dmel_scratch_bytes_multi(self._h, int(batch), int(channels)))
 
+    # (``lengths_ptr``: int32 per-clip lengths on the device -- the *_lengths entry points; None: the whole rows)
     def forward_multi(self, x_ptr: int, batch: int, lambd, out_ptr: int, tangent_ptr: int | None, log: bool, eps: float, stream: int,
-                      scratch_ptr: int, out_bf16: bool = False):
+                      scratch_ptr: int, out_bf16: bool = False, lengths_ptr: int | None = None):
         """lambd: the K host values (a sequence of floats)"""
         lam = _floats(lambd)
         flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
-        _check(load().dmel_forward_multi(self._h, x_ptr, batch, lam, len(lambd), flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream))
+        tail = (batch, lam, len(lambd), flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream)
+        if lengths_ptr is None:
+            _check(load().dmel_forward_multi(self._h, x_ptr, *tail))
+        else:
+            _check(load().dmel_forward_multi_lengths(self._h, x_ptr, lengths_ptr, *tail))
 
     def forward_multi_dev(self, x_ptr: int, batch: int, lambd_ptr: int, channels: int, out_ptr: int, tangent_ptr: int | None, log: bool,
-                          eps: float, stream: int, scratch_ptr: int, out_bf16: bool = False):
+                          eps: float, stream: int, scratch_ptr: int, out_bf16: bool = False, lengths_ptr: int | None = None):
         flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
-        _check(load().dmel_forward_multi_dev(self._h, x_ptr, batch, lambd_ptr, int(channels), flags, float(eps), out_ptr, tangent_ptr,
-                                             scratch_ptr, stream))
+        tail = (batch, lambd_ptr, int(channels), flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream)
+        if lengths_ptr is None:
+            _check(load().dmel_forward_multi_dev(self._h, x_ptr, *tail))
+        else:
+            _check(load().dmel_forward_multi_dev_lengths(self._h, x_ptr, lengths_ptr, *tail))
 
     def backward_multi(self, grad_ptr: int, tangent_ptr: int, batch: int, channels: int, dlambd_ptr: int, stream: int, scratch_ptr: int,
                        accumulate: bool = False, grad_bf16: bool = False):
@@ -453,19 +465,26 @@ class Plan:
 
     # -- the band-split layer (dmel_forward_band*, dmel_backward_band): one (B, 1, M, T) image, channel k owns rows edges[k] ... edges[k + 1] - 1 --
     def forward_band(self, x_ptr: int, batch: int, lambd, edges, out_ptr: int, tangent_ptr: int | None, log: bool, eps: float, stream: int,
-                     scratch_ptr: int, out_bf16: bool = False):
+                     scratch_ptr: int, out_bf16: bool = False, lengths_ptr: int | None = None):
         """lambd: the K host values; edges: K + 1 host integers"""
         lam = _floats(lambd)
         ed = _ints(edges)
         flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
-        _check(load().dmel_forward_band(self._h, x_ptr, batch, lam, len(lambd), ed, flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream))
+        tail = (batch, lam, len(lambd), ed, flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream)
+        if lengths_ptr is None:
+            _check(load().dmel_forward_band(self._h, x_ptr, *tail))
+        else:
+            _check(load().dmel_forward_band_lengths(self._h, x_ptr, lengths_ptr, *tail))
 
     def forward_band_dev(self, x_ptr: int, batch: int, lambd_ptr: int, edges, out_ptr: int, tangent_ptr: int | None, log: bool,
-                         eps: float, stream: int, scratch_ptr: int, out_bf16: bool = False):
+                         eps: float, stream: int, scratch_ptr: int, out_bf16: bool = False, lengths_ptr: int | None = None):
         ed = _ints(edges)
         flags = (DMEL_FLAG_LOG if log else 0) | (DMEL_FLAG_OUT_BF16 if out_bf16 else 0)
-        _check(load().dmel_forward_band_dev(self._h, x_ptr, batch, lambd_ptr, len(edges) - 1, ed, flags, float(eps), out_ptr, tangent_ptr,
-                                            scratch_ptr, stream))
+        tail = (batch, lambd_ptr, len(edges) - 1, ed, flags, float(eps), out_ptr, tangent_ptr, scratch_ptr, stream)
+        if lengths_ptr is None:
+            _check(load().dmel_forward_band_dev(self._h, x_ptr, *tail))
+        else:
+            _check(load().dmel_forward_band_dev_lengths(self._h, x_ptr, lengths_ptr, *tail))
 
     def backward_band(self, grad_ptr: int, tangent_ptr: int, batch: int, edges, dlambd_ptr: int, stream: int, scratch_ptr: int,
                       accumulate: bool = False, grad_bf16: bool = False):

@@ -815,8 +815,8 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     if (N < 1) return fail(DMEL_ERR_UNSUPPORTED, "n_fft = " + std::to_string(N));
     const bool pow2 = (N & (N - 1)) == 0;
     const bool big = !pow2 || N > dmel::kMaxNfft;
-    // per-clip lengths (dmel_fwd_len_kernel): the fused kernel's range, the scalar layer's HTK bank
-    if (lengths && (big || N < dmel::kMinFastNfft || spec_out || ml || win_half))
+    // per-clip lengths (dmel_fwd_len_kernel; with `ml`, dmel_fwd_multi_len_kernel / dmel_fwd_band_len_kernel): the fused kernel's range, the HTK bank
+    if (lengths && (big || N < dmel::kMinFastNfft || spec_out || win_half))
         return fail(DMEL_ERR_UNSUPPORTED, "per-clip lengths run the fused kernel only: n_fft 32 ... 16384 (n_fft = " + std::to_string(N) + ")");
     if (ml && (big || N < dmel::kMinFastNfft || spec_out))
         return fail(DMEL_ERR_UNSUPPORTED, "the multi-window layer runs n_fft 32 ... 16384 only (n_fft = " + std::to_string(N) + ")");
@@ -980,7 +980,7 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     static const int force_tpw = std::getenv("DMEL_TILES_PER_WG") ? std::atoi(std::getenv("DMEL_TILES_PER_WG")) : 0;   // diagnostics
     int tpw = dmel::forward_tiles_per_wg(N, mode, batch, fp.tiles_per_clip);
     if (force_tpw == 1 || (force_tpw == 2 && dmel::forward_two_tiles(N, mode))) tpw = force_tpw;
-    if (hsplit || lengths || (ml && ml->edges)) tpw = 1;                  // (dmel_fwd_len_kernel, dmel_fwd_band_kernel: one tile per workgroup)
+    if (hsplit || lengths || (ml && ml->edges)) tpw = 1;                  // (the length-aware kernels, dmel_fwd_band_kernel: one tile per workgroup)
     fp.wgs_per_clip = (fp.tiles_per_clip + tpw - 1) / tpw;
     long long grid = (long long)batch * fp.wgs_per_clip;
     if (ml) {
@@ -990,14 +990,18 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     }
     if (grid > 0x7fffffffLL) return fail(DMEL_ERR_INVALID_ARGUMENT, "too many tiles for one launch");
     if (grid <= dmel::forward_resident_workgroups(N, mode)) fp.flags |= dmel::kFwdEdgeFirst;      // one round: see the kernel's prologue
-    // the kernel follows the parameter type: per-clip lengths, the band-split layer's row ranges, or neither
+    // the kernel follows the parameter type: per-clip lengths, the band-split layer's row ranges, both, or neither
     const bool band = ml && ml->edges;
     dmel::FwdLenParams lp{};
     lp.lengths = lengths;
+    dmel::FwdMultiLenParams mlp{};
+    mlp.lengths = lengths;
     dmel::FwdBandParams bp{};
-    for (int c = 0; band && c <= dmel::kMaxChannels; ++c) bp.band_edges[c] = ml->edges[std::min(c, ml->channels)];
+    dmel::FwdBandLenParams blp{};
+    blp.lengths = lengths;
+    for (int c = 0; band && c <= dmel::kMaxChannels; ++c) blp.band_edges[c] = bp.band_edges[c] = ml->edges[std::min(c, ml->channels)];
     auto launch = [&](auto& q) { static_cast<dmel::FwdParams&>(q) = fp; return dmel::launch_forward(N, mode, tpw, q, (int)grid, s); };
-    DMEL_HIP(lengths ? launch(lp) : band ? launch(bp) : launch(fp));
+    DMEL_HIP(lengths ? (band ? launch(blp) : ml ? launch(mlp) : launch(lp)) : band ? launch(bp) : launch(fp));
     prof_span(pl, m1, prof_mark(pl, s), 1);
     pl->info.kernel_path = 0; pl->info.frames_per_tile = fpt; pl->info.grid_fwd = (int)grid;
     pl->info.fb_blocks = tb->n_entries; pl->info.fb_blocks_dense = tb->n_dense;
@@ -1788,6 +1792,9 @@ size_t dmel_scratch_bytes_multi(const dmel_plan* plan, int32_t batch, int32_t ch
 
 namespace {
 
+// the flags the multi-window and band-split forwards take
+constexpr uint32_t kMultiFlags = DMEL_FLAG_LOG | DMEL_FLAG_OUT_BF16;
+
 dmel_status check_multi_args(dmel_plan* pl, const float* x, int batch, int channels, uint32_t flags, const void* out, const float* tangent,
                              void* scratch, const char* fn)
 {
@@ -1795,7 +1802,7 @@ dmel_status check_multi_args(dmel_plan* pl, const float* x, int batch, int chann
     if (st != DMEL_OK) return st;
     if ((st = check_store_aligned(fn, {{"out", out}, {"tangent", tangent}, {"scratch", scratch}})) != DMEL_OK) return st;
     if (channels < 1 || channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, "channels must be 1 ... 8");
-    if (flags & ~(uint32_t)(DMEL_FLAG_LOG | DMEL_FLAG_OUT_BF16))
+    if (flags & ~kMultiFlags)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi: only DMEL_FLAG_LOG and DMEL_FLAG_OUT_BF16 are accepted");
     if (batch > 0 && !scratch) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi: scratch (dmel_scratch_bytes_multi) is required");
     if ((long long)batch * channels > 65534) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch x channels > 65534 (split the call)");
@@ -1808,7 +1815,7 @@ bool multi_in_range(int n) { return n >= dmel::kMinFastNfft && n <= dmel::kMaxFa
 // among the launches that carry it
 dmel_status issue_multi(dmel_plan* pl, const float* x, int batch, int channels, const int* ns, const uint32_t* mask, int nl,
                         const dmel::LamArgs& base, const float* vals, uint32_t flags, double eps, void* out, float* tangent,
-                        const Scratch& sc, hipStream_t s, const int32_t* edges = nullptr)
+                        const Scratch& sc, hipStream_t s, const int32_t* edges = nullptr, const int32_t* lengths = nullptr)
 {
     int first[dmel::kMaxChannels], last[dmel::kMaxChannels];
     for (int c = 0; c < channels; ++c) { first[c] = -1; last[c] = -1; }
@@ -1834,7 +1841,7 @@ dmel_status issue_multi(dmel_plan* pl, const float* x, int batch, int channels, 
         lam.n_expected = base.n_expected ? ns[i] : 0;
         if (i != 0) lam.dot_counter = nullptr;
         const dmel_status st = launch_forward_n(pl, x, batch, ns[i], lam, flags, eps, static_cast<float*>(out), tangent,
-                                                tangent ? dmel::kTrain : dmel::kInfer, /*remove_dc=*/1, sc, s, 0, &sums_done, nullptr, &ml);
+                                                tangent ? dmel::kTrain : dmel::kInfer, /*remove_dc=*/1, sc, s, 0, &sums_done, nullptr, &ml, lengths);
         if (st != DMEL_OK) return st;
         if (i == 0) primary_info = pl->info;
     }
@@ -1864,7 +1871,8 @@ dmel_status check_band_plan(const dmel_plan* pl, const int32_t* edges, int chann
 }
 
 dmel_status forward_multi_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, uint32_t flags,
-                               double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges)
+                               double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges,
+                               const int32_t* lengths = nullptr)
 {
     dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, tangent, scratch, edges ? "dmel_forward_band" : "dmel_forward_multi");
     if (st != DMEL_OK) return st;
@@ -1887,11 +1895,12 @@ dmel_status forward_multi_impl(dmel_plan* plan, const float* x, int32_t batch, c
     base.n_expected = 0;                          // every n_fft was derived from these very values
     base.dot_counter = sc.counter;
     return issue_multi(plan, x, batch, channels, ns, mask, nl, base, lambd_host, flags, eps, out, tangent, sc,
-                       reinterpret_cast<hipStream_t>(stream), edges);
+                       reinterpret_cast<hipStream_t>(stream), edges, lengths);
 }
 
 dmel_status forward_multi_dev_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
-                                   double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges)
+                                   double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges,
+                                   const int32_t* lengths = nullptr)
 {
     dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, tangent, scratch, edges ? "dmel_forward_band_dev" : "dmel_forward_multi_dev");
     if (st != DMEL_OK) return st;
@@ -1986,7 +1995,7 @@ dmel_status forward_multi_dev_impl(dmel_plan* plan, const float* x, int32_t batc
     base.exec_counter = plan->multi_exec; base.handled = sc.handled;
     base.host_seen = plan->multi_words; base.host_error = plan->multi_words + dmel::kLamRing;
     base.dot_counter = sc.counter;
-    return issue_multi(plan, x, batch, channels, ns, mask, nl, base, nullptr, flags, eps, out, tangent, sc, s, edges);
+    return issue_multi(plan, x, batch, channels, ns, mask, nl, base, nullptr, flags, eps, out, tangent, sc, s, edges, lengths);
 }
 
 }  // namespace
@@ -2003,29 +2012,79 @@ dmel_status dmel_forward_multi_dev(dmel_plan* plan, const float* x, int32_t batc
     return forward_multi_dev_impl(plan, x, batch, lambd_dev, channels, flags, eps, out, tangent, scratch, stream, nullptr);
 }
 
+// the multi-window forwards over clips of per-clip lengths (dmel_fwd_multi_len_kernel): the same launches, guards and per-channel pictures
+dmel_status dmel_forward_multi_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
+                                       int32_t channels, uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    if (!plan || !x || !lengths || !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_lengths: plan / x / lengths / out is NULL");
+    if (flags & ~kMultiFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_lengths: flags other than LOG, OUT_BF16");
+    return forward_multi_impl(plan, x, batch, lambd_host, channels, flags, eps, out, tangent, scratch, stream, nullptr, lengths);
+}
+
+dmel_status dmel_forward_multi_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                           int32_t channels, uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
+{
+    if (!plan || !x || !lengths || !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_dev_lengths: plan / x / lengths / out is NULL");
+    if (flags & ~kMultiFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_dev_lengths: flags other than LOG, OUT_BF16");
+    return forward_multi_dev_impl(plan, x, batch, lambd_dev, channels, flags, eps, out, tangent, scratch, stream, nullptr, lengths);
+}
+
 // ---- the band-split layer: K window widths inside ONE image, a width per group of mel bands -----------------------------------------
 // The multi-window layer's launches (one per distinct n_fft, the same per-channel lambd words, guards and scratch) through dmel_fwd_band_kernel.
 // band_edges are host integers, validated and taken by value (they travel in the kernel arguments).
+namespace {
+
+// what the four band forwards share: with `lengths_wanted` the NULL and flag checks of the *_lengths forms, then the edges validated against
+// themselves and the plan and taken by value, then the multi-window implementation `impl` (host or device lambd)
+using MultiImpl = dmel_status (*)(dmel_plan*, const float*, int32_t, const float*, int32_t, uint32_t, double, void*, float*, void*, void*,
+                                  const int32_t*, const int32_t*);
+dmel_status forward_band_common(MultiImpl impl, const char* who, bool lengths_wanted, dmel_plan* plan, const float* x, const int32_t* lengths,
+                                int32_t batch, const float* lambd, int32_t channels, const int32_t* band_edges, uint32_t flags, double eps,
+                                void* out, float* tangent, void* scratch, void* stream)
+{
+    if (lengths_wanted) {
+        if (!plan || !x || !lengths || !out) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": plan / x / lengths / out is NULL");
+        if (flags & ~kMultiFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": flags other than LOG, OUT_BF16");
+    }
+    dmel_status st = check_band_edges(band_edges, channels, who);
+    if (st != DMEL_OK) return st;
+    if ((st = check_band_plan(plan, band_edges, channels, who)) != DMEL_OK) return st;
+    int32_t edges[dmel::kMaxChannels + 1];
+    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
+    return impl(plan, x, batch, lambd, channels, flags, eps, out, tangent, scratch, stream, edges, lengths);
+}
+
+}  // namespace
+
 dmel_status dmel_forward_band(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, const int32_t* band_edges,
                               uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    dmel_status st = check_band_edges(band_edges, channels, "dmel_forward_band");
-    if (st != DMEL_OK) return st;
-    if ((st = check_band_plan(plan, band_edges, channels, "dmel_forward_band")) != DMEL_OK) return st;
-    int32_t edges[dmel::kMaxChannels + 1];
-    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
-    return forward_multi_impl(plan, x, batch, lambd_host, channels, flags, eps, out, tangent, scratch, stream, edges);
+    return forward_band_common(forward_multi_impl, "dmel_forward_band", false, plan, x, nullptr, batch, lambd_host, channels, band_edges, flags, eps,
+                               out, tangent, scratch, stream);
 }
 
 dmel_status dmel_forward_band_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, const int32_t* band_edges,
                                   uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    dmel_status st = check_band_edges(band_edges, channels, "dmel_forward_band_dev");
-    if (st != DMEL_OK) return st;
-    if ((st = check_band_plan(plan, band_edges, channels, "dmel_forward_band_dev")) != DMEL_OK) return st;
-    int32_t edges[dmel::kMaxChannels + 1];
-    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
-    return forward_multi_dev_impl(plan, x, batch, lambd_dev, channels, flags, eps, out, tangent, scratch, stream, edges);
+    return forward_band_common(forward_multi_dev_impl, "dmel_forward_band_dev", false, plan, x, nullptr, batch, lambd_dev, channels, band_edges, flags,
+                               eps, out, tangent, scratch, stream);
+}
+
+// the band-split forwards over clips of per-clip lengths (dmel_fwd_band_len_kernel)
+dmel_status dmel_forward_band_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
+                                      int32_t channels, const int32_t* band_edges, uint32_t flags, double eps, void* out, float* tangent,
+                                      void* scratch, void* stream)
+{
+    return forward_band_common(forward_multi_impl, "dmel_forward_band_lengths", true, plan, x, lengths, batch, lambd_host, channels, band_edges, flags,
+                               eps, out, tangent, scratch, stream);
+}
+
+dmel_status dmel_forward_band_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                          int32_t channels, const int32_t* band_edges, uint32_t flags, double eps, void* out, float* tangent,
+                                          void* scratch, void* stream)
+{
+    return forward_band_common(forward_multi_dev_impl, "dmel_forward_band_dev_lengths", true, plan, x, lengths, batch, lambd_dev, channels, band_edges,
+                               flags, eps, out, tangent, scratch, stream);
 }
 
 dmel_status dmel_backward_band(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int32_t batch, int32_t channels,

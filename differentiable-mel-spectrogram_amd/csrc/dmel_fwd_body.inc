@@ -5,15 +5,25 @@
 // dmel_fwd_band.hip includes it with DMEL_FWD_MULTI = 1 and DMEL_FWD_BAND = 1: dmel_fwd_band_kernel (BandSplitMelSpectrogram, FwdBandParams) -- the
 // multi-window kernel's channel addressing, but all channels write ONE (B, 1, M, T) image and channel c only its rows [e_c, e_c+1): the
 // contraction work of the other rows is skipped where a whole tile / phase lies outside them and every store site is confined to them.
+// The two axes compose: DMEL_FWD_LEN = 1 on top of DMEL_FWD_MULTI (and DMEL_FWD_BAND) makes dmel_fwd_multi_len_kernel (dmel_fwd_multi_len.hip,
+// FwdMultiLenParams) and dmel_fwd_band_len_kernel (dmel_fwd_band_len.hip, FwdBandLenParams): the K-window layers over clips of per-clip lengths.
 #if DMEL_FWD_MULTI
 #define FWD_BO bo
 #define FWD_LAM lam_args
 #define FWD_WIN2 win2
 #define FWD_LEADER grid_leader
-#if DMEL_FWD_BAND
+#if DMEL_FWD_BAND && DMEL_FWD_LEN
+#define FWD_KERNEL dmel_fwd_band_len_kernel
+#define FWD_PARAMS FwdBandLenParams
+#elif DMEL_FWD_BAND
 #define FWD_KERNEL dmel_fwd_band_kernel
+#define FWD_PARAMS FwdBandParams
+#elif DMEL_FWD_LEN
+#define FWD_KERNEL dmel_fwd_multi_len_kernel
+#define FWD_PARAMS FwdMultiLenParams
 #else
 #define FWD_KERNEL dmel_fwd_multi_kernel
+#define FWD_PARAMS FwdParams
 #endif
 #else
 #define FWD_BO b
@@ -22,8 +32,10 @@
 #define FWD_LEADER blockIdx.x == 0
 #if DMEL_FWD_LEN
 #define FWD_KERNEL dmel_fwd_len_kernel
+#define FWD_PARAMS FwdLenParams
 #else
 #define FWD_KERNEL dmel_fwd_kernel
+#define FWD_PARAMS FwdParams
 #endif
 #endif
 // sample-space bounds of a clip: p.L (also the row stride of x) and fl32(1 / L), or the clip's own length Lc (dmel_fwd_len_kernel); its
@@ -31,17 +43,11 @@
 // FWD_PAD_MEL(t, v): the mel power v of frame t, or 0 in a pad frame -- the pair modes' epilogue: there a pad frame shares its complex FFT
 // with a frame of the clip and would carry that frame's rounding noise
 #if DMEL_FWD_LEN
-#define FWD_PARAMS FwdLenParams
 #define FWD_LC Lc
 #define FWD_INV_L inv_Lc
 #define FWD_TC Tc
 #define FWD_PAD_MEL(t, v) ((t) < Tc ? (v) : 0.f)
 #else
-#if DMEL_FWD_BAND
-#define FWD_PARAMS FwdBandParams
-#else
-#define FWD_PARAMS FwdParams
-#endif
 #define FWD_LC p.L
 #define FWD_INV_L p.inv_L
 #define FWD_TC p.T
@@ -347,7 +353,15 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
 
 #if DMEL_FWD_LEN
     // rows of frames [t_first, t_end) of this clip without a transform: pad frames (zero mel power -- 0, or the epilogue's own log(0 + eps) --
-    // and a zero tangent) or, for an invalid length, NaN
+    // and a zero tangent) or, for an invalid length, NaN.  The rows are the channel's: all M of its own image (FWD_BO), or, in the band build,
+    // rows [e_lo, e_hi) of the shared one -- another group's rows are never written here
+#if DMEL_FWD_BAND
+#define FWD_FILL_ROWS (e_hi - e_lo)
+#define FWD_FILL_ROW(i) (e_lo + (i))
+#else
+#define FWD_FILL_ROWS p.M
+#define FWD_FILL_ROW(i) i
+#endif
     auto fill_rows = [&](int t_first, int t_end, bool pad) {
         const bool do_log = (p.flags & 1u) != 0;
         const bool out_bf16 = (p.flags & 4u) != 0;
@@ -360,9 +374,9 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
         if (t_end > p.T) t_end = p.T;
         const int nf = t_end - t_first;
         if (nf <= 0) return;
-        for (int idx = tid; idx < p.M * nf; idx += THREADS) {
-            const int m = idx / nf, t = t_first + idx % nf;
-            const size_t o = ((size_t)b * p.M + m) * p.T + t;
+        for (int idx = tid; idx < FWD_FILL_ROWS * nf; idx += THREADS) {
+            const int m = FWD_FILL_ROW(idx / nf), t = t_first + idx % nf;
+            const size_t o = ((size_t)FWD_BO * p.M + m) * p.T + t;
             if (out_bf16) reinterpret_cast<unsigned short*>(p.out)[o] = bf16_bits(v); else p.out[o] = v;
             if (p.tangent) p.tangent[o] = tv;
         }
@@ -1657,3 +1671,5 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
 #undef FWD_PAD_MEL
 #undef FWD_LIM_A
 #undef FWD_LIM_B
+#undef FWD_FILL_ROWS
+#undef FWD_FILL_ROW

@@ -1,6 +1,6 @@
-// dmel_fwd_dispatch.h -- the launch and attribute scaffolding the three builds of the fused forward share: dmel_fwd.hip (dmel_fwd_kernel,
-// dmel_fwd_multi_kernel), dmel_fwd_len.hip (dmel_fwd_len_kernel) and dmel_fwd_band.hip (dmel_fwd_band_kernel).  Each of them describes itself
-// in a variant V:
+// dmel_fwd_dispatch.h -- the launch and attribute scaffolding the builds of the fused forward share: dmel_fwd.hip (dmel_fwd_kernel,
+// dmel_fwd_multi_kernel), dmel_fwd_len.hip (dmel_fwd_len_kernel), dmel_fwd_band.hip (dmel_fwd_band_kernel), dmel_fwd_multi_len.hip
+// (dmel_fwd_multi_len_kernel) and dmel_fwd_band_len.hip (dmel_fwd_band_len_kernel).  Each of them describes itself in a variant V:
 //
 //   using Params                                       FwdParams or what derives from it
 //   using Modes = FwdModes<...>                        the modes it is built for
@@ -33,7 +33,7 @@ template <class F> static bool with_nfft(int n_fft, F&& f)
     return false;
 }
 
-// -DDMEL_FWD_SPLIT -DDMEL_FWD_PART=<k>, k = 0..3: build.py compiles each of the three files four times for libdmel_hip.so so that the
+// -DDMEL_FWD_SPLIT -DDMEL_FWD_PART=<k>, k = 0..3: build.py compiles each of these files four times for libdmel_hip.so so that the
 // instantiations of the large transforms -- minutes of compile time each -- build in parallel: part 0 holds everything that is not a template
 // instantiation plus the sizes up to 512, parts 1-3 hold 1024 / 2048 + 16384 / 4096 + 8192 and nothing else.  Without DMEL_FWD_SPLIT (the
 // tools' one-command builds) everything is in one translation unit, part 0.

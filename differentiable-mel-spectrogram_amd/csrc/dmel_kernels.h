@@ -444,6 +444,15 @@ struct FwdBandParams : FwdParams {
     int band_edges[kMaxChannels + 1];   // 0 = e_0 < e_1 < ... < e_K = M (validated by the host)
 };
 
+// dmel_fwd_multi_len_kernel (csrc/dmel_fwd_multi_len.hip) and dmel_fwd_band_len_kernel (csrc/dmel_fwd_band_len.hip): the multi-window and the
+// band-split launch over clips of per-clip lengths.  Layouts of their own: the structs above are what the existing kernels take.
+struct FwdMultiLenParams : FwdParams {
+    const int* lengths;         // (B) device, as FwdLenParams::lengths
+};
+struct FwdBandLenParams : FwdBandParams {
+    const int* lengths;         // (B) device, as FwdLenParams::lengths
+};
+
 struct PrepParams {
     const float* x; float* psum; float2* win2;
     const float* const* x_ind;      // DMEL_FLAG_X_INDIRECT: the address of x is read from here (then x is nullptr), as in FwdParams
@@ -456,10 +465,13 @@ struct PrepParams {
 };
 
 hipError_t launch_prep(const PrepParams& p, hipStream_t s);
-// the fused forward: the kernel is picked by the parameter type (dmel_fwd.hip, dmel_fwd_len.hip, dmel_fwd_band.hip)
+// the fused forward: the kernel is picked by the parameter type (dmel_fwd.hip, dmel_fwd_len.hip, dmel_fwd_band.hip, dmel_fwd_multi_len.hip,
+// dmel_fwd_band_len.hip)
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdParams& p, int grid, hipStream_t s);
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdLenParams& p, int grid, hipStream_t s);    // kTrain, kTrainW, kInfer
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdBandParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
+hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdMultiLenParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
+hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdBandLenParams& p, int grid, hipStream_t s);    // kTrain, kTrainW, kInfer
 int forward_tiles_per_wg(int n_fft, int mode, int batch, int tiles_per_clip);          // 1 or 2: what launch_forward should be given
 bool forward_two_tiles(int n_fft, int mode);          // the two-tiles-per-workgroup instantiation exists for this size and mode
 int forward_lds_bytes(int n_fft, int mode);
@@ -710,13 +722,16 @@ hipError_t launch_mailbox_allreduce(float* buf, const MailboxArgs& mb, hipStream
 hipError_t forward_prepare_attributes();
 hipError_t forward_len_prepare_attributes();
 hipError_t forward_band_prepare_attributes();
+hipError_t forward_multi_len_prepare_attributes();
+hipError_t forward_band_len_prepare_attributes();
 hipError_t xgrad_prepare_attributes();
 hipError_t xgrad_len_prepare_attributes();
 hipError_t xgrad_band_prepare_attributes();
 hipError_t big_prepare_attributes();
 inline hipError_t prepare_attributes()
 {
-    for (auto unit : {forward_prepare_attributes, forward_len_prepare_attributes, forward_band_prepare_attributes, xgrad_prepare_attributes,
+    for (auto unit : {forward_prepare_attributes, forward_len_prepare_attributes, forward_band_prepare_attributes, forward_multi_len_prepare_attributes,
+                      forward_band_len_prepare_attributes, xgrad_prepare_attributes,
                       xgrad_len_prepare_attributes, xgrad_band_prepare_attributes, big_prepare_attributes})
         if (const hipError_t e = unit(); e != hipSuccess) return e;
     return hipSuccess;

@@ -422,6 +422,31 @@ def _no_lengths(name: str) -> str:
     return f"{name} does not take per-clip lengths (MelSpectrogramLayer does)"
 
 
+def _frame_lengths(lengths, hop_length):
+    """Valid frames per clip of a ``forward(x, lengths)``: ``lengths // hop_length + 1`` (models.py:30 at ``n_points = lengths[b]``), on the
+    tensor's own device.  One definition for every layer that takes lengths."""
+    return lengths // hop_length + 1
+
+
+def _lengths_for_kernels(x, lengths, n_points):
+    """Type, dtype, shape and device of the ``lengths`` of a ``forward(x, lengths)``; returns them as the kernels read them (int32,
+    contiguous, on x's device).  Their values never leave the device.  One copy for every layer that takes lengths."""
+    if not torch.is_tensor(lengths):
+        raise TypeError(f"lengths must be a 1-D integer tensor, got {type(lengths).__name__}")
+    if lengths.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"lengths must hold int32 or int64 values, got {lengths.dtype}")
+    if lengths.dim() != 1 or lengths.shape[0] != x.shape[0]:
+        raise ValueError(f"lengths must have shape ({x.shape[0]},), got {tuple(lengths.shape)}")
+    if lengths.device.type == "cpu":
+        lengths = lengths.to(x.device)
+    elif lengths.device != x.device:
+        raise RuntimeError(f"lengths is on {lengths.device} but x is on {x.device}")
+    if lengths.dtype != torch.int32:
+        # int64 values clamped on the device before the narrowing: a length such as 2**32 + 4000 must stay invalid (NaN), not wrap to 4000
+        lengths = lengths.clamp(0, n_points + 1).to(torch.int32)
+    return lengths if lengths.is_contiguous() else lengths.contiguous()
+
+
 def _check_input(name, x, lambd, lengths=None, *, n_points=None, check_lengths=None, refuse_slot=None, slot_config_ok=None,
                  refuse_x_grad=None):
     """Every refusal the ``forward`` of a layer class starts with, in one order (the order decides which error wins when two apply).
@@ -618,7 +643,7 @@ class MelSpectrogramLayer(_PlanCachingModule):
     def frame_lengths(self, lengths: torch.Tensor) -> torch.Tensor:
         """Valid frames per clip of ``forward(x, lengths)``: ``lengths // hop_length + 1`` (models.py:30 at ``n_points = lengths[b]``),
         on the tensor's own device."""
-        return lengths // self.hop_length + 1
+        return _frame_lengths(lengths, self.hop_length)
 
     def _slot_config_ok(self) -> bool:
         return self.mel_fb is None and self.optimized and not self.lambd_sync
@@ -637,8 +662,8 @@ class MelSpectrogramLayer(_PlanCachingModule):
             plan.set_filterbank_dev(n, fbd.data_ptr(), _stream_ptr(x.device))
 
     def _check_lengths(self, x, lengths):
-        """Whether this layer takes per-clip lengths, then shape, dtype and device of ``lengths``; returns them as the kernels read them
-        (int32, contiguous, on x's device).  Their values never leave the device."""
+        """Whether this layer takes per-clip lengths, then shape, dtype and device of ``lengths`` (_lengths_for_kernels); returns them as the
+        kernels read them (int32, contiguous, on x's device).  Their values never leave the device."""
         want_x = self.lengths_waveform_grad and torch.is_grad_enabled() and not isinstance(x, SlotInput) and x.requires_grad
         if self.mel_fb is not None:
             raise RuntimeError("per-clip lengths run the HTK bank only: learnable_fb=True does not take lengths"
@@ -646,20 +671,7 @@ class MelSpectrogramLayer(_PlanCachingModule):
         if not self.optimized:
             raise RuntimeError("per-clip lengths need optimized=True (the optimized=False branch's n_fft = 2 n_points depends on the clip length)"
                                + ("; the waveform gradient of per-clip lengths needs it too" if want_x else ""))
-        if not torch.is_tensor(lengths):
-            raise TypeError(f"lengths must be a 1-D integer tensor, got {type(lengths).__name__}")
-        if lengths.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"lengths must hold int32 or int64 values, got {lengths.dtype}")
-        if lengths.dim() != 1 or lengths.shape[0] != x.shape[0]:
-            raise ValueError(f"lengths must have shape ({x.shape[0]},), got {tuple(lengths.shape)}")
-        if lengths.device.type == "cpu":
-            lengths = lengths.to(x.device)
-        elif lengths.device != x.device:
-            raise RuntimeError(f"lengths is on {lengths.device} but x is on {x.device}")
-        if lengths.dtype != torch.int32:
-            # int64 values clamped on the device before the narrowing: a length such as 2**32 + 4000 must stay invalid (NaN), not wrap to 4000
-            lengths = lengths.clamp(0, self.n_points + 1).to(torch.int32)
-        return lengths if lengths.is_contiguous() else lengths.contiguous()
+        return _lengths_for_kernels(x, lengths, self.n_points)
 
     # -- forward ------------------------------------------------------------------------------
     def _forward_lengths(self, x, lengths):
@@ -728,10 +740,12 @@ class MelSpectrogramLayer(_PlanCachingModule):
 class _MultiFunction(torch.autograd.Function):
     """forward: dmel_forward_multi(_dev) -- one launch per distinct n_fft for all K channels, carrying d out / d lambd[k] per channel;
     backward: dmel_backward_multi (K dot products in one launch) and, for a waveform that requires grad (waveform_grad=True),
-    dmel_backward_x_multi(_dev): one x-gradient for all K channels, the sum of the K scalar layers' in ascending channel order."""
+    dmel_backward_x_multi(_dev): one x-gradient for all K channels, the sum of the K scalar layers' in ascending channel order.
+    With ``lengths`` (per_clip_lengths=True; int32 on x's device) the forward is dmel_forward_multi(_dev)_lengths; the backward is the same
+    dot over its tangent, whose pad frames are zero.  (No waveform gradient with lengths: the layer refuses it.)"""
 
     @staticmethod
-    def forward(ctx, x, lambd, plan, lam_host, log, eps, out_dtype, want_tangent):
+    def forward(ctx, x, lambd, plan, lam_host, log, eps, out_dtype, want_tangent, lengths=None):
         B, K = x.shape[0], lambd.shape[0]
         want_x = ctx.needs_input_grad[0]
         out, tangent, scratch, round_later = _alloc(x, (B, K, plan.n_mels, plan.n_time), out_dtype, want_tangent, log and want_x,
@@ -741,11 +755,11 @@ class _MultiFunction(torch.autograd.Function):
         with _on_device(x.device):
             if lam_host is not None:
                 plan.forward_multi(x.data_ptr(), B, lam_host, out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
-                                   scratch.data_ptr(), out_bf16=bf16)
+                                   scratch.data_ptr(), out_bf16=bf16, lengths_ptr=_ptr(lengths))
             else:
                 lam = _lambd_f32(lambd)
                 plan.forward_multi_dev(x.data_ptr(), B, lam.data_ptr(), K, out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
-                                       scratch.data_ptr(), out_bf16=bf16)
+                                       scratch.data_ptr(), out_bf16=bf16, lengths_ptr=_ptr(lengths))
         ctx.plan, ctx.K, ctx.lambd_shape, ctx.lambd_dtype = plan, K, lambd.shape, lambd.dtype
         ctx.want_tangent, ctx.want_x, ctx.log, ctx.lam_host = want_tangent, want_x, bool(log), lam_host
         # what this forward launched for (host bookkeeping of the plan, no device read): a later forward cannot change what the backward covers
@@ -780,7 +794,7 @@ class _MultiFunction(torch.autograd.Function):
                 else:
                     ctx.plan.backward_x_multi_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.K, ctx.launches, g32.data_ptr(), _ptr(out),
                                                   gx.data_ptr(), ctx.log, _stream_ptr(g.device))
-        return gx, dl, None, None, None, None, None, None
+        return gx, dl, None, None, None, None, None, None, None
 
 
 class MultiWindowMelSpectrogram(_PlanCachingModule):
@@ -788,7 +802,7 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
 
         MultiWindowMelSpectrogram(init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1,
                                   normalize_window=False, *, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False,
-                                  waveform_grad=False)
+                                  waveform_grad=False, per_clip_lengths=False)
         forward(x: (B, n_points)) -> (B, K, n_mels, n_points // hop_length + 1)
 
     ``y[:, k:k+1]`` is what ``MelSpectrogramLayer(lambd[k], ..., optimized=True)`` returns for the same ``x``, bit for bit (each
@@ -799,12 +813,19 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
     ``waveform_grad=True`` accepts an ``x`` that requires grad: ``x.grad`` is, bit for bit, the sum in ascending channel order of what the K
     scalar layers give (one x-gradient launch per distinct n_fft and one combine for all channels).  The forward then keeps ``x`` and the
     fp32 output alive until the backward, which the default layer does not; without it ``x.requires_grad`` raises.
+    ``per_clip_lengths=True`` (keyword-only, off by default: without it ``lengths`` is refused) makes ``forward(x, lengths)`` compute a
+    zero-padded batch clip by clip: ``lengths`` as ``MelSpectrogramLayer.forward(x, lengths)`` takes them (a (B,) int32 / int64 tensor, read by
+    the kernels only, so the sync-free step stays capturable), and ``y[:, k:k+1]`` is what that scalar forward returns at ``lambd[k]``, bit for
+    bit -- each clip's own mean, pad frames (``0`` or ``log(0 + eps)``, no gradient) from ``frame_lengths(lengths)[b]`` on, tiles of pad
+    frames not transformed, ``x[b, lengths[b]:]`` never read, a length outside ``1 ... n_points`` NaN in every channel of that clip.
+    ``lambd.grad`` comes through the same backward.  ``forward(x)`` is unchanged.  Per-clip lengths have no waveform gradient on this
+    layer yet: ``x.requires_grad`` together with ``lengths`` raises, with or without ``waveform_grad``.
     Not supported: ``SlotInput``, ``GraphedStep`` and ``LambdAdam(fused_into_backward=...)``."""
 
     MAX_CHANNELS = 8
 
     def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
-                 log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False):
+                 log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False, per_clip_lengths=False):
         super().__init__()
         lam = init_lambd.detach().clone() if torch.is_tensor(init_lambd) else torch.tensor([float(v) for v in init_lambd])
         if lam.dim() != 1:
@@ -828,6 +849,7 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
         self.n_time = n_points // hop_length + 1
         self.log, self.eps, self.out_dtype, self.lambd_sync = bool(log), float(eps), out_dtype, bool(lambd_sync)
         self.waveform_grad = bool(waveform_grad)
+        self.per_clip_lengths = bool(per_clip_lengths)                # forward(x, lengths) is taken (opt-in: without it lengths are refused)
 
     @property
     def channels(self) -> int:
@@ -836,35 +858,49 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
     def lambd_status(self, channel: int = 0, device=None) -> dict:
         return self._plan_on(device).lambd_status_channel(channel)
 
+    def frame_lengths(self, lengths: torch.Tensor) -> torch.Tensor:
+        """Valid frames per clip of ``forward(x, lengths)``: ``lengths // hop_length + 1``, as MelSpectrogramLayer.frame_lengths."""
+        return _frame_lengths(lengths, self.hop_length)
+
     def _prepare(self, name, x, lengths, refuse_slot, refuse_x_grad):
-        """the checks and conversions the K-channel forwards share: (x as fp32, lambd's host values or None, whether to carry the tangent)"""
-        _check_input(name, x, self.lambd, lengths, n_points=self.n_points, refuse_slot=refuse_slot, refuse_x_grad=refuse_x_grad)
-        xf = _as_f32_contiguous(x)
+        """the checks and conversions the K-channel forwards share: (x as fp32, lambd's host values or None, whether to carry the tangent,
+        the lengths as the kernels read them or None)"""
+        check = None
+        if self.per_clip_lengths:
+            check = lambda x_, l_: _lengths_for_kernels(x_, l_, self.n_points)      # noqa: E731
+            if lengths is not None:
+                refuse_x_grad = (f"per-clip lengths have no waveform gradient on {name} yet: pass x.detach() "
+                                 "(MelSpectrogramLayer(lengths_waveform_grad=True) has one)")
+        lengths = _check_input(name, x, self.lambd, lengths, n_points=self.n_points, check_lengths=check, refuse_slot=refuse_slot,
+                               refuse_x_grad=refuse_x_grad)
+        xf = _as_f32_contiguous(x, lengths)
         lam_host = [float(v) for v in self.lambd.detach().cpu().tolist()] if self.lambd_sync else None
         # the tangent only when a gradient will be asked for (as torch.ops.dmel.mel_spectrogram: grad mode and lambd.requires_grad);
         # otherwise the inference kernels, which pair two frames per FFT
-        return xf, lam_host, torch.is_grad_enabled() and self.lambd.requires_grad
+        return xf, lam_host, torch.is_grad_enabled() and self.lambd.requires_grad, lengths
 
     def forward(self, x, lengths=None):
         no_x_grad = None if self.waveform_grad else ("MultiWindowMelSpectrogram has no waveform gradient by default: pass waveform_grad=True, "
                                                      "or x.detach()")
-        xf, lam_host, want = self._prepare("MultiWindowMelSpectrogram", x, lengths, "MultiWindowMelSpectrogram does not take a SlotInput", no_x_grad)
-        return _MultiFunction.apply(xf, self.lambd, self._plan_for(x.device), lam_host, self.log, self.eps, self.out_dtype, want)
+        xf, lam_host, want, lengths = self._prepare("MultiWindowMelSpectrogram", x, lengths, "MultiWindowMelSpectrogram does not take a SlotInput",
+                                                    no_x_grad)
+        return _MultiFunction.apply(xf, self.lambd, self._plan_for(x.device), lam_host, self.log, self.eps, self.out_dtype, want, lengths)
 
     def extra_repr(self):
         return (f"channels={self.channels}, n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
                 f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}, "
-                f"waveform_grad={self.waveform_grad}")
+                f"waveform_grad={self.waveform_grad}, per_clip_lengths={self.per_clip_lengths}")
 
 
 class _BandFunction(torch.autograd.Function):
     """forward: dmel_forward_band(_dev) -- one launch per distinct n_fft for all K channels, every channel writing its own rows of ONE
     (B, 1, M, T) image and of its tangent; backward: dmel_backward_band (the K row-group dot products in one launch) and, for a waveform
     that requires grad (waveform_grad=True), dmel_backward_x_band(_dev): every channel's x-gradient from its own rows of the ONE cotangent,
-    summed in ascending channel order (what _MultiFunction saves for it, this one saves too)."""
+    summed in ascending channel order (what _MultiFunction saves for it, this one saves too).  With ``lengths``:
+    dmel_forward_band(_dev)_lengths, as _MultiFunction."""
 
     @staticmethod
-    def forward(ctx, x, lambd, plan, lam_host, edges, log, eps, out_dtype, want_tangent):
+    def forward(ctx, x, lambd, plan, lam_host, edges, log, eps, out_dtype, want_tangent, lengths=None):
         B, K = x.shape[0], lambd.shape[0]
         want_x = ctx.needs_input_grad[0]
         out, tangent, scratch, round_later = _alloc(x, (B, 1, plan.n_mels, plan.n_time), out_dtype, want_tangent, log and want_x,
@@ -874,11 +910,11 @@ class _BandFunction(torch.autograd.Function):
         with _on_device(x.device):
             if lam_host is not None:
                 plan.forward_band(x.data_ptr(), B, lam_host, edges, out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
-                                  scratch.data_ptr(), out_bf16=bf16)
+                                  scratch.data_ptr(), out_bf16=bf16, lengths_ptr=_ptr(lengths))
             else:
                 lam = _lambd_f32(lambd)
                 plan.forward_band_dev(x.data_ptr(), B, lam.data_ptr(), edges, out.data_ptr(), _ptr(tangent), log, eps,
-                                      _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16)
+                                      _stream_ptr(x.device), scratch.data_ptr(), out_bf16=bf16, lengths_ptr=_ptr(lengths))
         ctx.plan, ctx.lambd_shape, ctx.lambd_dtype, ctx.edges, ctx.want_tangent = plan, lambd.shape, lambd.dtype, edges, want_tangent
         ctx.want_x, ctx.log, ctx.lam_host = want_x, bool(log), lam_host
         # what this forward launched for (host bookkeeping of the plan, no device read): a later forward cannot change what the backward covers
@@ -913,14 +949,15 @@ class _BandFunction(torch.autograd.Function):
                 else:
                     ctx.plan.backward_x_band_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.edges, ctx.launches, g32.data_ptr(), _ptr(out),
                                                  gx.data_ptr(), ctx.log, _stream_ptr(g.device))
-        return gx, dl, None, None, None, None, None, None, None
+        return gx, dl, None, None, None, None, None, None, None, None
 
 
 class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
     """A trainable window width per GROUP OF MEL BANDS inside one image: the scalar layer's output shape, K resolutions.
 
         BandSplitMelSpectrogram(init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
-                                band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False)
+                                band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False,
+                                per_clip_lengths=False)
         forward(x: (B, n_points)) -> (B, 1, n_mels, n_points // hop_length + 1)
 
     ``band_edges`` are K + 1 integers ``0 = e_0 < e_1 < ... < e_K = n_mels`` (default ``e_k = (k * n_mels) // K``).  Rows
@@ -947,13 +984,21 @@ class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
     ``x.grad`` for the stacked ``G_k`` without the ``(B, K, M, T)`` tensors: every channel loads only its own rows of the one cotangent.
     The forward output and ``lambd.grad`` do not change; the forward then keeps ``x`` and the fp32 output alive until the backward.  A
     channel no launch covered makes ``x.grad`` NaN.  Without the flag ``x.requires_grad`` raises.
-    Out of scope, not forgotten (each raises and says what to use instead): per-clip ``lengths``, ``SlotInput``, ``GraphedStep`` and
+    ``per_clip_lengths=True`` (keyword-only, off by default: without it ``lengths`` is refused) makes ``forward(x, lengths)`` compute a
+    zero-padded batch clip by clip, as ``MelSpectrogramLayer.forward(x, lengths)`` does and with its ``lengths``: rows
+    ``e_k ... e_{k+1} - 1`` are those rows of that scalar forward at ``lambd[k]``, bit for bit (each clip's own mean, pad frames of value
+    ``0`` / ``log(0 + eps)`` and no gradient from ``frame_lengths(lengths)[b]`` on, pad tiles not transformed, ``x[b, lengths[b]:]`` never
+    read, a length outside ``1 ... n_points`` NaN in every group's rows of that clip); a channel writes pad and NaN rows into its own rows
+    only.  The values are read by the kernels only: the sync-free step stays capturable.  ``forward(x)`` is unchanged.
+    Out of scope, not forgotten (each raises and says what to use instead): the waveform gradient of per-clip ``lengths``
+    (``x.requires_grad`` together with ``lengths`` raises, with or without ``waveform_grad``), ``SlotInput``, ``GraphedStep`` and
     ``LambdAdam(fused_into_backward=...)``; band edges and the filterbank are not trainable."""
 
     def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
-                 band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False):
+                 band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False,
+                 per_clip_lengths=False):
         super().__init__(init_lambd, n_mels, n_points, sample_rate, f_min, f_max, hop_length, normalize_window, log=log, eps=eps,
-                         out_dtype=out_dtype, lambd_sync=lambd_sync, waveform_grad=waveform_grad)
+                         out_dtype=out_dtype, lambd_sync=lambd_sync, waveform_grad=waveform_grad, per_clip_lengths=per_clip_lengths)
         K = self.lambd.shape[0]
         if band_edges is None:
             if K > n_mels:
@@ -973,15 +1018,16 @@ class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
     def forward(self, x, lengths=None):
         no_x_grad = None if self.waveform_grad else ("BandSplitMelSpectrogram has no waveform gradient: pass x.detach() (MelSpectrogramLayer and "
                                                      "MultiWindowMelSpectrogram(waveform_grad=True) have one)")
-        xf, lam_host, want = self._prepare("BandSplitMelSpectrogram", x, lengths,
-                                           "BandSplitMelSpectrogram does not take a SlotInput: pass the batch tensor (MelSpectrogramLayer takes slots)",
-                                           no_x_grad)
-        return _BandFunction.apply(xf, self.lambd, self._plan_for(x.device), lam_host, self.band_edges, self.log, self.eps, self.out_dtype, want)
+        xf, lam_host, want, lengths = self._prepare("BandSplitMelSpectrogram", x, lengths,
+                                                    "BandSplitMelSpectrogram does not take a SlotInput: pass the batch tensor (MelSpectrogramLayer takes slots)",
+                                                    no_x_grad)
+        return _BandFunction.apply(xf, self.lambd, self._plan_for(x.device), lam_host, self.band_edges, self.log, self.eps, self.out_dtype, want,
+                                   lengths)
 
     def extra_repr(self):
         return (f"band_edges={list(self.band_edges)}, n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
                 f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}, "
-                f"waveform_grad={self.waveform_grad}")
+                f"waveform_grad={self.waveform_grad}, per_clip_lengths={self.per_clip_lengths}")
 
 
 class _DspecFunction(torch.autograd.Function):

@@ -480,6 +480,17 @@ dmel_status dmel_forward_multi(dmel_plan* plan, const float* x, int32_t batch, c
                                double eps, void* out, float* tangent, void* scratch, void* stream);
 dmel_status dmel_forward_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
                                    double eps, void* out, float* tangent, void* scratch, void* stream);
+/* dmel_forward_multi(_dev) over clips of per-clip lengths (zero-padded batches): lengths as dmel_forward_lengths takes them (device, `batch`
+ * int32 values, read by the kernels only), and that function's semantics per channel -- channel k is what dmel_forward_lengths computes for
+ * lambd[k], bit for bit: the clip's own mean, pad frames (0, or log(0 + eps); zero tangent) from lengths[b] / hop_length + 1 on, tiles of pad
+ * frames not transformed, x[b, lengths[b]:] never read, a length outside 1 ... n_points NaN in every channel of that clip.  A channel that no
+ * launch covered is NaN whatever the lengths are.  Flags, scratch, launch choice, guards, per-channel pictures, DMEL_ERR_LAMBD_TRACKING and
+ * dmel_plan_last_multi_launch are dmel_forward_multi(_dev)'s; dmel_backward_multi consumes the tangent.  NULL handles and pointers:
+ * DMEL_ERR_INVALID_ARGUMENT before any device call. */
+dmel_status dmel_forward_multi_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
+                                       int32_t channels, uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream);
+dmel_status dmel_forward_multi_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                           int32_t channels, uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream);
 /* dlambd[k] (= or += with accumulate) sum over clips of grad_out[:, k] . tangent[:, k], K values in ONE deterministic launch (fp64
  * accumulation, fixed-order combine; bf16 gradients widened exactly).  Not with an attached mailbox or fused Adam. */
 dmel_status dmel_backward_multi(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int32_t batch, int32_t channels,
@@ -505,7 +516,7 @@ dmel_status dmel_backward_x_multi(dmel_plan* plan, const float* x, int32_t batch
 dmel_status dmel_backward_x_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
                                       const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count, uint32_t flags,
                                       const float* grad_out, const float* out, float* grad_x, void* stream);
-/* What the most recent dmel_forward_multi(_dev) or dmel_forward_band(_dev) on this plan issued (host bookkeeping, captured calls included):
+/* What the most recent dmel_forward_multi(_dev), dmel_forward_band(_dev) or their _lengths forms on this plan issued (host bookkeeping, captured calls included):
  * count entries in ascending n_fft with their channel masks; arrays of 24 (3 x 8) entries.  count = 0 before the first such call. */
 dmel_status dmel_plan_last_multi_launch(dmel_plan* plan, int32_t* n_ffts, uint32_t* channel_masks, int32_t* count);
 
@@ -521,6 +532,15 @@ dmel_status dmel_forward_band(dmel_plan* plan, const float* x, int32_t batch, co
                               uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream);
 dmel_status dmel_forward_band_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, const int32_t* band_edges,
                                   uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream);
+/* dmel_forward_band(_dev) over clips of per-clip lengths: rows e_k ... e_{k+1} - 1 are those rows of what dmel_forward_lengths computes for
+ * lambd[k], bit for bit; pad rows and the NaN rows of an invalid length are written by each channel into its own rows only.  Everything else as
+ * dmel_forward_multi(_dev)_lengths and dmel_forward_band(_dev). */
+dmel_status dmel_forward_band_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
+                                      int32_t channels, const int32_t* band_edges, uint32_t flags, double eps, void* out, float* tangent,
+                                      void* scratch, void* stream);
+dmel_status dmel_forward_band_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                          int32_t channels, const int32_t* band_edges, uint32_t flags, double eps, void* out, float* tangent,
+                                          void* scratch, void* stream);
 /* dlambd[k] (= or += with accumulate) sum over clips and rows e_k ... e_{k+1} - 1 of grad_out . tangent, both (batch, 1, n_mels, n_time): K
  * values in ONE deterministic launch (fp64 accumulation, workgroups dealt to the groups in proportion to their rows, fixed-order combine; bf16
  * gradients widened exactly).  Not with an attached mailbox or fused Adam. */
