@@ -1,10 +1,12 @@
 // dmel_api.cpp -- host side of libdmel_hip.so: the C ABI of include/dmel.h.
 //
-// Owns everything that is not a kernel: n_fft derivation (time_frequency.py:39,60-65), the HTK mel
-// filterbank of models.py:42-48 and its packing into non-zero MFMA B-fragments, FFT twiddle tables,
-// per-plan workspace, argument checking and kernel dispatch.  No torch types, no oracle code.
+// Owns everything that is not a kernel: the HTK mel filterbank of models.py:42-48 and its packing into non-zero MFMA B-fragments, FFT twiddle tables,
+// per-plan workspace, argument checking and kernel dispatch.  No torch types, no oracle code.  In order: tables; scratch and workspaces; the forward
+// (FwdCall describes a call, launch_forward_n issues it for one n_fft through forward_big / _naive / _fused); the host steps of the sync-free lambd
+// tracking around dmel_lamtrack.h, once for K tracked values; the extern "C" entry points, which check, fill a call description by name and hand it on.
 #include "../../include/dmel.h"
 #include "dmel_kernels.h"
+#include "dmel_lamtrack.h"
 
 #include <algorithm>
 #include <cmath>
@@ -128,28 +130,14 @@ struct dmel_plan {
     // Every forward that executes draws an execution number from `exec_counter` (device) and reports under it (dmel_kernels.h).
     unsigned long long* host_words = nullptr;   // pinned, device-visible: [0..kLamRing) reports (number << 32) | bits(lambd), [kLamRing] sticky error
     unsigned* exec_counter = nullptr;           // device: executions so far
-    unsigned issued = 0;           // the host's estimate of the execution number of its most recent eagerly issued forward (caught up
-                                   // with the reports: replays of captured forwards execute without the host counting them)
+    dmel::LamTrack track;          // the host's picture of the scalar layer's lambd (dmel_lamtrack.h)
     unsigned calls = 0;            // dmel_forward_dev / _fixed calls, captured ones included; never adjusted
-    bool lam_known = false;        // lam_seen / seq_seen hold an observation
-    float lam_seen = 0.f;
-    unsigned seq_seen = 0;         // execution number the observation belongs to
-    unsigned seq_floor = 0;        // reports with a smaller number predate the last reset
-    int n_obs = 0;                 // observations since the last reset
-    float lam_rate = 0.f;          // decayed maximum of |d lambd| per execution
     int max_ahead = 8;             // forwards the host may run ahead of the last observation (0: unbounded)
     int guard_mode = 0;            // 0 auto, 1 always both neighbours, 2 never, 3 auto also under capture
     int forced_n_fft = 0, forced_guards = 0;    // dmel_plan_force_launch: the caller chooses the launches (0: the library does)
-    int last_guards = 0;           // bit 0: n_fft/2 launched, bit 1: 2 n_fft launched (most recent call)
-    // the multi-window layer (dmel_forward_multi_dev): one picture of lambd per channel, kept like the fields above, and its own words on
-    // the device side (made at the first multi-window call): channel c reports into multi_words + c kLamMultiStride and counts on multi_exec[c]
-    struct LamTrack {
-        unsigned issued = 0, seq_seen = 0, seq_floor = 0;
-        bool lam_known = false;
-        float lam_seen = 0.f, lam_rate = 0.f;
-        int n_obs = 0, last_guards = 0;
-    };
-    LamTrack multi[dmel::kMaxChannels];
+    // the multi-window layer (dmel_forward_multi_dev): one picture of lambd per channel, and its own words on the device side (made at
+    // the first multi-window call): channel c reports into multi_words + c kLamMultiStride and counts on multi_exec[c]
+    dmel::LamTrack multi[dmel::kMaxChannels];
     unsigned long long* multi_words = nullptr;
     unsigned* multi_exec = nullptr;
     // what the most recent dmel_forward_multi(_dev) issued (dmel_plan_last_multi_launch), and the workspace of dmel_backward_x_multi(_dev)
@@ -653,7 +641,7 @@ size_t scratch_bytes_multi(const dmel_plan* pl, int batch, int channels)
     return scratch_bytes(pl, batch) + (size_t)(channels - 1) * dmel::kMaxNfft * 8;
 }
 
-Scratch carve(void* base, int channels = 1)
+Scratch carve(void* base, int channels)
 {
     unsigned char* b = static_cast<unsigned char*>(base);
     Scratch sc;
@@ -696,7 +684,28 @@ dmel_status ensure_own_scratch(dmel_plan* pl, int batch, hipStream_t s, Scratch*
         DMEL_HIP(hipMemset(pl->own_scratch, 0, kScratchWin));
         pl->own_scratch_clips = clips;
     }
-    *sc = carve(pl->own_scratch);
+    *sc = carve(pl->own_scratch, 1);
+    return DMEL_OK;
+}
+
+// the scratch of a call: the caller's, or the plan's own behind whatever the plan's previous stream still runs
+dmel_status select_scratch(dmel_plan* pl, void* scratch, int batch, hipStream_t s, Scratch* sc)
+{
+    if (scratch) { *sc = carve(scratch, 1); return DMEL_OK; }
+    const dmel_status st = order_after_last_stream(pl, s);
+    if (st != DMEL_OK) return st;
+    return ensure_own_scratch(pl, batch, s, sc);
+}
+
+// a plan-owned workspace of floats (dmel_plan::fbw, xmw) grows to `need`: never under capture (`who`: the refusal's first words)
+dmel_status grow_floats(float** buf, size_t* have, size_t need, hipStream_t s, const std::string& who)
+{
+    if (need <= *have) return DMEL_OK;
+    if (is_capturing(s)) return fail(DMEL_ERR_INVALID_ARGUMENT, who + "workspace must grow but the stream is capturing: run one call eagerly first");
+    DMEL_HIP(hipStreamSynchronize(s));
+    (void)hipFree(*buf); *buf = nullptr; *have = 0;
+    DMEL_HIP(hipMalloc(buf, need * sizeof(float)));
+    *have = need;
     return DMEL_OK;
 }
 
@@ -801,161 +810,162 @@ dmel_status grow_big_workspace(dmel_plan* pl, int N, size_t need_z, hipStream_t 
     return DMEL_OK;
 }
 
-// One launch (plus, when needed, the partial-sum / window-table kernel in front of it) of the forward for a given n_fft.
-// `lam` says where lambd comes from and whether the kernels check it against N (dmel_kernels.h); `sc` is the scratch of
-// this call.  Shared by every entry point; the plan mutex is held by the caller.
-// one launch of the multi-window layer: `count` channels (nibbles of `list`, with their lambd roles in `roles`) of an output with `ch_out` channels
-// (edges != nullptr: the band-split layer -- ch_out = 1, channel c writes rows [edges[c], edges[c + 1]) of the one image: dmel_fwd_band_kernel)
+// one launch of the multi-window layer: `count` channels (nibbles of `list`, with their lambd roles in `roles`) of an output with `ch_out` channels (edges !=
+// nullptr: the band-split layer -- ch_out = 1, channel c writes rows [edges[c], edges[c + 1]) of the one image: dmel_fwd_band_kernel).  channels = 0: none
 struct MultiLaunch { int ch_out = 0, count = 0; unsigned list = 0, roles = 0; float vals[dmel::kMaxChannels] = {}; const int32_t* edges = nullptr; int channels = 0; };
 
-dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dmel::LamArgs lam, unsigned flags, double eps,
-                             float* out, float* tangent, int mode, int remove_dc, const Scratch& sc, hipStream_t s, int win_half,
-                             bool* sums_done, float* spec_out = nullptr, const MultiLaunch* ml = nullptr, const int32_t* lengths = nullptr)
+// What a forward call asks for, filled by field name at the entry points; what varies between the launches of one call (n_fft, lambd roles) travels next to it
+struct FwdCall {
+    const float* x = nullptr; int batch = 0; unsigned flags = 0; double eps = 0.0; float* out = nullptr; float* tangent = nullptr;
+    int mode = dmel::kInfer, remove_dc = 1, win_half = 0;
+    float* spec_out = nullptr; const int32_t* lengths = nullptr;       // dmel_forward_dev_fixed_spec: the spectrogram is saved too; per-clip lengths (device)
+    MultiLaunch ml;
+    bool multi() const { return ml.channels > 0; }
+    // DMEL_FLAG_X_INDIRECT: x is a pointer cell that holds the batch's address, read by every kernel of the forward
+    const float* const* x_cell() const { return (flags & DMEL_FLAG_X_INDIRECT) ? reinterpret_cast<const float* const*>(x) : nullptr; }
+    const float* x_direct() const { return (flags & DMEL_FLAG_X_INDIRECT) ? nullptr : x; }
+};
+// the mel layer's forward: the training kernels when a tangent is asked for, DC removed
+FwdCall mel_call(const float* x, int batch, unsigned flags, double eps, void* out, float* tangent)
 {
-    if (N < 1) return fail(DMEL_ERR_UNSUPPORTED, "n_fft = " + std::to_string(N));
-    const bool pow2 = (N & (N - 1)) == 0;
-    const bool big = !pow2 || N > dmel::kMaxNfft;
-    // per-clip lengths (dmel_fwd_len_kernel; with `ml`, dmel_fwd_multi_len_kernel / dmel_fwd_band_len_kernel): the fused kernel's range, the HTK bank
-    if (lengths && (big || N < dmel::kMinFastNfft || spec_out || win_half))
-        return fail(DMEL_ERR_UNSUPPORTED, "per-clip lengths run the fused kernel only: n_fft 32 ... 16384 (n_fft = " + std::to_string(N) + ")");
-    if (ml && (big || N < dmel::kMinFastNfft || spec_out))
-        return fail(DMEL_ERR_UNSUPPORTED, "the multi-window layer runs n_fft 32 ... 16384 only (n_fft = " + std::to_string(N) + ")");
-    if (spec_out && (big || N < dmel::kMinFastNfft || mode != dmel::kTrain))
-        return fail(DMEL_ERR_UNSUPPORTED, "the spectrogram is saved by the fused training kernel only (power-of-two n_fft from 32 to 16384, tangent requested)");
-    if (big && (N & 1)) return fail(DMEL_ERR_UNSUPPORTED, "n_fft = " + std::to_string(N) + " is odd");
-    // DMEL_FLAG_X_INDIRECT: every kernel of the forward reads the batch's address from a pointer cell (round 5: the fused kernel and the
-    // partial sums only; a lambd that left n_fft 32 ... 16384 inside a captured loop then ended in NaN + an error -- ADVICE r05)
-    const float* const* x_cell = (flags & DMEL_FLAG_X_INDIRECT) ? reinterpret_cast<const float* const*>(x) : nullptr;
-    NfftTables* tb = nullptr;
-    dmel_status st = build_tables(pl, N, &tb);
+    FwdCall c;
+    c.x = x; c.batch = batch; c.flags = flags; c.eps = eps; c.out = static_cast<float*>(out); c.tangent = tangent; c.mode = tangent ? dmel::kTrain : dmel::kInfer;
+    return c;
+}
+// the K-window layers: K channels of (batch, K, M, T), or with band_edges the row groups of ONE (batch, 1, M, T) image
+FwdCall k_call(const float* x, int batch, int channels, const int32_t* band_edges, unsigned flags, double eps, void* out, float* tangent)
+{
+    FwdCall c = mel_call(x, batch, flags, eps, out, tangent);
+    c.ml.channels = channels; c.ml.ch_out = channels; c.ml.edges = band_edges;
+    return c;
+}
+// the spectrogram layer's forward: no mel stage, no log
+FwdCall spec_call(const float* x, int batch, float* spec, float* tangent, uint32_t spec_flags)
+{
+    FwdCall c;
+    c.x = x; c.batch = batch; c.out = spec; c.tangent = tangent; c.mode = tangent ? dmel::kSpecTrain : dmel::kSpec;
+    c.remove_dc = (spec_flags & DMEL_SPEC_REMOVE_DC) ? 1 : 0; c.win_half = (spec_flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0;
+    return c;
+}
+
+// the prep kernel in front of a forward launch: clip sums (kPrepSums) and / or window table (kPrepWindow; multi-window: one per channel at win + c kMaxNfft)
+constexpr unsigned kPrepSums = 1u, kPrepWindow = 2u;
+dmel_status forward_prep(dmel_plan* pl, int N, float2* win, const dmel::LamArgs& lam, const FwdCall& c, const Scratch& sc, hipStream_t s, unsigned what)
+{
+    const bool need_sums = (what & kPrepSums) != 0, need_window = (what & kPrepWindow) != 0;
+    dmel::PrepParams pp{};
+    pp.x = c.x_direct(); pp.x_ind = c.x_cell(); pp.psum = sc.psum; pp.win2 = win;
+    pp.B = need_sums ? c.batch : 0; pp.L = pl->cfg.n_points; pp.nchunks = pl->nchunks; pp.chunk = pl->chunk;
+    pp.N = need_window ? N : 0; pp.normalize = pl->cfg.normalize_window; pp.win_half = c.win_half; pp.center = window_center(N, c.win_half);
+    pp.lam = lam; pp.lam.role = dmel::kLamQuiet; pp.lengths = need_sums ? c.lengths : nullptr;
+    if (c.multi() && need_window) {
+        for (int i = 0; i < c.ml.count; ++i) {
+            const int ch = (int)((c.ml.list >> (4 * i)) & 15u);
+            pp.lam = dmel::lam_for_channel(lam, ch, 0, dmel::kLamQuiet, c.ml.vals);
+            pp.win2 = win + (size_t)ch * dmel::kMaxNfft;
+            pp.B = (need_sums && i == 0) ? c.batch : 0;
+            DMEL_HIP(dmel::launch_prep(pp, s));
+        }
+        return DMEL_OK;
+    }
+    DMEL_HIP(dmel::launch_prep(pp, s));
+    return DMEL_OK;
+}
+
+// ---- lengths the LDS kernels do not reach: global-memory FFT / Bluestein (dmel_big.hip) --------------------------------
+dmel_status forward_big(dmel_plan* pl, NfftTables* tb, const dmel::LamArgs& lam, const FwdCall& c, const Scratch& sc, hipStream_t s,
+                        bool* sums_done, dmel_plan_info* info)
+{
+    const int N = tb->n_fft;
+    dmel_plan::BigTab bt;
+    const float2* tw = nullptr;
+    dmel_status st = big_tables_for(pl, N, &bt, &tw);
     if (st != DMEL_OK) return st;
-    const float center = window_center(N, win_half);
-    if (big) {
-        // ---- lengths the LDS kernels do not reach: global-memory FFT / Bluestein (dmel_big.hip) ------------------------
-        dmel_plan::BigTab bt;
-        const float2* tw = nullptr;
-        if ((st = big_tables_for(pl, N, &bt, &tw)) != DMEL_OK) return st;
-        // split mode (dmel_big.hip): the transform itself would live in global memory, its two halves fit LDS
-        const float2* wodd = nullptr;
-        bool split = false;
-        if (dmel::big_uses_global(bt.M)) {
-            const int H = N / 2;
-            int Mh = H;
-            if (H & (H - 1)) { Mh = 1; while (Mh < 2 * H - 1) Mh <<= 1; }
-            if (H >= 2 && dmel::big_can_split(Mh, pl->cfg.n_mels)) {
-                if ((st = big_tables_for(pl, H, &bt, &tw)) != DMEL_OK) return st;
-                auto wit = pl->big_wodd.find(N);
-                if (wit == pl->big_wodd.end()) {
-                    std::vector<float2> w((size_t)H);
-                    for (int n = 0; n < H; ++n) {
-                        const double th = -2.0 * M_PI * (double)n / (double)N;
-                        w[n] = make_float2((float)std::cos(th), (float)std::sin(th));
-                    }
-                    float2* d = nullptr;
-                    DMEL_HIP(hipMalloc(&d, w.size() * sizeof(float2)));
-                    DMEL_HIP(hipMemcpy(d, w.data(), w.size() * sizeof(float2), hipMemcpyHostToDevice));
-                    wit = pl->big_wodd.emplace(N, d).first;
+    // split mode (dmel_big.hip): the transform itself would live in global memory, its two halves fit LDS
+    const float2* wodd = nullptr;
+    bool split = false;
+    if (dmel::big_uses_global(bt.M)) {
+        const int H = N / 2;
+        int Mh = H;
+        if (H & (H - 1)) { Mh = 1; while (Mh < 2 * H - 1) Mh <<= 1; }
+        if (H >= 2 && dmel::big_can_split(Mh, pl->cfg.n_mels)) {
+            if ((st = big_tables_for(pl, H, &bt, &tw)) != DMEL_OK) return st;
+            auto wit = pl->big_wodd.find(N);
+            if (wit == pl->big_wodd.end()) {
+                std::vector<float2> w((size_t)H);
+                for (int n = 0; n < H; ++n) {
+                    const double th = -2.0 * M_PI * (double)n / (double)N;
+                    w[n] = make_float2((float)std::cos(th), (float)std::sin(th));
                 }
-                wodd = wit->second;
-                split = true;
+                float2* d = nullptr;
+                DMEL_HIP(hipMalloc(&d, w.size() * sizeof(float2)));
+                DMEL_HIP(hipMemcpy(d, w.data(), w.size() * sizeof(float2), hipMemcpyHostToDevice));
+                wit = pl->big_wodd.emplace(N, d).first;
             }
+            wodd = wit->second;
+            split = true;
         }
-        if ((st = order_after_last_stream(pl, s)) != DMEL_OK) return st;          // window table and sequences are plan-owned
-        const bool pair = (mode == dmel::kInfer || mode == dmel::kSpec);
-        const long long units = (long long)batch * (pair ? (pl->T + 1) / 2 : pl->T);
-        const int grid = dmel::big_grid(units, bt.M);
-        const size_t need_z = dmel::big_uses_global(bt.M) ? (size_t)grid * bt.M : 0;
-        if ((st = grow_big_workspace(pl, N, need_z, s)) != DMEL_OK) return st;
-        const bool need_sums = remove_dc && !*sums_done;
-        const size_t m0 = prof_mark(pl, s);
-        {
-            dmel::PrepParams pp{};
-            pp.x = x_cell ? nullptr : x; pp.x_ind = x_cell; pp.psum = sc.psum; pp.win2 = pl->big_win;
-            pp.B = need_sums ? batch : 0; pp.L = pl->cfg.n_points; pp.nchunks = pl->nchunks; pp.chunk = pl->chunk;
-            pp.N = N; pp.normalize = pl->cfg.normalize_window; pp.win_half = win_half; pp.center = center;
-            pp.lam = lam; pp.lam.role = dmel::kLamQuiet;
-            DMEL_HIP(dmel::launch_prep(pp, s));
-            if (need_sums) *sums_done = true;
-        }
-        const size_t m1 = prof_mark(pl, s);
-        prof_span(pl, m0, m1, 0);
-        dmel::BigParams bp{};
-        bp.x = x_cell ? nullptr : x; bp.x_ind = x_cell; bp.out = out; bp.tangent = tangent; bp.psum = sc.psum; bp.win2 = pl->big_win;
-        bp.tw = tw; bp.chirp = bt.chirp; bp.hbr = bt.hbr; bp.zws = pl->big_z; bp.fbT = tb->fbT; bp.band = tb->band;
-        bp.B = batch; bp.L = pl->cfg.n_points; bp.T = pl->T; bp.hop = pl->cfg.hop_length; bp.M = pl->cfg.n_mels;
-        bp.nchunks = pl->nchunks; bp.N = N; bp.F = tb->F; bp.mode = mode; bp.Mfft = bt.M; bp.logM = bt.logM;
-        bp.inv_L = 1.0f / (float)pl->cfg.n_points; bp.eps = (float)eps; bp.flags = flags; bp.remove_dc = remove_dc; bp.lam = lam;
-        bp.split = split ? 1 : 0; bp.wodd = wodd;
-        DMEL_HIP(dmel::launch_big(bp, s));
-        prof_span(pl, m1, prof_mark(pl, s), 1);
-        pl->info.n_fft = N; pl->info.n_freqs = tb->F; pl->info.n_time = pl->T;
-        pl->info.kernel_path = 3; pl->info.frames_per_tile = pair ? 2 : 1; pl->info.grid_fwd = grid;
-        pl->info.fb_blocks = 0; pl->info.fb_blocks_dense = 0; pl->info.lds_bytes = dmel::big_uses_global(bt.M) ? 0 : bt.M * 8;
-        pl->info.contraction = -1; pl->info.wl_steps = 0;
-        return DMEL_OK;
     }
-
-    // The fused kernel builds its own window table (n_fft <= 4096) and, for clips up to 32768 samples, its
-    // own clip mean; the prep kernel only runs for what is left: partial sums of long clips, the window
-    // table of n_fft 8192 / 16384, and everything the direct-DFT kernel (n_fft < 32) needs.
-    const bool fast = N >= dmel::kMinFastNfft && N <= dmel::kMaxFastNfft;
-    const bool kernel_mean = fast && pl->cfg.n_points <= 32768;
-    const bool need_sums = remove_dc && !kernel_mean && !*sums_done;                  // the launches of one group share the sums
-    const bool need_window = !fast || !dmel::forward_window_in_lds(N);
+    if ((st = order_after_last_stream(pl, s)) != DMEL_OK) return st;          // window table and sequences are plan-owned
+    const bool pair = (c.mode == dmel::kInfer || c.mode == dmel::kSpec);
+    const long long units = (long long)c.batch * (pair ? (pl->T + 1) / 2 : pl->T);
+    const int grid = dmel::big_grid(units, bt.M);
+    const size_t need_z = dmel::big_uses_global(bt.M) ? (size_t)grid * bt.M : 0;
+    if ((st = grow_big_workspace(pl, N, need_z, s)) != DMEL_OK) return st;
+    const bool need_sums = c.remove_dc && !*sums_done;
     const size_t m0 = prof_mark(pl, s);
-    if (need_sums || need_window) {
-        dmel::PrepParams pp{};
-        pp.x = x; pp.psum = sc.psum; pp.win2 = sc.win;
-        if (flags & DMEL_FLAG_X_INDIRECT) { pp.x_ind = reinterpret_cast<const float* const*>(x); pp.x = nullptr; }
-        pp.B = need_sums ? batch : 0; pp.L = pl->cfg.n_points; pp.nchunks = pl->nchunks; pp.chunk = pl->chunk;
-        pp.N = need_window ? N : 0; pp.normalize = pl->cfg.normalize_window; pp.win_half = win_half; pp.center = center;
-        pp.lam = lam; pp.lam.role = dmel::kLamQuiet;
-        pp.lengths = need_sums ? lengths : nullptr;
-        if (ml && need_window) {
-            // the multi-window layer: one window table per channel (win + c kMaxNfft, lambd[c]); the clip sums once for all of them
-            for (int i = 0; i < ml->count; ++i) {
-                const int c = (int)((ml->list >> (4 * i)) & 15u);
-                pp.lam = dmel::lam_for_channel(lam, c, 0, dmel::kLamQuiet, ml->vals);
-                pp.win2 = sc.win + (size_t)c * dmel::kMaxNfft;
-                pp.B = (need_sums && i == 0) ? batch : 0;
-                DMEL_HIP(dmel::launch_prep(pp, s));
-            }
-        } else {
-            DMEL_HIP(dmel::launch_prep(pp, s));
-        }
-        if (need_sums) *sums_done = true;
-    }
+    if ((st = forward_prep(pl, N, pl->big_win, lam, c, sc, s, kPrepWindow | (need_sums ? kPrepSums : 0u))) != DMEL_OK) return st;
+    if (need_sums) *sums_done = true;
     const size_t m1 = prof_mark(pl, s);
-    if (need_sums || need_window) prof_span(pl, m0, m1, 0);
+    prof_span(pl, m0, m1, 0);
+    dmel::BigParams bp{};
+    bp.x = c.x_direct(); bp.x_ind = c.x_cell(); bp.out = c.out; bp.tangent = c.tangent; bp.psum = sc.psum; bp.win2 = pl->big_win;
+    bp.tw = tw; bp.chirp = bt.chirp; bp.hbr = bt.hbr; bp.zws = pl->big_z; bp.fbT = tb->fbT; bp.band = tb->band;
+    bp.B = c.batch; bp.L = pl->cfg.n_points; bp.T = pl->T; bp.hop = pl->cfg.hop_length; bp.M = pl->cfg.n_mels;
+    bp.nchunks = pl->nchunks; bp.N = N; bp.F = tb->F; bp.mode = c.mode; bp.Mfft = bt.M; bp.logM = bt.logM;
+    bp.inv_L = 1.0f / (float)pl->cfg.n_points; bp.eps = (float)c.eps; bp.flags = c.flags; bp.remove_dc = c.remove_dc; bp.lam = lam;
+    bp.split = split ? 1 : 0; bp.wodd = wodd;
+    DMEL_HIP(dmel::launch_big(bp, s));
+    prof_span(pl, m1, prof_mark(pl, s), 1);
+    info->kernel_path = 3; info->frames_per_tile = pair ? 2 : 1; info->grid_fwd = grid;
+    info->fb_blocks = 0; info->fb_blocks_dense = 0; info->lds_bytes = dmel::big_uses_global(bt.M) ? 0 : bt.M * 8;
+    info->contraction = -1; info->wl_steps = 0;
+    return DMEL_OK;
+}
 
-    pl->info.n_fft = N; pl->info.n_freqs = tb->F; pl->info.n_time = pl->T;
-    const float inv_L = 1.0f / (float)pl->cfg.n_points;
-    if (N < dmel::kMinFastNfft) {
-        dmel::NaiveParams np{};
-        np.x = x_cell ? nullptr : x; np.x_ind = x_cell; np.out = out; np.tangent = tangent; np.psum = sc.psum; np.win2 = sc.win; np.fb = tb->fb_dense;
-        np.B = batch; np.L = pl->cfg.n_points; np.T = pl->T; np.hop = pl->cfg.hop_length; np.M = pl->cfg.n_mels;
-        np.nchunks = pl->nchunks; np.N = N; np.F = tb->F; np.mode = mode;
-        np.inv_L = inv_L; np.eps = (float)eps; np.flags = flags; np.remove_dc = remove_dc; np.lam = lam;
-        DMEL_HIP(dmel::launch_naive(np, s));
-        prof_span(pl, m1, prof_mark(pl, s), 1);
-        pl->info.kernel_path = 1; pl->info.frames_per_tile = 1; pl->info.grid_fwd = batch * pl->T;
-        pl->info.fb_blocks = 0; pl->info.fb_blocks_dense = 0; pl->info.lds_bytes = (2 * N + 2 * tb->F) * 4;
-        pl->info.contraction = -1; pl->info.wl_steps = 0;
-        return DMEL_OK;
-    }
+// ---- n_fft < 32: the direct-DFT kernel (its window table and clip sums come from the prep kernel, already issued) ----------
+dmel_status forward_naive(dmel_plan* pl, NfftTables* tb, const dmel::LamArgs& lam, const FwdCall& c, const Scratch& sc, hipStream_t s,
+                          dmel_plan_info* info)
+{
+    const int N = tb->n_fft;
+    dmel::NaiveParams np{};
+    np.x = c.x_direct(); np.x_ind = c.x_cell(); np.out = c.out; np.tangent = c.tangent; np.psum = sc.psum; np.win2 = sc.win; np.fb = tb->fb_dense;
+    np.B = c.batch; np.L = pl->cfg.n_points; np.T = pl->T; np.hop = pl->cfg.hop_length; np.M = pl->cfg.n_mels;
+    np.nchunks = pl->nchunks; np.N = N; np.F = tb->F; np.mode = c.mode;
+    np.inv_L = 1.0f / (float)pl->cfg.n_points; np.eps = (float)c.eps; np.flags = c.flags; np.remove_dc = c.remove_dc; np.lam = lam;
+    DMEL_HIP(dmel::launch_naive(np, s));
+    info->kernel_path = 1; info->frames_per_tile = 1; info->grid_fwd = c.batch * pl->T;
+    info->fb_blocks = 0; info->fb_blocks_dense = 0; info->lds_bytes = (2 * N + 2 * tb->F) * 4;
+    info->contraction = -1; info->wl_steps = 0;
+    return DMEL_OK;
+}
+
+// ---- n_fft 32 ... 16384: the fused wave-FFT + MFMA kernel; `kernel_mean`: it forms the clip mean itself --------------------
+dmel_status forward_fused(dmel_plan* pl, NfftTables* tb, const dmel::LamArgs& lam, const FwdCall& c, const Scratch& sc, hipStream_t s,
+                          bool kernel_mean, dmel_plan_info* info)
+{
+    const int N = tb->n_fft;
+    const MultiLaunch* ml = c.multi() ? &c.ml : nullptr;
+    int mode = c.mode;
+    const unsigned flags = c.flags & ~DMEL_FLAG_X_INDIRECT;
     dmel::FwdParams fp{};
-    if (flags & DMEL_FLAG_X_INDIRECT) {
-        fp.x_ind = reinterpret_cast<const float* const*>(x);
-        x = nullptr;
-        flags &= ~DMEL_FLAG_X_INDIRECT;
-    }
-    fp.x = x; fp.out = out; fp.tangent = tangent; fp.psum = (remove_dc && !kernel_mean) ? sc.psum : nullptr; fp.win2 = sc.win;
+    fp.x = c.x_direct(); fp.x_ind = c.x_cell(); fp.out = c.out; fp.tangent = c.tangent; fp.psum = (c.remove_dc && !kernel_mean) ? sc.psum : nullptr; fp.win2 = sc.win;
     fp.tw1 = dmel::mode_pairs(mode) ? tb->tw1p : tb->tw1; fp.tw2 = dmel::mode_pairs(mode) ? tb->tw2p : tb->tw2; fp.ent_b = tb->ent_b; fp.tile_ranges = tb->tile_ranges; fp.ent_b_floats = tb->ent_b_floats; fp.ent_pre = tb->ent_pre;
     for (int i = 0; i < 16; ++i) fp.pre_groups[i] = tb->pre_groups[i];
-    fp.B = batch; fp.L = pl->cfg.n_points; fp.T = pl->T; fp.hop = pl->cfg.hop_length; fp.M = pl->cfg.n_mels;
+    fp.B = c.batch; fp.L = pl->cfg.n_points; fp.T = pl->T; fp.hop = pl->cfg.hop_length; fp.M = pl->cfg.n_mels;
     fp.nchunks = pl->nchunks; fp.groups = tb->groups; fp.xch_groups = tb->xch_groups;
     // DMEL_FLAG_MFMA_BF16X3: the training forward through a caller-supplied (dense) bank contracts on the bf16 matrix pipe
-    const bool hsplit = (flags & DMEL_FLAG_MFMA_BF16X3) && mode == dmel::kTrain && tb->ent_h != nullptr && !lengths;
+    const bool hsplit = (flags & DMEL_FLAG_MFMA_BF16X3) && mode == dmel::kTrain && tb->ent_h != nullptr && !c.lengths;
     if (hsplit) mode = dmel::kTrainH;
     // the wave-local contraction where it is built (n_fft 1024, up to 512 mel bands): DMEL_WLC=0 keeps the round-4 kernel, DMEL_WLC=1
     // the 8-wave workgroups, DMEL_WLC=2 the 16-wave ones where they are built (diagnostics).
@@ -965,7 +975,7 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     const bool wl_compact = tb->wl_total4 * 4 <= 320;
     if (mode == dmel::kTrain && tb->wl_b4 != nullptr && wlc_env != 0 && (wl_compact || wlc_env > 0)) {
         const int wide_fpt = dmel::forward_has_wlc_wide(N) ? dmel::forward_frames_per_tile(N, dmel::kTrainWW) : 0;
-        const bool wide = wide_fpt > 0 && wlc_env == 2 && !lengths;      // (16-wave workgroups: measured slower, dmel_kernels.h; built only on request)
+        const bool wide = wide_fpt > 0 && wlc_env == 2 && !c.lengths;      // (16-wave workgroups: measured slower, dmel_kernels.h; built only on request)
         mode = wide ? dmel::kTrainWW : dmel::kTrainW;
         fp.wl_b4 = tb->wl_b4; fp.wl_lane = tb->wl_lane; fp.wl_phases = tb->wl_phases; fp.wl_total4 = tb->wl_total4;
         for (int i = 0; i < dmel::kWlMaxPhases; ++i) { fp.wl_len4[i] = tb->wl_len4[i]; fp.wl_mg[i] = tb->wl_mg[i]; }
@@ -973,19 +983,19 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     }
     const int fpt = dmel::forward_frames_per_tile(N, mode);
     fp.tiles_per_clip = (pl->T + fpt - 1) / fpt;
-    fp.inv_L = inv_L; fp.eps = (float)eps; fp.flags = flags; fp.lam = lam;
-    fp.remove_dc = remove_dc; fp.normalize = pl->cfg.normalize_window; fp.win_half = win_half;
-    fp.spec_out = spec_out;
+    fp.inv_L = 1.0f / (float)pl->cfg.n_points; fp.eps = (float)c.eps; fp.flags = flags; fp.lam = lam;
+    fp.remove_dc = c.remove_dc; fp.normalize = pl->cfg.normalize_window; fp.win_half = c.win_half;
+    fp.spec_out = c.spec_out;
     fp.ent_h = tb->ent_h; fp.fb_nyq = tb->fb_nyq;
     static const int force_tpw = std::getenv("DMEL_TILES_PER_WG") ? std::atoi(std::getenv("DMEL_TILES_PER_WG")) : 0;   // diagnostics
-    int tpw = dmel::forward_tiles_per_wg(N, mode, batch, fp.tiles_per_clip);
+    int tpw = dmel::forward_tiles_per_wg(N, mode, c.batch, fp.tiles_per_clip);
     if (force_tpw == 1 || (force_tpw == 2 && dmel::forward_two_tiles(N, mode))) tpw = force_tpw;
-    if (hsplit || lengths || (ml && ml->edges)) tpw = 1;                  // (the length-aware kernels, dmel_fwd_band_kernel: one tile per workgroup)
+    if (hsplit || c.lengths || (ml && ml->edges)) tpw = 1;                  // (the length-aware kernels, dmel_fwd_band_kernel: one tile per workgroup)
     fp.wgs_per_clip = (fp.tiles_per_clip + tpw - 1) / tpw;
-    long long grid = (long long)batch * fp.wgs_per_clip;
+    long long grid = (long long)c.batch * fp.wgs_per_clip;
     if (ml) {
         fp.ch_out = ml->ch_out; fp.ch_grid = (int)grid; fp.ch_list = ml->list; fp.ch_roles = ml->roles;
-        for (int c = 0; c < dmel::kMaxChannels; ++c) fp.ch_val[c] = ml->vals[c];
+        for (int ch = 0; ch < dmel::kMaxChannels; ++ch) fp.ch_val[ch] = ml->vals[ch];
         grid *= ml->count;
     }
     if (grid > 0x7fffffffLL) return fail(DMEL_ERR_INVALID_ARGUMENT, "too many tiles for one launch");
@@ -993,22 +1003,79 @@ dmel_status launch_forward_n(dmel_plan* pl, const float* x, int batch, int N, dm
     // the kernel follows the parameter type: per-clip lengths, the band-split layer's row ranges, both, or neither
     const bool band = ml && ml->edges;
     dmel::FwdLenParams lp{};
-    lp.lengths = lengths;
+    lp.lengths = c.lengths;
     dmel::FwdMultiLenParams mlp{};
-    mlp.lengths = lengths;
+    mlp.lengths = c.lengths;
     dmel::FwdBandParams bp{};
     dmel::FwdBandLenParams blp{};
-    blp.lengths = lengths;
-    for (int c = 0; band && c <= dmel::kMaxChannels; ++c) blp.band_edges[c] = bp.band_edges[c] = ml->edges[std::min(c, ml->channels)];
+    blp.lengths = c.lengths;
+    for (int ch = 0; band && ch <= dmel::kMaxChannels; ++ch) blp.band_edges[ch] = bp.band_edges[ch] = ml->edges[std::min(ch, ml->channels)];
     auto launch = [&](auto& q) { static_cast<dmel::FwdParams&>(q) = fp; return dmel::launch_forward(N, mode, tpw, q, (int)grid, s); };
-    DMEL_HIP(lengths ? (band ? launch(blp) : ml ? launch(mlp) : launch(lp)) : band ? launch(bp) : launch(fp));
-    prof_span(pl, m1, prof_mark(pl, s), 1);
-    pl->info.kernel_path = 0; pl->info.frames_per_tile = fpt; pl->info.grid_fwd = (int)grid;
-    pl->info.fb_blocks = tb->n_entries; pl->info.fb_blocks_dense = tb->n_dense;
-    pl->info.lds_bytes = dmel::forward_lds_bytes(N, mode);
+    DMEL_HIP(c.lengths ? (band ? launch(blp) : ml ? launch(mlp) : launch(lp)) : band ? launch(bp) : launch(fp));
+    info->kernel_path = 0; info->frames_per_tile = fpt; info->grid_fwd = (int)grid;
+    info->fb_blocks = tb->n_entries; info->fb_blocks_dense = tb->n_dense;
+    info->lds_bytes = dmel::forward_lds_bytes(N, mode);
     const bool spec_only = mode == dmel::kSpec || mode == dmel::kSpecTrain;
-    pl->info.contraction = spec_only ? -1 : (dmel::mode_wlc(mode) ? 1 : (mode == dmel::kTrainH ? 2 : 0));
-    pl->info.wl_steps = dmel::mode_wlc(mode) ? 4 * fp.wl_total4 : 0;
+    info->contraction = spec_only ? -1 : (dmel::mode_wlc(mode) ? 1 : (mode == dmel::kTrainH ? 2 : 0));
+    info->wl_steps = dmel::mode_wlc(mode) ? 4 * fp.wl_total4 : 0;
+    return DMEL_OK;
+}
+
+// One launch (plus, when needed, the prep kernel in front of it) of the forward `c` for a given n_fft.  `lam`: where lambd comes from and whether the kernels check
+// it against N (dmel_kernels.h); `sc`: this call's scratch; `sums_done`: shared by the launches of one call.  The plan mutex is held by the caller.
+dmel_status launch_forward_n(dmel_plan* pl, int N, const dmel::LamArgs& lam, const FwdCall& c, const Scratch& sc, hipStream_t s, bool* sums_done)
+{
+    if (N < 1) return fail(DMEL_ERR_UNSUPPORTED, "n_fft = " + std::to_string(N));
+    const bool pow2 = (N & (N - 1)) == 0;
+    const bool big = !pow2 || N > dmel::kMaxNfft;
+    // per-clip lengths (dmel_fwd_len_kernel; multi-window: dmel_fwd_multi_len_kernel / dmel_fwd_band_len_kernel): the fused kernel's range, the HTK bank
+    if (c.lengths && (big || N < dmel::kMinFastNfft || c.spec_out || c.win_half))
+        return fail(DMEL_ERR_UNSUPPORTED, "per-clip lengths run the fused kernel only: n_fft 32 ... 16384 (n_fft = " + std::to_string(N) + ")");
+    if (c.multi() && (big || N < dmel::kMinFastNfft || c.spec_out))
+        return fail(DMEL_ERR_UNSUPPORTED, "the multi-window layer runs n_fft 32 ... 16384 only (n_fft = " + std::to_string(N) + ")");
+    if (c.spec_out && (big || N < dmel::kMinFastNfft || c.mode != dmel::kTrain))
+        return fail(DMEL_ERR_UNSUPPORTED, "the spectrogram is saved by the fused training kernel only (power-of-two n_fft from 32 to 16384, tangent requested)");
+    if (big && (N & 1)) return fail(DMEL_ERR_UNSUPPORTED, "n_fft = " + std::to_string(N) + " is odd");
+    NfftTables* tb = nullptr;
+    dmel_status st = build_tables(pl, N, &tb);
+    if (st != DMEL_OK) return st;
+    dmel_plan_info info{};
+    info.n_fft = N; info.n_freqs = tb->F; info.n_time = pl->T;
+    if (big) {
+        if ((st = forward_big(pl, tb, lam, c, sc, s, sums_done, &info)) == DMEL_OK) pl->info = info;
+        return st;
+    }
+    // The fused kernel builds its own window table (n_fft <= 4096) and, for clips up to 32768 samples, its own clip mean; the prep kernel only runs for
+    // what is left: partial sums of long clips, the window table of n_fft 8192 / 16384, and everything the direct-DFT kernel (n_fft < 32) needs.
+    const bool fast = N >= dmel::kMinFastNfft && N <= dmel::kMaxFastNfft;
+    const bool kernel_mean = fast && pl->cfg.n_points <= 32768;
+    const bool need_sums = c.remove_dc && !kernel_mean && !*sums_done;                  // the launches of one group share the sums
+    const bool need_window = !fast || !dmel::forward_window_in_lds(N);
+    const size_t m0 = prof_mark(pl, s);
+    if (need_sums || need_window) {
+        if ((st = forward_prep(pl, N, sc.win, lam, c, sc, s, (need_sums ? kPrepSums : 0u) | (need_window ? kPrepWindow : 0u))) != DMEL_OK) return st;
+        if (need_sums) *sums_done = true;
+    }
+    const size_t m1 = prof_mark(pl, s);
+    if (need_sums || need_window) prof_span(pl, m0, m1, 0);
+    pl->info.n_fft = info.n_fft; pl->info.n_freqs = info.n_freqs; pl->info.n_time = info.n_time;      // (these three also when the launch below is refused)
+    st = N < dmel::kMinFastNfft ? forward_naive(pl, tb, lam, c, sc, s, &info) : forward_fused(pl, tb, lam, c, sc, s, kernel_mean, &info);
+    if (st != DMEL_OK) return st;
+    prof_span(pl, m1, prof_mark(pl, s), 1);
+    pl->info = info;
+    return DMEL_OK;
+}
+
+// the launches of one forward call, in order; dmel_plan_get_info then describes the first, the one the host expected to do the work
+template <class F> dmel_status issue_group(dmel_plan* pl, int nl, F&& launch)
+{
+    dmel_plan_info primary_info = pl->info;
+    for (int i = 0; i < nl; ++i) {
+        const dmel_status st = launch(i);
+        if (st != DMEL_OK) return st;
+        if (i == 0) primary_info = pl->info;
+    }
+    pl->info = primary_info;
     return DMEL_OK;
 }
 
@@ -1059,123 +1126,163 @@ dmel_status check_forward_args(dmel_plan* pl, const float* x, int batch, const v
     return check_device(pl);
 }
 
-// lambd by value (the host has read it, as time_frequency.py:39 does): one launch, plan-owned scratch unless given.
-// The plan mutex is held by the caller.
+// lambd by value (the host has read it, as time_frequency.py:39 does): one launch, plan-owned scratch unless given; the plan mutex is held by the caller.
 // lambd_dev != nullptr: the kernels read lambd from the device instead (no host read: capturable); the transform length must then
 // be given (n_fft_override: the lengths that do not depend on lambd -- optimized=False branches, the spectrogram layer).
-dmel_status run_forward_nolock(dmel_plan* pl, const float* x, int batch, float lambd, unsigned flags, double eps,
-                        float* out, float* tangent, int mode, int remove_dc, void* stream,
-                        int n_fft_override = 0, int win_half = 0, void* scratch = nullptr, const float* lambd_dev = nullptr,
-                        const int32_t* lengths = nullptr)
+dmel_status run_forward_nolock(dmel_plan* pl, const FwdCall& c, float lambd, const float* lambd_dev, int n_fft_override, void* scratch, void* stream)
 {
-    dmel_status st = check_forward_args(pl, x, batch, out);
+    dmel_status st = check_forward_args(pl, c.x, c.batch, c.out);
     if (st != DMEL_OK) return st;
-    if (batch == 0) return DMEL_OK;
+    if (c.batch == 0) return DMEL_OK;
     if (lambd_dev && n_fft_override <= 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd on the device needs an explicit n_fft");
     if (!lambd_dev && !std::isfinite(lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int N = n_fft_override > 0 ? n_fft_override : dmel_n_fft(lambd);
     Scratch sc;
-    if (scratch) sc = carve(scratch);
-    else {
-        if ((st = order_after_last_stream(pl, s)) != DMEL_OK) return st;
-        if ((st = ensure_own_scratch(pl, batch, s, &sc)) != DMEL_OK) return st;
-    }
+    if ((st = select_scratch(pl, scratch, c.batch, s, &sc)) != DMEL_OK) return st;
     dmel::LamArgs lam{};
     lam.dev = lambd_dev; lam.val = lambd_dev ? 0.f : lambd; lam.n_expected = 0;      // N was derived from this very value (or given explicitly)
     lam.role = dmel::kLamFirst | dmel::kLamLast;
     lam.dot_counter = scratch ? sc.counter : nullptr;            // plan-owned counters are zeroed at allocation and reset themselves
     bool sums_done = false;
-    return launch_forward_n(pl, x, batch, N, lam, flags, eps, out, tangent, mode, remove_dc, sc, s, win_half, &sums_done, nullptr, nullptr, lengths);
+    return launch_forward_n(pl, N, lam, c, sc, s, &sums_done);
 }
 
-dmel_status run_forward(dmel_plan* pl, const float* x, int batch, float lambd, unsigned flags, double eps,
-                        float* out, float* tangent, int mode, int remove_dc, void* stream,
-                        int n_fft_override = 0, int win_half = 0, void* scratch = nullptr, const float* lambd_dev = nullptr,
-                        const int32_t* lengths = nullptr)
+dmel_status run_forward(dmel_plan* pl, const FwdCall& c, float lambd, const float* lambd_dev, int n_fft_override, void* scratch, void* stream)
 {
     if (!pl) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
     std::lock_guard<std::mutex> lock(pl->mu);
-    return run_forward_nolock(pl, x, batch, lambd, flags, eps, out, tangent, mode, remove_dc, stream, n_fft_override, win_half, scratch, lambd_dev,
-                              lengths);
+    return run_forward_nolock(pl, c, lambd, lambd_dev, n_fft_override, scratch, stream);
 }
 
-// ---- device-resident lambd ---------------------------------------------------------------------------------------------
-// (templates: the plan's own picture and the multi-window layer's per-channel ones, dmel_plan::LamTrack, have the same fields)
-template <class P> void lam_reset(P* pl)
-{
-    pl->lam_known = false; pl->n_obs = 0; pl->lam_rate = 0.f; pl->seq_seen = pl->issued; pl->seq_floor = pl->issued + 1;
-}
+// ---- device-resident lambd: the host steps around the rule of dmel_lamtrack.h ------------------------------------------------------
+static_assert(dmel::lamtrack::kMaxGuardNfft == dmel::kMaxBigFft, "dmel_lamtrack.h stops guarding where the HIP path stops");
+namespace lt = dmel::lamtrack;
 
-// The launch choice as a pure function (also exported: dmel_decide_launch): n_fft from lambd, and the neighbours within reach
-// of a boundary when lambd may move by `rate` per forward for `stale` forwards before anybody looks again (factor 2 of margin)
-void decide_launch(float lambd, float rate, float stale, int* n_fft, int* guards)
-{
-    const float a = std::fabs(lambd);
-    const int N = dmel_n_fft(lambd);
-    int g = 0;
-    const float reach = 2.0f * rate * stale + 1e-5f * a;
-    if ((a - reach) * 6.0f < (float)(N / 2 + 1)) g |= 1;
-    if ((a + reach) * 6.0f >= (float)N + 1.0f) g |= 2;
-    if (2 * N > dmel::kMaxBigFft) g &= ~2;
-    if (N < 2) g &= ~1;
-    *n_fft = N; *guards = g;
-}
+// K tracked values: their pictures and pinned words -- value c has its ring of kLamRing reports and, behind it, its sticky error word at words + c
+// kLamMultiStride.  The scalar layer is K = 1 over dmel_plan::track / host_words, the multi-window layer its channels over multi / multi_words
+struct Tracked {
+    dmel::LamTrack* tr; unsigned long long* words; int K; bool multi;       // multi: the multi-window layer's channels (their texts, their n_fft range)
+    unsigned long long* ring(int c) const { return words + (size_t)c * dmel::kLamMultiStride; }
+};
 
-// which n_fft the next dmel_forward_dev launches for and which neighbours it guards (bit 0: n_fft / 2, bit 1: 2 n_fft), from
-// the host's current picture: both neighbours while the drift per call is unknown, on request, and under a graph capture
-// nobody manages; otherwise only the ones within reach of a boundary before the host would notice
-template <class P> void lam_decide_track(const dmel_plan* pl, const P* tr, bool capturing, int* n_fft, int* guards)
+// forwards that no launch covered (NaN on the device): every sticky word is read and cleared, its value started over; the first is returned for the caller's text
+struct LamError { int channel = -1; float seen = 0.f, lam = 0.f; unsigned seq = 0; };
+LamError take_errors(const Tracked& t)
 {
-    const int N = dmel_n_fft(tr->lam_seen);
-    int g = 0;
-    if (pl->guard_mode == 1 || (capturing && pl->guard_mode != 3 && pl->guard_mode != 2)) g = 3;
-    else if (pl->guard_mode == 0 || pl->guard_mode == 3) {
-        if (tr->n_obs < 2) g = 3;
-        else {
-            const float stale = (float)(tr->issued - tr->seq_seen) + 2.0f + (capturing ? (float)pl->max_ahead : 0.f);
-            int n2 = 0;
-            decide_launch(tr->lam_seen, tr->lam_rate, stale, &n2, &g);
-        }
+    LamError e;
+    for (int c = 0; c < t.K; ++c) {
+        float lam = 0.f; unsigned seq = 0;
+        if (!lt::take_error(t.ring(c), dmel::kLamRing, &seq, &lam)) continue;
+        const float seen = t.tr[c].lam_seen;
+        lt::reset(&t.tr[c]);
+        if (e.channel < 0) { e.channel = c; e.seen = seen; e.lam = lam; e.seq = seq; }
     }
-    if (2 * N > dmel::kMaxBigFft) g &= ~2;
-    if (N < 2) g &= ~1;
-    *n_fft = N; *guards = g;
+    return e;
 }
 
-void lam_decide(const dmel_plan* pl, bool capturing, int* n_fft, int* guards)
+bool multi_in_range(int n) { return n >= dmel::kMinFastNfft && n <= dmel::kMaxFastNfft; }
+
+// the multi-window layer's K host values: finite, n_fft inside the fused kernel's range
+dmel_status check_lambd_multi(const float* lam, int channels)
+{
+    for (int c = 0; c < channels; ++c) {
+        if (!std::isfinite(lam[c])) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd of channel " + std::to_string(c) + " is not finite");
+        const int n = dmel_n_fft(lam[c]);
+        if (!multi_in_range(n))
+            return fail(DMEL_ERR_UNSUPPORTED, "channel " + std::to_string(c) + ": lambd = " + std::to_string(lam[c]) + " gives n_fft " +
+                        std::to_string(n) + ", the multi-window layer serves 32 ... 16384");
+    }
+    return DMEL_OK;
+}
+
+// Fold the latest reports into every picture; then the cold start if one of them is empty -- the one blocking read of the K values (the reference does one
+// per sample, time_frequency.py:39) -- and otherwise the bounded run-ahead: the picture the launches are chosen from is at most max_ahead calls old
+dmel_status settle_pictures(dmel_plan* pl, const Tracked& t, const float* lambd_dev, hipStream_t s, bool capturing)
+{
+    bool cold = false;
+    for (int c = 0; c < t.K; ++c) { lt::observe(&t.tr[c], t.ring(c), dmel::kLamRing); cold |= !t.tr[c].lam_known; }
+    if (cold) {
+        if (capturing) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(t.multi ? "dmel_forward_multi_dev" : "dmel_forward_dev") + ": run the layer once eagerly before capturing it into a graph");
+        float lam[dmel::kMaxChannels];
+        DMEL_HIP(hipMemcpyAsync(lam, lambd_dev, t.K * sizeof(float), hipMemcpyDeviceToHost, s));
+        DMEL_HIP(hipStreamSynchronize(s));
+        // (the scalar layer follows a finite lambd to any n_fft; a channel of the multi-window layer must stay in the fused kernel's range)
+        if (!t.multi && !std::isfinite(lam[0])) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
+        const dmel_status st = t.multi ? check_lambd_multi(lam, t.K) : DMEL_OK;
+        if (st != DMEL_OK) return st;
+        for (int c = 0; c < t.K; ++c)
+            if (!t.tr[c].lam_known) lt::cold_start(&t.tr[c], t.ring(c), dmel::kLamRing, lam[c]);
+    } else if (!capturing && pl->max_ahead > 0) {
+        for (int c = 0; c < t.K; ++c) {
+            dmel::LamTrack& tr = t.tr[c];
+            for (long spins = 0; tr.issued - tr.seq_seen > (unsigned)pl->max_ahead && spins < 200000000L; ++spins) {
+                if (!lt::observe(&tr, t.ring(c), dmel::kLamRing) && (spins & 1023) == 1023 && hipStreamQuery(s) == hipSuccess) { lt::observe(&tr, t.ring(c), dmel::kLamRing); break; }
+            }
+        }
+        (void)hipGetLastError();
+    }
+    return DMEL_OK;
+}
+
+// tables of the sizes about to be launched and of their neighbours inside [lo, hi] exist before they are needed: building allocates and copies (no capture)
+dmel_status prebuild_tables(dmel_plan* pl, const int* ns, int nl, int lo, int hi)
+{
+    NfftTables* tb = nullptr;
+    for (int i = 0; i < nl; ++i)
+        for (int n : {ns[i], 2 * ns[i], ns[i] / 2}) {
+            const dmel_status st = (n >= lo && n <= hi) ? build_tables(pl, n, &tb) : DMEL_OK;
+            if (st != DMEL_OK) return st;
+        }
+    return DMEL_OK;
+}
+
+// a captured forward executes when (and as often as) its graph is replayed: only eager calls draw an execution number now
+void count_call(dmel_plan* pl, const Tracked& t, bool capturing)
+{
+    ++pl->calls;
+    for (int c = 0; !capturing && c < t.K; ++c) ++t.tr[c].issued;
+}
+
+// where a tracked forward's kernels find lambd, their execution counter(s) and the words they report into
+dmel::LamArgs tracked_lam_args(const float* lambd_dev, unsigned* exec_counter, unsigned long long* words, const Scratch& sc)
+{
+    dmel::LamArgs lam{};
+    lam.dev = lambd_dev; lam.exec_counter = exec_counter; lam.handled = sc.handled; lam.host_seen = words; lam.host_error = words + dmel::kLamRing;
+    return lam;
+}
+
+// the scalar layer's launch choice: the caller's (dmel_plan_force_launch; the multi-window layer has none) or the tracker's
+void decide_scalar(const dmel_plan* pl, bool capturing, int* n_fft, int* guards)
 {
     if (pl->forced_n_fft > 0) { *n_fft = pl->forced_n_fft; *guards = pl->forced_guards; return; }
-    lam_decide_track(pl, pl, capturing, n_fft, guards);
+    lt::decide(pl->track, pl->guard_mode, pl->max_ahead, capturing, n_fft, guards);
 }
 
-// fold the kernels' latest report into the host's picture; returns false if nothing new.  The ring is scanned for the
-// highest execution number past the last one seen (and past the last reset): whichever forward executed last -- an eager
-// call or a replay of a captured one -- is what the picture follows.
-template <class P> bool lam_observe_ring(P* pl, const unsigned long long* ring)
+// The launches of a multi-window call: one entry per distinct n_fft, ascending, each with the mask of the channels that need it
+struct LaunchList { int ns[3 * dmel::kMaxChannels] = {}; uint32_t mask[3 * dmel::kMaxChannels] = {}; int nl = 0; };
+// channel c needs n[c] and, where `guards` says so (bit 0: n / 2, bit 1: 2 n; nullptr: none), the neighbours that lie inside [lo, hi]
+LaunchList group_by_nfft(const int* n, const int* guards, int channels, int lo, int hi)
 {
-    bool any = false;
-    unsigned best_seq = 0; unsigned best_bits = 0;
-    for (unsigned i = 0; i < dmel::kLamRing; ++i) {
-        const unsigned long long w = __atomic_load_n(&ring[i], __ATOMIC_RELAXED);
-        const unsigned seq = (unsigned)(w >> 32);
-        if (seq == 0 || (int)(seq - pl->seq_floor) < 0) continue;                       // empty, or older than the last reset
-        if (pl->lam_known ? (int)(seq - pl->seq_seen) <= 0 : false) continue;           // not newer than what is known
-        if (!any || (int)(seq - best_seq) > 0) { best_seq = seq; best_bits = (unsigned)w; any = true; }
+    std::map<int, uint32_t> u;
+    for (int c = 0; c < channels; ++c) {
+        u[n[c]] |= 1u << c;
+        const int g = guards ? guards[c] : 0;
+        if ((g & 2) && 2 * n[c] >= lo && 2 * n[c] <= hi) u[2 * n[c]] |= 1u << c;
+        if ((g & 1) && n[c] / 2 >= lo && n[c] / 2 <= hi) u[n[c] / 2] |= 1u << c;
     }
-    if (!any) return false;
-    float lam; std::memcpy(&lam, &best_bits, 4);
-    if (pl->lam_known && pl->n_obs >= 1) {
-        const unsigned dseq = best_seq - pl->seq_seen;
-        const float r = std::fabs(lam - pl->lam_seen) / (float)(dseq ? dseq : 1);
-        pl->lam_rate = std::max(0.98f * pl->lam_rate, r);
-    }
-    pl->lam_seen = lam; pl->seq_seen = best_seq; pl->lam_known = true; ++pl->n_obs;
-    if ((int)(best_seq - pl->issued) > 0) pl->issued = best_seq;                      // replays executed forwards the host never counted
-    return true;
+    LaunchList ll;
+    for (const auto& kv : u) { ll.ns[ll.nl] = kv.first; ll.mask[ll.nl] = kv.second; ++ll.nl; }
+    return ll;
 }
 
-bool lam_observe(dmel_plan* pl) { return lam_observe_ring(pl, pl->host_words); }
+// the launches K host values ask for: each channel's own n_fft
+LaunchList group_host_values(const float* lambd, int channels)
+{
+    int n[dmel::kMaxChannels];
+    for (int c = 0; c < channels; ++c) n[c] = dmel_n_fft(lambd[c]);
+    return group_by_nfft(n, nullptr, channels, 0, 0);
+}
 
 std::mutex g_plans_mu;             // guards dmel_plan::refs and g_live_plans
 std::unordered_set<const dmel_plan*> g_live_plans;     // every plan between dmel_plan_create and its last release (dmel_plan_is_live)
@@ -1188,19 +1295,7 @@ int32_t dmel_abi_version(void) { return DMEL_ABI_VERSION; }
 
 const char* dmel_last_error(void) { return g_err.c_str(); }
 
-int32_t dmel_n_fft(float lambd)
-{
-    const float a = std::fabs(lambd);       // models.py:38
-    const float prod = a * 6.0f;            // time_frequency.py:39, fp32 tensor product
-    if (!(prod < 9.0e15f)) return 0x40000000;
-    long long x = (long long)prod;          // time_frequency.py:61 int(): truncation
-    long long v = x - 1;
-    int bits = 0;
-    if (v < 0) bits = 1;                    // python: (-1).bit_length() == 1
-    else while (v > 0) { ++bits; v >>= 1; }
-    if (bits > 30) return 0x40000000;
-    return (int32_t)(1LL << bits);          // time_frequency.py:62
-}
+int32_t dmel_n_fft(float lambd) { return lt::n_fft(lambd); }
 
 dmel_status dmel_window_host(float lambd, int32_t n_fft, int32_t normalize, float* window, float* dwindow)
 {
@@ -1445,14 +1540,13 @@ dmel_status dmel_forward_scratch(dmel_plan* plan, const float* x, int32_t batch,
 {
     if (flags & DMEL_FLAG_X_INDIRECT) return fail(DMEL_ERR_INVALID_ARGUMENT, "DMEL_FLAG_X_INDIRECT belongs to dmel_forward_dev");
     { dmel_status sa = check_store_aligned("dmel_forward", {{"out", out}, {"tangent", tangent}, {"scratch", scratch}}); if (sa != DMEL_OK) return sa; }
+    FwdCall c = mel_call(x, batch, flags, eps, out, tangent);
     if (flags & DMEL_FLAG_FULL_WINDOW) {
         if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
-        const int L = plan->cfg.n_points;
-        return run_forward(plan, x, batch, lambd, flags & ~DMEL_FLAG_FULL_WINDOW, eps, static_cast<float*>(out), tangent,
-                           tangent ? dmel::kTrain : dmel::kInfer, 1, stream, 2 * L, 1, scratch);
+        c.flags = flags & ~DMEL_FLAG_FULL_WINDOW; c.win_half = 1;
+        return run_forward(plan, c, lambd, nullptr, 2 * plan->cfg.n_points, scratch, stream);
     }
-    return run_forward(plan, x, batch, lambd, flags, eps, static_cast<float*>(out), tangent,
-                       tangent ? dmel::kTrain : dmel::kInfer, /*remove_dc=*/1, stream, 0, 0, scratch);
+    return run_forward(plan, c, lambd, nullptr, 0, scratch, stream);
 }
 
 dmel_status dmel_forward(dmel_plan* plan, const float* x, int32_t batch, float lambd, uint32_t flags,
@@ -1474,107 +1568,60 @@ size_t dmel_scratch_bytes(const dmel_plan* plan, int32_t batch)
     return scratch_bytes(plan, batch);
 }
 
-// dmel_forward_dev and dmel_forward_dev_lengths (lengths != nullptr: the launches stay inside the fused kernel's range)
-static dmel_status forward_dev_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, uint32_t flags,
-                                    double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* lengths)
+// dmel_forward_dev and dmel_forward_dev_lengths (c.lengths: the launches stay in the fused kernel's range): K = 1 of the host steps dmel_forward_multi_dev runs
+static dmel_status forward_dev_impl(dmel_plan* plan, const FwdCall& c, const float* lambd_dev, void* scratch, void* stream)
 {
-    dmel_status st = check_forward_args(plan, x, batch, out);
+    dmel_status st = check_forward_args(plan, c.x, c.batch, c.out);
     if (st != DMEL_OK) return st;
-    if ((st = check_store_aligned(lengths ? "dmel_forward_dev_lengths" : "dmel_forward_dev", {{"out", out}, {"tangent", tangent}, {"scratch", scratch}})) != DMEL_OK) return st;
+    if ((st = check_store_aligned(c.lengths ? "dmel_forward_dev_lengths" : "dmel_forward_dev", {{"out", c.out}, {"tangent", c.tangent}, {"scratch", scratch}})) != DMEL_OK) return st;
     if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
-    if (flags & DMEL_FLAG_FULL_WINDOW)
+    if (c.flags & DMEL_FLAG_FULL_WINDOW)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev: DMEL_FLAG_FULL_WINDOW has a fixed n_fft, use dmel_forward");
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool capturing = is_capturing(s);
-
-    // a forward that no launch covered: its outputs are NaN on the device; tell the caller once and start over
-    const unsigned long long err = __atomic_load_n(&plan->host_words[dmel::kLamRing], __ATOMIC_RELAXED);
-    if (err != 0) {
-        float lam; const unsigned bits = (unsigned)err; std::memcpy(&lam, &bits, 4);
-        __atomic_store_n(&plan->host_words[dmel::kLamRing], 0ull, __ATOMIC_RELAXED);
-        const float seen = plan->lam_seen;
-        lam_reset(plan);
+    const Tracked t{&plan->track, plan->host_words, 1, false};
+    const LamError e = take_errors(t);
+    if (e.channel >= 0)
         return fail(DMEL_ERR_LAMBD_TRACKING,
-                    "lambd moved from " + std::to_string(seen) + " (n_fft " + std::to_string(dmel_n_fft(seen)) + ") to " +
-                    std::to_string(lam) + " (n_fft " + std::to_string(dmel_n_fft(lam)) + ") faster than the sync-free forward "
-                    "tracks it: call " + std::to_string((unsigned)(err >> 32)) + " produced NaN.  Tracking has been reset; use "
+                    "lambd moved from " + std::to_string(e.seen) + " (n_fft " + std::to_string(dmel_n_fft(e.seen)) + ") to " +
+                    std::to_string(e.lam) + " (n_fft " + std::to_string(dmel_n_fft(e.lam)) + ") faster than the sync-free forward "
+                    "tracks it: call " + std::to_string(e.seq) + " produced NaN.  Tracking has been reset; use "
                     "dmel_forward (host read per call), dmel_plan_set_tracking(plan, max_ahead, 1) or a smaller run-ahead");
-    }
-    if (batch == 0) return DMEL_OK;
-    lam_observe(plan);
-    if (!plan->lam_known) {
-        // cold start: the one blocking read (the reference does one per sample, time_frequency.py:39)
-        if (capturing) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev: run the layer once eagerly before capturing it into a graph");
-        float lam = 0.f;
-        DMEL_HIP(hipMemcpyAsync(&lam, lambd_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-        DMEL_HIP(hipStreamSynchronize(s));
-        if (!std::isfinite(lam)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
-        // the stream is idle: every report of earlier forwards on it is in the ring; whatever executed without the host
-        // counting it (replays of captured forwards) is caught up with here
-        for (unsigned i = 0; i < dmel::kLamRing; ++i) {
-            const unsigned q = (unsigned)(__atomic_load_n(&plan->host_words[i], __ATOMIC_RELAXED) >> 32);
-            if (q != 0 && (int)(q - plan->issued) > 0) plan->issued = q;
-        }
-        plan->lam_seen = lam; plan->seq_seen = plan->issued; plan->lam_known = true; plan->n_obs = 0; plan->lam_rate = 0.f;
-    } else if (!capturing && plan->max_ahead > 0) {
-        // bounded run-ahead: the picture of lambd the launches are chosen from is at most max_ahead calls old
-        for (long spins = 0; plan->issued - plan->seq_seen > (unsigned)plan->max_ahead && spins < 200000000L; ++spins) {
-            if (!lam_observe(plan) && (spins & 1023) == 1023 && hipStreamQuery(s) == hipSuccess) { lam_observe(plan); break; }
-        }
-        (void)hipGetLastError();
-    }
+    if (c.batch == 0) return DMEL_OK;
+    if ((st = settle_pictures(plan, t, lambd_dev, s, capturing)) != DMEL_OK) return st;
     int N = 0, guards = 0;
-    lam_decide(plan, capturing, &N, &guards);
-    if (lengths) {
-        // clamped to the range the fused kernel serves, as dmel_forward_multi_dev: a forward whose lambd left it is poisoned and reported
+    decide_scalar(plan, capturing, &N, &guards);
+    if (c.lengths) {
+        // clamped to the fused kernel's range, as dmel_forward_multi_dev: a forward whose lambd left it is poisoned and reported (without lengths: every length)
         N = std::min(std::max(N, dmel::kMinFastNfft), dmel::kMaxFastNfft);
         if (2 * N > dmel::kMaxFastNfft) guards &= ~2;
         if (N / 2 < dmel::kMinFastNfft) guards &= ~1;
     }
-    // tables of the neighbouring sizes exist before they are needed: building them allocates and copies (not allowed
-    // under capture, and a stall at the moment of a crossing otherwise)
-    if (!capturing) {
-        NfftTables* tb = nullptr;
-        for (int n : {N, 2 * N, N / 2})
-            if (n >= 1 && n <= dmel::kMaxBigFft && (st = build_tables(plan, n, &tb)) != DMEL_OK) return st;
-    }
+    if (!capturing && (st = prebuild_tables(plan, &N, 1, 1, dmel::kMaxBigFft)) != DMEL_OK) return st;     // (N and both neighbours whatever the guards; the multi-window layer: inside 32 ... 16384)
     int cand[3], nc = 0;
     cand[nc++] = N;
     if (guards & 2) cand[nc++] = 2 * N;
     if (guards & 1) cand[nc++] = N / 2;
-    plan->last_guards = guards;
+    plan->track.last_guards = guards;       // (the launches issued; the multi-window layer records a channel's guards before its range cuts them)
 
     Scratch sc;
-    if (scratch) sc = carve(scratch);
-    else {
-        if ((st = order_after_last_stream(plan, s)) != DMEL_OK) return st;
-        if ((st = ensure_own_scratch(plan, batch, s, &sc)) != DMEL_OK) return st;
-    }
-    ++plan->calls;
-    if (!capturing) ++plan->issued;          // a captured forward executes when (and as often as) its graph is replayed
+    if ((st = select_scratch(plan, scratch, c.batch, s, &sc)) != DMEL_OK) return st;
+    count_call(plan, t, capturing);
     bool sums_done = false;
-    dmel_plan_info primary_info = plan->info;
-    for (int i = 0; i < nc; ++i) {
-        dmel::LamArgs lam{};
-        lam.dev = lambd_dev; lam.val = 0.f; lam.n_expected = cand[i];
+    return issue_group(plan, nc, [&](int i) {
+        dmel::LamArgs lam = tracked_lam_args(lambd_dev, plan->exec_counter, plan->host_words, sc);
+        lam.n_expected = cand[i];
         lam.role = (i == 0 ? dmel::kLamFirst : 0u) | (i == nc - 1 ? dmel::kLamLast : 0u);
-        lam.exec_counter = plan->exec_counter; lam.handled = sc.handled;
-        lam.host_seen = &plan->host_words[0]; lam.host_error = &plan->host_words[dmel::kLamRing];
         lam.dot_counter = scratch ? sc.counter : nullptr;
-        st = launch_forward_n(plan, x, batch, cand[i], lam, flags, eps, static_cast<float*>(out), tangent,
-                              tangent ? dmel::kTrain : dmel::kInfer, /*remove_dc=*/1, sc, s, 0, &sums_done, nullptr, nullptr, lengths);
-        if (st != DMEL_OK) return st;
-        if (i == 0) primary_info = plan->info;
-    }
-    plan->info = primary_info;        // dmel_plan_get_info describes the launch the host expected to do the work
-    return DMEL_OK;
+        return launch_forward_n(plan, cand[i], lam, c, sc, s, &sums_done);
+    });
 }
 
 dmel_status dmel_forward_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, uint32_t flags,
                              double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    return forward_dev_impl(plan, x, batch, lambd_dev, flags, eps, out, tangent, scratch, stream, nullptr);
+    return forward_dev_impl(plan, mel_call(x, batch, flags, eps, out, tangent), lambd_dev, scratch, stream);
 }
 
 // the flags the per-clip-lengths forwards take
@@ -1590,8 +1637,9 @@ dmel_status dmel_forward_lengths(dmel_plan* plan, const float* x, const int32_t*
     const int N = dmel_n_fft(lambd);
     if (N < dmel::kMinFastNfft || N > dmel::kMaxFastNfft)
         return fail(DMEL_ERR_UNSUPPORTED, "per-clip lengths run n_fft 32 ... 16384; lambd = " + std::to_string(lambd) + " gives n_fft " + std::to_string(N));
-    return run_forward(plan, x, batch, lambd, flags, eps, static_cast<float*>(out), tangent, tangent ? dmel::kTrain : dmel::kInfer,
-                       /*remove_dc=*/1, stream, 0, 0, scratch, nullptr, lengths);
+    FwdCall c = mel_call(x, batch, flags, eps, out, tangent);
+    c.lengths = lengths;
+    return run_forward(plan, c, lambd, nullptr, 0, scratch, stream);
 }
 
 dmel_status dmel_forward_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
@@ -1600,118 +1648,75 @@ dmel_status dmel_forward_dev_lengths(dmel_plan* plan, const float* x, const int3
     if (!plan || !x || !lengths || !out || !lambd_dev)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_lengths: plan / x / lengths / lambd_dev / out is NULL");
     if (flags & ~kLengthsFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_lengths: flags other than LOG, OUT_BF16, X_INDIRECT");
-    return forward_dev_impl(plan, x, batch, lambd_dev, flags, eps, out, tangent, scratch, stream, lengths);
+    FwdCall c = mel_call(x, batch, flags, eps, out, tangent);
+    c.lengths = lengths;
+    return forward_dev_impl(plan, c, lambd_dev, scratch, stream);
 }
 
 dmel_status dmel_forward_dev_fixed(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft,
                                    uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    dmel_status st = check_forward_args(plan, x, batch, out);
-    if (st != DMEL_OK) return st;
-    if ((st = check_store_aligned("dmel_forward_dev_fixed", {{"out", out}, {"tangent", tangent}, {"scratch", scratch}})) != DMEL_OK) return st;
-    if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
-    if (flags & DMEL_FLAG_X_INDIRECT) return fail(DMEL_ERR_INVALID_ARGUMENT, "DMEL_FLAG_X_INDIRECT belongs to dmel_forward_dev");
-    if (flags & DMEL_FLAG_FULL_WINDOW) {
-        // optimized=False (time_frequency.py:41,51): window = the clip, n_fft = 2 n_points whatever lambd is -- nothing to check on
-        // the device, nothing for the host to read: lambd only shapes the window, which the kernels build from the device value
-        return run_forward(plan, x, batch, 0.f, flags & ~DMEL_FLAG_FULL_WINDOW, eps, static_cast<float*>(out), tangent,
-                           tangent ? dmel::kTrain : dmel::kInfer, 1, stream, 2 * plan->cfg.n_points, 1, scratch, lambd_dev);
-    }
-    if (n_fft < 1 || n_fft > dmel::kMaxNfft || (n_fft & (n_fft - 1)))
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be a power of two in [1, 16384]");
-    std::lock_guard<std::mutex> lock(plan->mu);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const unsigned long long err = __atomic_load_n(&plan->host_words[dmel::kLamRing], __ATOMIC_RELAXED);
-    if (err != 0) {
-        float lam; const unsigned bits = (unsigned)err; std::memcpy(&lam, &bits, 4);
-        __atomic_store_n(&plan->host_words[dmel::kLamRing], 0ull, __ATOMIC_RELAXED);
-        lam_reset(plan);
-        return fail(DMEL_ERR_LAMBD_TRACKING,
-                    "lambd = " + std::to_string(lam) + " asks for n_fft " + std::to_string(dmel_n_fft(lam)) + " but the forward was issued for the "
-                    "fixed n_fft " + std::to_string(n_fft) + " (a learnable filterbank is tied to one n_fft): call " +
-                    std::to_string((unsigned)(err >> 32)) + " produced NaN");
-    }
-    if (batch == 0) return DMEL_OK;
-    Scratch sc;
-    if (scratch) sc = carve(scratch);
-    else {
-        if ((st = order_after_last_stream(plan, s)) != DMEL_OK) return st;
-        if ((st = ensure_own_scratch(plan, batch, s, &sc)) != DMEL_OK) return st;
-    }
-    dmel::LamArgs lam{};
-    lam.dev = lambd_dev; lam.val = 0.f; lam.n_expected = n_fft;
-    lam.role = dmel::kLamFirst | dmel::kLamLast;
-    ++plan->calls;
-    if (!is_capturing(s)) ++plan->issued;
-    lam.exec_counter = plan->exec_counter; lam.handled = sc.handled;
-    lam.host_seen = &plan->host_words[0]; lam.host_error = &plan->host_words[dmel::kLamRing];
-    lam.dot_counter = scratch ? sc.counter : nullptr;
-    plan->last_guards = 0;
-    bool sums_done = false;
-    return launch_forward_n(plan, x, batch, n_fft, lam, flags, eps, static_cast<float*>(out), tangent,
-                            tangent ? dmel::kTrain : dmel::kInfer, /*remove_dc=*/1, sc, s, 0, &sums_done);
+    return dmel_forward_dev_fixed_spec(plan, x, batch, lambd_dev, n_fft, flags, eps, out, tangent, nullptr, scratch, stream);
 }
 
+// spec == nullptr is dmel_forward_dev_fixed: its name in the messages, its wider range and its refusal of DMEL_FLAG_X_INDIRECT, which this form never had
 dmel_status dmel_forward_dev_fixed_spec(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft,
                                         uint32_t flags, double eps, void* out, float* tangent, float* spec, void* scratch, void* stream)
 {
-    if (!spec) return dmel_forward_dev_fixed(plan, x, batch, lambd_dev, n_fft, flags, eps, out, tangent, scratch, stream);
     dmel_status st = check_forward_args(plan, x, batch, out);
     if (st != DMEL_OK) return st;
-    if ((st = check_store_aligned("dmel_forward_dev_fixed_spec", {{"out", out}, {"tangent", tangent}, {"spec", spec}, {"scratch", scratch}})) != DMEL_OK) return st;
-    if (!lambd_dev || !tangent) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_fixed_spec: lambd_dev / tangent is NULL (the training forward saves the spectrogram)");
-    if (flags & DMEL_FLAG_FULL_WINDOW) return fail(DMEL_ERR_UNSUPPORTED, "dmel_forward_dev_fixed_spec: not with DMEL_FLAG_FULL_WINDOW");
-    if (n_fft < dmel::kMinFastNfft || n_fft > dmel::kMaxNfft || (n_fft & (n_fft - 1)))
-        return fail(DMEL_ERR_UNSUPPORTED, "dmel_forward_dev_fixed_spec: n_fft must be a power of two in [32, 16384]");
+    if ((st = check_store_aligned(spec ? "dmel_forward_dev_fixed_spec" : "dmel_forward_dev_fixed",
+                                  {{"out", out}, {"tangent", tangent}, {"spec", spec}, {"scratch", scratch}})) != DMEL_OK) return st;
+    FwdCall c = mel_call(x, batch, flags, eps, out, tangent);
+    c.spec_out = spec;
+    if (spec) {
+        if (!lambd_dev || !tangent) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_fixed_spec: lambd_dev / tangent is NULL (the training forward saves the spectrogram)");
+        if (flags & DMEL_FLAG_FULL_WINDOW) return fail(DMEL_ERR_UNSUPPORTED, "dmel_forward_dev_fixed_spec: not with DMEL_FLAG_FULL_WINDOW");
+        if (n_fft < dmel::kMinFastNfft || n_fft > dmel::kMaxNfft || (n_fft & (n_fft - 1)))
+            return fail(DMEL_ERR_UNSUPPORTED, "dmel_forward_dev_fixed_spec: n_fft must be a power of two in [32, 16384]");
+    } else {
+        if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
+        if (flags & DMEL_FLAG_X_INDIRECT) return fail(DMEL_ERR_INVALID_ARGUMENT, "DMEL_FLAG_X_INDIRECT belongs to dmel_forward_dev");
+        if (flags & DMEL_FLAG_FULL_WINDOW) {
+            // optimized=False (time_frequency.py:41,51): window = the clip, n_fft = 2 n_points whatever lambd is -- nothing to check on
+            // the device, nothing for the host to read: lambd only shapes the window, which the kernels build from the device value
+            c.flags = flags & ~DMEL_FLAG_FULL_WINDOW; c.win_half = 1;
+            return run_forward(plan, c, 0.f, lambd_dev, 2 * plan->cfg.n_points, scratch, stream);
+        }
+        if (n_fft < 1 || n_fft > dmel::kMaxNfft || (n_fft & (n_fft - 1)))
+            return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be a power of two in [1, 16384]");
+    }
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const unsigned long long err = __atomic_load_n(&plan->host_words[dmel::kLamRing], __ATOMIC_RELAXED);
-    if (err != 0) {
-        float lam; const unsigned bits = (unsigned)err; std::memcpy(&lam, &bits, 4);
-        __atomic_store_n(&plan->host_words[dmel::kLamRing], 0ull, __ATOMIC_RELAXED);
-        lam_reset(plan);
+    const Tracked t{&plan->track, plan->host_words, 1, false};
+    const LamError e = take_errors(t);
+    if (e.channel >= 0)
         return fail(DMEL_ERR_LAMBD_TRACKING,
-                    "lambd = " + std::to_string(lam) + " asks for n_fft " + std::to_string(dmel_n_fft(lam)) + " but the forward was issued for the "
+                    "lambd = " + std::to_string(e.lam) + " asks for n_fft " + std::to_string(dmel_n_fft(e.lam)) + " but the forward was issued for the "
                     "fixed n_fft " + std::to_string(n_fft) + " (a learnable filterbank is tied to one n_fft): call " +
-                    std::to_string((unsigned)(err >> 32)) + " produced NaN");
-    }
+                    std::to_string(e.seq) + " produced NaN");
     if (batch == 0) return DMEL_OK;
     Scratch sc;
-    if (scratch) sc = carve(scratch);
-    else {
-        if ((st = order_after_last_stream(plan, s)) != DMEL_OK) return st;
-        if ((st = ensure_own_scratch(plan, batch, s, &sc)) != DMEL_OK) return st;
-    }
-    dmel::LamArgs lam{};
-    lam.dev = lambd_dev; lam.val = 0.f; lam.n_expected = n_fft;
+    if ((st = select_scratch(plan, scratch, batch, s, &sc)) != DMEL_OK) return st;
+    dmel::LamArgs lam = tracked_lam_args(lambd_dev, plan->exec_counter, plan->host_words, sc);
+    lam.n_expected = n_fft;
     lam.role = dmel::kLamFirst | dmel::kLamLast;
-    ++plan->calls;
-    if (!is_capturing(s)) ++plan->issued;
-    lam.exec_counter = plan->exec_counter; lam.handled = sc.handled;
-    lam.host_seen = &plan->host_words[0]; lam.host_error = &plan->host_words[dmel::kLamRing];
     lam.dot_counter = scratch ? sc.counter : nullptr;
-    plan->last_guards = 0;
+    count_call(plan, t, is_capturing(s));
+    plan->track.last_guards = 0;
     bool sums_done = false;
-    return launch_forward_n(plan, x, batch, n_fft, lam, flags, eps, static_cast<float*>(out), tangent, dmel::kTrain, /*remove_dc=*/1, sc, s, 0,
-                            &sums_done, spec);
+    return launch_forward_n(plan, n_fft, lam, c, sc, s, &sums_done);
 }
 
 dmel_status dmel_plan_lambd_status(dmel_plan* plan, dmel_lambd_status* status)
 {
     if (!plan || !status) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan / status is NULL");
     std::lock_guard<std::mutex> lock(plan->mu);
-    lam_observe(plan);
+    lt::observe(&plan->track, plan->host_words, dmel::kLamRing);
     dmel_lambd_status r{};
-    r.known = plan->lam_known ? 1 : 0;
-    r.lambd_seen = plan->lam_seen;
-    r.n_fft_seen = plan->lam_known ? dmel_n_fft(plan->lam_seen) : 0;
-    r.seq_issued = plan->issued; r.seq_seen = plan->seq_seen; r.calls = plan->calls;
-    r.rate = plan->lam_rate; r.guards = plan->last_guards;
-    if (plan->lam_known) lam_decide(plan, false, &r.next_n_fft, &r.next_guards);
-    const unsigned long long err = __atomic_load_n(&plan->host_words[dmel::kLamRing], __ATOMIC_RELAXED);
-    r.error = err != 0 ? 1 : 0;
-    r.error_seq = (uint32_t)(err >> 32);
-    { const unsigned bits = (unsigned)err; std::memcpy(&r.error_lambd, &bits, 4); }
+    lt::fill_status(plan->track, plan->host_words, dmel::kLamRing, &r);
+    if (r.known) decide_scalar(plan, false, &r.next_n_fft, &r.next_guards);      // (a forced launch is what the next call issues)
+    r.calls = plan->calls;
     *status = r;
     return DMEL_OK;
 }
@@ -1728,8 +1733,8 @@ dmel_status dmel_plan_lambd_reset(dmel_plan* plan)
 {
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
     std::lock_guard<std::mutex> lock(plan->mu);
-    lam_reset(plan);
-    for (auto& tr : plan->multi) lam_reset(&tr);
+    lt::reset(&plan->track);
+    for (auto& tr : plan->multi) lt::reset(&tr);
     return DMEL_OK;
 }
 
@@ -1757,7 +1762,7 @@ dmel_status dmel_decide_launch(float lambd, float rate, float stale_forwards, in
 {
     if (!n_fft || !guards || !(rate >= 0.f) || !(stale_forwards >= 0.f)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_decide_launch: bad arguments");
     int n = 0, g = 0;
-    decide_launch(lambd, rate, stale_forwards, &n, &g);
+    lt::decide_launch(lambd, rate, stale_forwards, &n, &g);
     *n_fft = n; *guards = g;
     return DMEL_OK;
 }
@@ -1769,18 +1774,14 @@ dmel_status dmel_decide_launch_multi(const float* lambd, const float* rate, int3
 {
     if (!lambd || !rate || !n_ffts || !channel_masks || !count || channels < 1 || channels > dmel::kMaxChannels || !(stale_forwards >= 0.f))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_decide_launch_multi: bad arguments");
-    std::map<int, uint32_t> u;
+    int n[dmel::kMaxChannels], g[dmel::kMaxChannels];
     for (int c = 0; c < channels; ++c) {
         if (!(rate[c] >= 0.f)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_decide_launch_multi: rate < 0");
-        int n = 0, g = 0;
-        decide_launch(lambd[c], rate[c], stale_forwards, &n, &g);
-        u[n] |= 1u << c;
-        if (g & 2) u[2 * n] |= 1u << c;
-        if (g & 1) u[n / 2] |= 1u << c;
+        lt::decide_launch(lambd[c], rate[c], stale_forwards, &n[c], &g[c]);
     }
-    int k = 0;
-    for (const auto& kv : u) { n_ffts[k] = kv.first; channel_masks[k] = kv.second; ++k; }
-    *count = k;
+    const LaunchList ll = group_by_nfft(n, g, channels, 0, 0x7fffffff);
+    for (int i = 0; i < ll.nl; ++i) { n_ffts[i] = ll.ns[i]; channel_masks[i] = ll.mask[i]; }
+    *count = ll.nl;
     return DMEL_OK;
 }
 
@@ -1795,62 +1796,53 @@ namespace {
 // the flags the multi-window and band-split forwards take
 constexpr uint32_t kMultiFlags = DMEL_FLAG_LOG | DMEL_FLAG_OUT_BF16;
 
-dmel_status check_multi_args(dmel_plan* pl, const float* x, int batch, int channels, uint32_t flags, const void* out, const float* tangent,
-                             void* scratch, const char* fn)
+dmel_status check_multi_args(dmel_plan* pl, const FwdCall& c, void* scratch, const char* fn)
 {
-    dmel_status st = check_forward_args(pl, x, batch, out);
+    const int channels = c.ml.channels;
+    dmel_status st = check_forward_args(pl, c.x, c.batch, c.out);
     if (st != DMEL_OK) return st;
-    if ((st = check_store_aligned(fn, {{"out", out}, {"tangent", tangent}, {"scratch", scratch}})) != DMEL_OK) return st;
+    if ((st = check_store_aligned(fn, {{"out", c.out}, {"tangent", c.tangent}, {"scratch", scratch}})) != DMEL_OK) return st;
     if (channels < 1 || channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, "channels must be 1 ... 8");
-    if (flags & ~kMultiFlags)
+    if (c.flags & ~kMultiFlags)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi: only DMEL_FLAG_LOG and DMEL_FLAG_OUT_BF16 are accepted");
-    if (batch > 0 && !scratch) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi: scratch (dmel_scratch_bytes_multi) is required");
-    if ((long long)batch * channels > 65534) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch x channels > 65534 (split the call)");
+    if (c.batch > 0 && !scratch) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi: scratch (dmel_scratch_bytes_multi) is required");
+    if ((long long)c.batch * channels > 65534) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch x channels > 65534 (split the call)");
     return DMEL_OK;
 }
 
-bool multi_in_range(int n) { return n >= dmel::kMinFastNfft && n <= dmel::kMaxFastNfft; }
-
-// one launch per distinct n_fft: `mask[i]` = the channels of launch i, in ascending channel order; a channel's lambd roles are first / last
-// among the launches that carry it
-dmel_status issue_multi(dmel_plan* pl, const float* x, int batch, int channels, const int* ns, const uint32_t* mask, int nl,
-                        const dmel::LamArgs& base, const float* vals, uint32_t flags, double eps, void* out, float* tangent,
-                        const Scratch& sc, hipStream_t s, const int32_t* edges = nullptr, const int32_t* lengths = nullptr)
+// one launch per entry of the list, its channels ascending; a channel's lambd roles are first / last among the launches that carry it (c.ml: the layer)
+dmel_status issue_multi(dmel_plan* pl, const LaunchList& ll, const dmel::LamArgs& base, const FwdCall& c, const Scratch& sc, hipStream_t s)
 {
+    const int channels = c.ml.channels;
     int first[dmel::kMaxChannels], last[dmel::kMaxChannels];
-    for (int c = 0; c < channels; ++c) { first[c] = -1; last[c] = -1; }
-    pl->last_multi_nl = nl;                       // (host code: runs under capture too)
-    for (int i = 0; i < nl; ++i) { pl->last_multi_ns[i] = ns[i]; pl->last_multi_mask[i] = mask[i]; }
-    for (int i = 0; i < nl; ++i)
-        for (int c = 0; c < channels; ++c)
-            if (mask[i] >> c & 1u) { if (first[c] < 0) first[c] = i; last[c] = i; }
+    for (int ch = 0; ch < channels; ++ch) { first[ch] = -1; last[ch] = -1; }
+    pl->last_multi_nl = ll.nl;                       // (host code: runs under capture too)
+    for (int i = 0; i < ll.nl; ++i) { pl->last_multi_ns[i] = ll.ns[i]; pl->last_multi_mask[i] = ll.mask[i]; }
+    for (int i = 0; i < ll.nl; ++i)
+        for (int ch = 0; ch < channels; ++ch)
+            if (ll.mask[i] >> ch & 1u) { if (first[ch] < 0) first[ch] = i; last[ch] = i; }
     bool sums_done = false;
-    dmel_plan_info primary_info = pl->info;
-    for (int i = 0; i < nl; ++i) {
-        MultiLaunch ml;
-        ml.ch_out = edges ? 1 : channels; ml.edges = edges; ml.channels = channels;
-        for (int c = 0; c < dmel::kMaxChannels; ++c) ml.vals[c] = c < channels && vals ? vals[c] : 0.f;
-        for (int c = 0; c < channels; ++c) {
-            if (!(mask[i] >> c & 1u)) continue;
-            const unsigned role = (first[c] == i ? dmel::kLamFirst : 0u) | (last[c] == i ? dmel::kLamLast : 0u);
-            ml.list |= (unsigned)c << (4 * ml.count);
-            ml.roles |= role << (4 * ml.count);
-            ++ml.count;
+    return issue_group(pl, ll.nl, [&](int i) {
+        FwdCall q = c;
+        for (int ch = 0; ch < channels; ++ch) {
+            if (!(ll.mask[i] >> ch & 1u)) continue;
+            const unsigned role = (first[ch] == i ? dmel::kLamFirst : 0u) | (last[ch] == i ? dmel::kLamLast : 0u);
+            q.ml.list |= (unsigned)ch << (4 * q.ml.count);
+            q.ml.roles |= role << (4 * q.ml.count);
+            ++q.ml.count;
         }
         dmel::LamArgs lam = base;
-        lam.n_expected = base.n_expected ? ns[i] : 0;
+        lam.n_expected = base.n_expected ? ll.ns[i] : 0;
         if (i != 0) lam.dot_counter = nullptr;
-        const dmel_status st = launch_forward_n(pl, x, batch, ns[i], lam, flags, eps, static_cast<float*>(out), tangent,
-                                                tangent ? dmel::kTrain : dmel::kInfer, /*remove_dc=*/1, sc, s, 0, &sums_done, nullptr, &ml, lengths);
-        if (st != DMEL_OK) return st;
-        if (i == 0) primary_info = pl->info;
-    }
-    pl->info = primary_info;
-    return DMEL_OK;
+        return launch_forward_n(pl, ll.ns[i], lam, q, sc, s, &sums_done);
+    });
 }
 
-// 0 = e_0 < e_1 < ... < e_K (every group non-empty); e_K = n_mels is checked against the plan by the caller
-dmel_status check_band_edges(const int32_t* edges, int channels, const char* who)
+// K validated band edges, taken by value (they travel in the kernel arguments)
+struct BandEdges { int32_t e[dmel::kMaxChannels + 1] = {}; };
+
+// 0 = e_0 < e_1 < ... < e_K = n_mels (every group non-empty)
+dmel_status take_band_edges(const dmel_plan* pl, const int32_t* edges, int channels, const char* who, BandEdges* out)
 {
     if (channels < 1 || channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": channels must be 1 ... 8");
     if (!edges) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges is NULL");
@@ -1858,51 +1850,36 @@ dmel_status check_band_edges(const int32_t* edges, int channels, const char* who
     for (int c = 0; c < channels; ++c)
         if (edges[c + 1] <= edges[c])
             return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges must be strictly ascending (group " + std::to_string(c) + " is empty)");
-    return DMEL_OK;
-}
-
-dmel_status check_band_plan(const dmel_plan* pl, const int32_t* edges, int channels, const char* who)
-{
     if (!pl) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
     if (edges[channels] != pl->cfg.n_mels)
         return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges must end at n_mels = " + std::to_string(pl->cfg.n_mels) + " (got " +
                     std::to_string(edges[channels]) + ")");
+    for (int c = 0; c <= channels; ++c) out->e[c] = edges[c];
     return DMEL_OK;
 }
 
-dmel_status forward_multi_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, uint32_t flags,
-                               double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges,
-                               const int32_t* lengths = nullptr)
+dmel_status forward_multi_impl(dmel_plan* plan, FwdCall c, const float* lambd_host, void* scratch, void* stream)
 {
-    dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, tangent, scratch, edges ? "dmel_forward_band" : "dmel_forward_multi");
+    const int channels = c.ml.channels;
+    dmel_status st = check_multi_args(plan, c, scratch, c.ml.edges ? "dmel_forward_band" : "dmel_forward_multi");
     if (st != DMEL_OK) return st;
     if (!lambd_host) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_host is NULL");
-    std::map<int, uint32_t> u;
-    for (int c = 0; c < channels; ++c) {
-        if (!std::isfinite(lambd_host[c])) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd of channel " + std::to_string(c) + " is not finite");
-        const int n = dmel_n_fft(lambd_host[c]);
-        if (!multi_in_range(n))
-            return fail(DMEL_ERR_UNSUPPORTED, "channel " + std::to_string(c) + ": lambd = " + std::to_string(lambd_host[c]) + " gives n_fft " +
-                        std::to_string(n) + ", the multi-window layer serves 32 ... 16384");
-        u[n] |= 1u << c;
-    }
-    if (batch == 0) return DMEL_OK;
+    if ((st = check_lambd_multi(lambd_host, channels)) != DMEL_OK) return st;
+    if (c.batch == 0) return DMEL_OK;
     std::lock_guard<std::mutex> lock(plan->mu);
-    int ns[dmel::kMaxChannels]; uint32_t mask[dmel::kMaxChannels]; int nl = 0;
-    for (const auto& kv : u) { ns[nl] = kv.first; mask[nl] = kv.second; ++nl; }
+    const LaunchList ll = group_host_values(lambd_host, channels);
+    for (int ch = 0; ch < channels; ++ch) c.ml.vals[ch] = lambd_host[ch];
     const Scratch sc = carve(scratch, channels);
     dmel::LamArgs base{};
     base.n_expected = 0;                          // every n_fft was derived from these very values
     base.dot_counter = sc.counter;
-    return issue_multi(plan, x, batch, channels, ns, mask, nl, base, lambd_host, flags, eps, out, tangent, sc,
-                       reinterpret_cast<hipStream_t>(stream), edges, lengths);
+    return issue_multi(plan, ll, base, c, sc, reinterpret_cast<hipStream_t>(stream));
 }
 
-dmel_status forward_multi_dev_impl(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
-                                   double eps, void* out, float* tangent, void* scratch, void* stream, const int32_t* edges,
-                                   const int32_t* lengths = nullptr)
+dmel_status forward_multi_dev_impl(dmel_plan* plan, FwdCall c, const float* lambd_dev, void* scratch, void* stream)
 {
-    dmel_status st = check_multi_args(plan, x, batch, channels, flags, out, tangent, scratch, edges ? "dmel_forward_band_dev" : "dmel_forward_multi_dev");
+    const int channels = c.ml.channels;
+    dmel_status st = check_multi_args(plan, c, scratch, c.ml.edges ? "dmel_forward_band_dev" : "dmel_forward_multi_dev");
     if (st != DMEL_OK) return st;
     if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
     std::lock_guard<std::mutex> lock(plan->mu);
@@ -1916,86 +1893,51 @@ dmel_status forward_multi_dev_impl(dmel_plan* plan, const float* x, int32_t batc
         DMEL_HIP(hipMalloc(reinterpret_cast<void**>(&plan->multi_exec), dmel::kMaxChannels * sizeof(unsigned)));
         DMEL_HIP(hipMemset(plan->multi_exec, 0, dmel::kMaxChannels * sizeof(unsigned)));
     }
-    auto ring = [&](int c) { return plan->multi_words + (size_t)c * dmel::kLamMultiStride; };
-    // a channel that no launch covered: NaN in that channel on the device; tell the caller once, naming it, and start that channel over
-    std::string msg;
-    for (int c = 0; c < channels; ++c) {
-        const unsigned long long err = __atomic_load_n(&ring(c)[dmel::kLamRing], __ATOMIC_RELAXED);
-        if (err == 0) continue;
-        float lam; const unsigned bits = (unsigned)err; std::memcpy(&lam, &bits, 4);
-        __atomic_store_n(&ring(c)[dmel::kLamRing], 0ull, __ATOMIC_RELAXED);
-        const float seen = plan->multi[c].lam_seen;
-        lam_reset(&plan->multi[c]);
-        if (msg.empty())
-            msg = "channel " + std::to_string(c) + ": lambd moved from " + std::to_string(seen) + " (n_fft " + std::to_string(dmel_n_fft(seen)) +
-                  ") to " + std::to_string(lam) + " (n_fft " + std::to_string(dmel_n_fft(lam)) + ") where no launch of the sync-free forward "
-                  "covered it (or out of the range 32 ... 16384): execution " + std::to_string((unsigned)(err >> 32)) + " of that channel "
-                  "produced NaN in it.  Its tracking has been reset";
-    }
-    if (!msg.empty()) return fail(DMEL_ERR_LAMBD_TRACKING, msg);
-    if (batch == 0) return DMEL_OK;
-    bool cold = false;
-    for (int c = 0; c < channels; ++c) { lam_observe_ring(&plan->multi[c], ring(c)); cold |= !plan->multi[c].lam_known; }
-    if (cold) {
-        // cold start (any channel): the one blocking read of the K values
-        if (capturing) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_dev: run the layer once eagerly before capturing it into a graph");
-        float lam[dmel::kMaxChannels];
-        DMEL_HIP(hipMemcpyAsync(lam, lambd_dev, channels * sizeof(float), hipMemcpyDeviceToHost, s));
-        DMEL_HIP(hipStreamSynchronize(s));
-        for (int c = 0; c < channels; ++c) {
-            if (!std::isfinite(lam[c])) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd of channel " + std::to_string(c) + " is not finite");
-            if (!multi_in_range(dmel_n_fft(lam[c])))
-                return fail(DMEL_ERR_UNSUPPORTED, "channel " + std::to_string(c) + ": lambd = " + std::to_string(lam[c]) + " gives n_fft " +
-                            std::to_string(dmel_n_fft(lam[c])) + ", the multi-window layer serves 32 ... 16384");
-        }
-        for (int c = 0; c < channels; ++c) {
-            auto& tr = plan->multi[c];
-            if (tr.lam_known) continue;
-            for (unsigned i = 0; i < dmel::kLamRing; ++i) {
-                const unsigned q = (unsigned)(__atomic_load_n(&ring(c)[i], __ATOMIC_RELAXED) >> 32);
-                if (q != 0 && (int)(q - tr.issued) > 0) tr.issued = q;
-            }
-            tr.lam_seen = lam[c]; tr.seq_seen = tr.issued; tr.lam_known = true; tr.n_obs = 0; tr.lam_rate = 0.f;
-        }
-    } else if (!capturing && plan->max_ahead > 0) {
-        // bounded run-ahead, per channel (all channels execute in the same forwards: in practice the first wait covers the others)
-        for (int c = 0; c < channels; ++c) {
-            auto& tr = plan->multi[c];
-            for (long spins = 0; tr.issued - tr.seq_seen > (unsigned)plan->max_ahead && spins < 200000000L; ++spins) {
-                if (!lam_observe_ring(&tr, ring(c)) && (spins & 1023) == 1023 && hipStreamQuery(s) == hipSuccess) { lam_observe_ring(&tr, ring(c)); break; }
-            }
-        }
-        (void)hipGetLastError();
-    }
+    const Tracked t{plan->multi, plan->multi_words, channels, true};
+    // a channel that no launch covered: NaN in that channel on the device; tell the caller once, naming it (that channel has started over)
+    const LamError e = take_errors(t);
+    if (e.channel >= 0)
+        return fail(DMEL_ERR_LAMBD_TRACKING,
+                    "channel " + std::to_string(e.channel) + ": lambd moved from " + std::to_string(e.seen) + " (n_fft " + std::to_string(dmel_n_fft(e.seen)) +
+                    ") to " + std::to_string(e.lam) + " (n_fft " + std::to_string(dmel_n_fft(e.lam)) + ") where no launch of the sync-free forward "
+                    "covered it (or out of the range 32 ... 16384): execution " + std::to_string(e.seq) + " of that channel "
+                    "produced NaN in it.  Its tracking has been reset");
+    if (c.batch == 0) return DMEL_OK;
+    if ((st = settle_pictures(plan, t, lambd_dev, s, capturing)) != DMEL_OK) return st;
     // each channel's launches, clamped to the range the fused kernel serves (a channel whose lambd left it is then poisoned and reported)
-    std::map<int, uint32_t> u;
-    for (int c = 0; c < channels; ++c) {
-        int N = 0, g = 0;
-        lam_decide_track(plan, &plan->multi[c], capturing, &N, &g);
-        plan->multi[c].last_guards = g;
-        N = std::min(std::max(N, dmel::kMinFastNfft), dmel::kMaxFastNfft);
-        u[N] |= 1u << c;
-        if ((g & 2) && multi_in_range(2 * N)) u[2 * N] |= 1u << c;
-        if ((g & 1) && multi_in_range(N / 2)) u[N / 2] |= 1u << c;
+    int n[dmel::kMaxChannels], g[dmel::kMaxChannels];
+    for (int ch = 0; ch < channels; ++ch) {
+        lt::decide(plan->multi[ch], plan->guard_mode, plan->max_ahead, capturing, &n[ch], &g[ch]);
+        plan->multi[ch].last_guards = g[ch];     // (as decided: a guard outside 32 ... 16384 is recorded and not launched; the scalar layer records its launches)
+        n[ch] = std::min(std::max(n[ch], dmel::kMinFastNfft), dmel::kMaxFastNfft);
     }
-    int ns[3 * dmel::kMaxChannels]; uint32_t mask[3 * dmel::kMaxChannels]; int nl = 0;
-    for (const auto& kv : u) { ns[nl] = kv.first; mask[nl] = kv.second; ++nl; }
-    if (!capturing) {
-        // tables of the neighbouring sizes exist before they are needed (as dmel_forward_dev)
-        NfftTables* tb = nullptr;
-        for (int i = 0; i < nl; ++i)
-            for (int n : {ns[i], 2 * ns[i], ns[i] / 2})
-                if (multi_in_range(n) && (st = build_tables(plan, n, &tb)) != DMEL_OK) return st;
-    }
-    ++plan->calls;
-    if (!capturing) for (int c = 0; c < channels; ++c) ++plan->multi[c].issued;
+    const LaunchList ll = group_by_nfft(n, g, channels, dmel::kMinFastNfft, dmel::kMaxFastNfft);
+    if (!capturing && (st = prebuild_tables(plan, ll.ns, ll.nl, dmel::kMinFastNfft, dmel::kMaxFastNfft)) != DMEL_OK) return st;
+    count_call(plan, t, capturing);
     const Scratch sc = carve(scratch, channels);
-    dmel::LamArgs base{};
-    base.dev = lambd_dev; base.n_expected = 1;    // (issue_multi: check against the n_fft of each launch)
-    base.exec_counter = plan->multi_exec; base.handled = sc.handled;
-    base.host_seen = plan->multi_words; base.host_error = plan->multi_words + dmel::kLamRing;
+    dmel::LamArgs base = tracked_lam_args(lambd_dev, plan->multi_exec, plan->multi_words, sc);
+    base.n_expected = 1;                          // (issue_multi: check against the n_fft of each launch)
     base.dot_counter = sc.counter;
-    return issue_multi(plan, x, batch, channels, ns, mask, nl, base, nullptr, flags, eps, out, tangent, sc, s, edges, lengths);
+    return issue_multi(plan, ll, base, c, sc, s);
+}
+
+// The eight K-window forwards are named multi | band, [_dev], [_lengths]; `form` says which: kFormDev (lambd on the device: tracked), kFormBand (c.ml.edges,
+// the caller's host integers, validated and taken by value), kFormLengths (the NULL and flag checks of those forms first, before the plan is looked at)
+constexpr unsigned kFormDev = 1u, kFormBand = 2u, kFormLengths = 4u;
+dmel_status forward_k(const char* who, unsigned form, dmel_plan* plan, FwdCall c, const int32_t* lengths, const float* lambd, void* scratch, void* stream)
+{
+    c.lengths = lengths;
+    if (form & kFormLengths) {
+        if (!plan || !c.x || !c.lengths || !c.out) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": plan / x / lengths / out is NULL");
+        if (c.flags & ~kMultiFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": flags other than LOG, OUT_BF16");
+    }
+    BandEdges be;
+    if (form & kFormBand) {
+        const dmel_status st = take_band_edges(plan, c.ml.edges, c.ml.channels, who, &be);
+        if (st != DMEL_OK) return st;
+        c.ml.edges = be.e; c.ml.ch_out = 1;
+    }
+    return (form & kFormDev) ? forward_multi_dev_impl(plan, c, lambd, scratch, stream) : forward_multi_impl(plan, c, lambd, scratch, stream);
 }
 
 }  // namespace
@@ -2003,104 +1945,83 @@ dmel_status forward_multi_dev_impl(dmel_plan* plan, const float* x, int32_t batc
 dmel_status dmel_forward_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, uint32_t flags,
                                double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    return forward_multi_impl(plan, x, batch, lambd_host, channels, flags, eps, out, tangent, scratch, stream, nullptr);
+    return forward_k("dmel_forward_multi", 0u, plan, k_call(x, batch, channels, nullptr, flags, eps, out, tangent), nullptr, lambd_host, scratch, stream);
 }
 
 dmel_status dmel_forward_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, uint32_t flags,
                                    double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    return forward_multi_dev_impl(plan, x, batch, lambd_dev, channels, flags, eps, out, tangent, scratch, stream, nullptr);
+    return forward_k("dmel_forward_multi_dev", kFormDev, plan, k_call(x, batch, channels, nullptr, flags, eps, out, tangent), nullptr, lambd_dev, scratch, stream);
 }
 
-// the multi-window forwards over clips of per-clip lengths (dmel_fwd_multi_len_kernel): the same launches, guards and per-channel pictures
 dmel_status dmel_forward_multi_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
                                        int32_t channels, uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    if (!plan || !x || !lengths || !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_lengths: plan / x / lengths / out is NULL");
-    if (flags & ~kMultiFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_lengths: flags other than LOG, OUT_BF16");
-    return forward_multi_impl(plan, x, batch, lambd_host, channels, flags, eps, out, tangent, scratch, stream, nullptr, lengths);
+    return forward_k("dmel_forward_multi_lengths", kFormLengths, plan, k_call(x, batch, channels, nullptr, flags, eps, out, tangent), lengths, lambd_host, scratch, stream);
 }
 
 dmel_status dmel_forward_multi_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
                                            int32_t channels, uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    if (!plan || !x || !lengths || !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_dev_lengths: plan / x / lengths / out is NULL");
-    if (flags & ~kMultiFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_multi_dev_lengths: flags other than LOG, OUT_BF16");
-    return forward_multi_dev_impl(plan, x, batch, lambd_dev, channels, flags, eps, out, tangent, scratch, stream, nullptr, lengths);
+    return forward_k("dmel_forward_multi_dev_lengths", kFormDev | kFormLengths, plan, k_call(x, batch, channels, nullptr, flags, eps, out, tangent), lengths, lambd_dev, scratch, stream);
 }
-
-// ---- the band-split layer: K window widths inside ONE image, a width per group of mel bands -----------------------------------------
-// The multi-window layer's launches (one per distinct n_fft, the same per-channel lambd words, guards and scratch) through dmel_fwd_band_kernel.
-// band_edges are host integers, validated and taken by value (they travel in the kernel arguments).
-namespace {
-
-// what the four band forwards share: with `lengths_wanted` the NULL and flag checks of the *_lengths forms, then the edges validated against
-// themselves and the plan and taken by value, then the multi-window implementation `impl` (host or device lambd)
-using MultiImpl = dmel_status (*)(dmel_plan*, const float*, int32_t, const float*, int32_t, uint32_t, double, void*, float*, void*, void*,
-                                  const int32_t*, const int32_t*);
-dmel_status forward_band_common(MultiImpl impl, const char* who, bool lengths_wanted, dmel_plan* plan, const float* x, const int32_t* lengths,
-                                int32_t batch, const float* lambd, int32_t channels, const int32_t* band_edges, uint32_t flags, double eps,
-                                void* out, float* tangent, void* scratch, void* stream)
-{
-    if (lengths_wanted) {
-        if (!plan || !x || !lengths || !out) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": plan / x / lengths / out is NULL");
-        if (flags & ~kMultiFlags) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": flags other than LOG, OUT_BF16");
-    }
-    dmel_status st = check_band_edges(band_edges, channels, who);
-    if (st != DMEL_OK) return st;
-    if ((st = check_band_plan(plan, band_edges, channels, who)) != DMEL_OK) return st;
-    int32_t edges[dmel::kMaxChannels + 1];
-    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
-    return impl(plan, x, batch, lambd, channels, flags, eps, out, tangent, scratch, stream, edges, lengths);
-}
-
-}  // namespace
 
 dmel_status dmel_forward_band(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, const int32_t* band_edges,
                               uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    return forward_band_common(forward_multi_impl, "dmel_forward_band", false, plan, x, nullptr, batch, lambd_host, channels, band_edges, flags, eps,
-                               out, tangent, scratch, stream);
+    return forward_k("dmel_forward_band", kFormBand, plan, k_call(x, batch, channels, band_edges, flags, eps, out, tangent), nullptr, lambd_host, scratch, stream);
 }
 
 dmel_status dmel_forward_band_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, const int32_t* band_edges,
                                   uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream)
 {
-    return forward_band_common(forward_multi_dev_impl, "dmel_forward_band_dev", false, plan, x, nullptr, batch, lambd_dev, channels, band_edges, flags,
-                               eps, out, tangent, scratch, stream);
+    return forward_k("dmel_forward_band_dev", kFormDev | kFormBand, plan, k_call(x, batch, channels, band_edges, flags, eps, out, tangent), nullptr, lambd_dev, scratch, stream);
 }
 
-// the band-split forwards over clips of per-clip lengths (dmel_fwd_band_len_kernel)
 dmel_status dmel_forward_band_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
                                       int32_t channels, const int32_t* band_edges, uint32_t flags, double eps, void* out, float* tangent,
                                       void* scratch, void* stream)
 {
-    return forward_band_common(forward_multi_impl, "dmel_forward_band_lengths", true, plan, x, lengths, batch, lambd_host, channels, band_edges, flags,
-                               eps, out, tangent, scratch, stream);
+    return forward_k("dmel_forward_band_lengths", kFormBand | kFormLengths, plan, k_call(x, batch, channels, band_edges, flags, eps, out, tangent), lengths, lambd_host, scratch, stream);
 }
 
 dmel_status dmel_forward_band_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
                                           int32_t channels, const int32_t* band_edges, uint32_t flags, double eps, void* out, float* tangent,
                                           void* scratch, void* stream)
 {
-    return forward_band_common(forward_multi_dev_impl, "dmel_forward_band_dev_lengths", true, plan, x, lengths, batch, lambd_dev, channels, band_edges,
-                               flags, eps, out, tangent, scratch, stream);
+    return forward_k("dmel_forward_band_dev_lengths", kFormDev | kFormBand | kFormLengths, plan, k_call(x, batch, channels, band_edges, flags, eps, out, tangent), lengths, lambd_dev, scratch, stream);
 }
+
+namespace {
+
+// what the dot entry points refuse alike, each under its own name
+dmel_status check_grad_dtype(int32_t grad_dtype, const char* who)
+{
+    if (grad_dtype == DMEL_DTYPE_F32 || grad_dtype == DMEL_DTYPE_BF16) return DMEL_OK;
+    return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
+}
+
+// the reducers that live in the scalar layer's dot kernel
+dmel_status check_scalar_reducers_only(const dmel_plan* plan, const char* who)
+{
+    if (!plan->mailbox && !plan->fused_adam.param) return DMEL_OK;
+    return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": a plan with an attached mailbox or fused Adam serves the scalar layer only");
+}
+
+}  // namespace
 
 dmel_status dmel_backward_band(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int32_t batch, int32_t channels,
                                const int32_t* band_edges, int32_t accumulate, float* dlambd, void* scratch, void* stream)
 {
-    dmel_status st = check_band_edges(band_edges, channels, "dmel_backward_band");
+    BandEdges be;
+    dmel_status st = take_band_edges(plan, band_edges, channels, "dmel_backward_band", &be);
     if (st != DMEL_OK) return st;
-    if ((st = check_band_plan(plan, band_edges, channels, "dmel_backward_band")) != DMEL_OK) return st;
     if (batch < 0 || !dlambd || !scratch || (batch > 0 && (!grad_out || !tangent)))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: bad arguments");
     if ((st = check_store_aligned("dmel_backward_band", {{"scratch", scratch}})) != DMEL_OK) return st;
-    if (grad_dtype != DMEL_DTYPE_F32 && grad_dtype != DMEL_DTYPE_BF16)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
-    if (plan->mailbox || plan->fused_adam.param)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: a plan with an attached mailbox or fused Adam serves the scalar layer only");
-    { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
+    if ((st = check_grad_dtype(grad_dtype, "dmel_backward_band")) != DMEL_OK) return st;
+    if ((st = check_scalar_reducers_only(plan, "dmel_backward_band")) != DMEL_OK) return st;
+    if ((st = check_device(plan)) != DMEL_OK) return st;
     if ((long long)batch * plan->cfg.n_mels * plan->T >= (1LL << 31)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_band: more than 2^31 elements");
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2109,7 +2030,7 @@ dmel_status dmel_backward_band(dmel_plan* plan, const void* grad_out, int32_t gr
     dp.g = grad_out; dp.t = tangent; dp.partials = sc.partials; dp.counter = sc.counter; dp.result = dlambd;
     dp.g_bf16 = grad_dtype == DMEL_DTYPE_BF16; dp.batch = batch; dp.channels = channels; dp.M = plan->cfg.n_mels; dp.T = plan->T;
     dp.accumulate = accumulate;
-    for (int c = 0; c <= dmel::kMaxChannels; ++c) dp.edges[c] = band_edges[std::min(c, channels)];
+    for (int c = 0; c <= dmel::kMaxChannels; ++c) dp.edges[c] = be.e[std::min(c, channels)];
     // at most kDotMaxBlocks partials in all (the ticket tree's layout), dealt to the groups in proportion to their rows
     dmel::dot_band_deal(dp.edges, channels, batch, plan->T, dp.blocks);
     const size_t m0 = prof_mark(plan, s);
@@ -2124,12 +2045,11 @@ dmel_status dmel_backward_multi(dmel_plan* plan, const void* grad_out, int32_t g
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
     if (batch < 0 || channels < 1 || channels > dmel::kMaxChannels || !dlambd || !scratch || (batch > 0 && (!grad_out || !tangent)))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: bad arguments");
-    { dmel_status sa = check_store_aligned("dmel_backward_multi", {{"scratch", scratch}}); if (sa != DMEL_OK) return sa; }
-    if (grad_dtype != DMEL_DTYPE_F32 && grad_dtype != DMEL_DTYPE_BF16)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
-    if (plan->mailbox || plan->fused_adam.param)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: a plan with an attached mailbox or fused Adam serves the scalar layer only");
-    { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
+    dmel_status st = check_store_aligned("dmel_backward_multi", {{"scratch", scratch}});
+    if (st != DMEL_OK) return st;
+    if ((st = check_grad_dtype(grad_dtype, "dmel_backward_multi")) != DMEL_OK) return st;
+    if ((st = check_scalar_reducers_only(plan, "dmel_backward_multi")) != DMEL_OK) return st;
+    if ((st = check_device(plan)) != DMEL_OK) return st;
     const long long per_row = (long long)plan->cfg.n_mels * plan->T;
     if ((long long)batch * per_row >= (1LL << 31)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_multi: more than 2^31 elements per channel");
     std::lock_guard<std::mutex> lock(plan->mu);
@@ -2151,22 +2071,13 @@ dmel_status dmel_plan_lambd_status_channel(dmel_plan* plan, int32_t channel, dme
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_plan_lambd_status_channel: bad arguments");
     std::lock_guard<std::mutex> lock(plan->mu);
     dmel_lambd_status r{};
-    r.calls = plan->calls;
     if (plan->multi_words) {
-        const unsigned long long* ring = plan->multi_words + (size_t)channel * dmel::kLamMultiStride;
-        auto& tr = plan->multi[channel];
-        lam_observe_ring(&tr, ring);
-        r.known = tr.lam_known ? 1 : 0;
-        r.lambd_seen = tr.lam_seen;
-        r.n_fft_seen = tr.lam_known ? dmel_n_fft(tr.lam_seen) : 0;
-        r.seq_issued = tr.issued; r.seq_seen = tr.seq_seen;
-        r.rate = tr.lam_rate; r.guards = tr.last_guards;
-        if (tr.lam_known) lam_decide_track(plan, &tr, false, &r.next_n_fft, &r.next_guards);
-        const unsigned long long err = __atomic_load_n(&ring[dmel::kLamRing], __ATOMIC_RELAXED);
-        r.error = err != 0 ? 1 : 0;
-        r.error_seq = (uint32_t)(err >> 32);
-        { const unsigned bits = (unsigned)err; std::memcpy(&r.error_lambd, &bits, 4); }
+        const Tracked t{plan->multi, plan->multi_words, dmel::kMaxChannels, true};
+        lt::observe(&t.tr[channel], t.ring(channel), dmel::kLamRing);
+        lt::fill_status(t.tr[channel], t.ring(channel), dmel::kLamRing, &r);
+        if (r.known) lt::decide(t.tr[channel], plan->guard_mode, plan->max_ahead, false, &r.next_n_fft, &r.next_guards);
     }
+    r.calls = plan->calls;
     *status = r;
     return DMEL_OK;
 }
@@ -2175,7 +2086,7 @@ dmel_status dmel_spectrogram(dmel_plan* plan, const float* x, int32_t batch, flo
                              int32_t remove_dc, float* spec, void* stream)
 {
     { dmel_status sa = check_store_aligned("dmel_spectrogram", {{"spec", spec}}); if (sa != DMEL_OK) return sa; }
-    return run_forward(plan, x, batch, lambd, 0u, 0.0, spec, nullptr, dmel::kSpec, remove_dc ? 1 : 0, stream);
+    return run_forward(plan, spec_call(x, batch, spec, nullptr, remove_dc ? DMEL_SPEC_REMOVE_DC : 0u), lambd, nullptr, 0, nullptr, stream);
 }
 
 dmel_status dmel_spectrogram_ex(dmel_plan* plan, const float* x, int32_t batch, float lambd, int32_t n_fft,
@@ -2183,8 +2094,7 @@ dmel_status dmel_spectrogram_ex(dmel_plan* plan, const float* x, int32_t batch, 
 {
     if (n_fft < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft < 0");
     { dmel_status sa = check_store_aligned("dmel_spectrogram_ex", {{"spec", spec}, {"tangent", tangent}}); if (sa != DMEL_OK) return sa; }
-    return run_forward(plan, x, batch, lambd, 0u, 0.0, spec, tangent, tangent ? dmel::kSpecTrain : dmel::kSpec,
-                       (flags & DMEL_SPEC_REMOVE_DC) ? 1 : 0, stream, n_fft, (flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0);
+    return run_forward(plan, spec_call(x, batch, spec, tangent, flags), lambd, nullptr, n_fft, nullptr, stream);
 }
 
 dmel_status dmel_spectrogram_ex_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft,
@@ -2193,44 +2103,36 @@ dmel_status dmel_spectrogram_ex_dev(dmel_plan* plan, const float* x, int32_t bat
     if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
     { dmel_status sa = check_store_aligned("dmel_spectrogram_ex_dev", {{"spec", spec}, {"tangent", tangent}}); if (sa != DMEL_OK) return sa; }
     if (n_fft <= 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_spectrogram_ex_dev: n_fft must be given (a length that depends on lambd needs the host value: dmel_spectrogram_ex)");
-    return run_forward(plan, x, batch, 0.f, 0u, 0.0, spec, tangent, tangent ? dmel::kSpecTrain : dmel::kSpec,
-                       (flags & DMEL_SPEC_REMOVE_DC) ? 1 : 0, stream, n_fft, (flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0, nullptr, lambd_dev);
+    return run_forward(plan, spec_call(x, batch, spec, tangent, flags), 0.f, lambd_dev, n_fft, nullptr, stream);
 }
 
 dmel_status dmel_backward_ex(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int64_t count,
                              int32_t accumulate, float* dlambd, void* stream)
 {
+    // (dmel_backward_scratch's first two checks, ahead of the one message that carries this function's name)
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
-    if (count < 0 || !dlambd || (count > 0 && (!grad_out || !tangent)))
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward: bad arguments");
-    if (grad_dtype != DMEL_DTYPE_F32 && grad_dtype != DMEL_DTYPE_BF16)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_ex: grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
-    return dmel_backward_scratch(plan, grad_out, grad_dtype, tangent, count, accumulate, dlambd, nullptr, stream);
+    if (count < 0 || !dlambd || (count > 0 && (!grad_out || !tangent))) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward: bad arguments");
+    const dmel_status st = check_grad_dtype(grad_dtype, "dmel_backward_ex");
+    return st != DMEL_OK ? st : dmel_backward_scratch(plan, grad_out, grad_dtype, tangent, count, accumulate, dlambd, nullptr, stream);
 }
 
 dmel_status dmel_backward_scratch(dmel_plan* plan, const void* grad_out, int32_t grad_dtype, const float* tangent, int64_t count,
                                   int32_t accumulate, float* dlambd, void* scratch, void* stream)
 {
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
-    if (count < 0 || !dlambd || (count > 0 && (!grad_out || !tangent)))
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward: bad arguments");
-    if (grad_dtype != DMEL_DTYPE_F32 && grad_dtype != DMEL_DTYPE_BF16)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward: grad_dtype must be DMEL_DTYPE_F32 or DMEL_DTYPE_BF16");
-    { dmel_status sa = check_store_aligned("dmel_backward", {{"scratch", scratch}}); if (sa != DMEL_OK) return sa; }
-    { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
+    if (count < 0 || !dlambd || (count > 0 && (!grad_out || !tangent))) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward: bad arguments");
+    dmel_status st = check_grad_dtype(grad_dtype, "dmel_backward");
+    if (st != DMEL_OK) return st;
+    if ((st = check_store_aligned("dmel_backward", {{"scratch", scratch}})) != DMEL_OK) return st;
+    if ((st = check_device(plan)) != DMEL_OK) return st;
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     Scratch sc;
-    if (scratch) sc = carve(scratch);
-    else {
-        dmel_status st = order_after_last_stream(plan, s);
-        if (st != DMEL_OK) return st;
-        if ((st = ensure_own_scratch(plan, 1, s, &sc)) != DMEL_OK) return st;
-    }
+    if ((st = select_scratch(plan, scratch, 1, s, &sc)) != DMEL_OK) return st;
     dmel::MailboxArgs mba;
     const bool use_mb = plan->mailbox != nullptr;
     if (use_mb && !dmel::mailbox_args(plan->mailbox, &mba)) return fail(DMEL_ERR_INVALID_ARGUMENT, "the plan's mailbox is not connected");
-    if (use_mb) { dmel_status ms = mailbox_status(plan); if (ms != DMEL_OK) return ms; }
+    if (use_mb && (st = mailbox_status(plan)) != DMEL_OK) return st;
     const size_t m0 = prof_mark(plan, s);
     DMEL_HIP(dmel::launch_dot(grad_out, grad_dtype == DMEL_DTYPE_BF16, tangent, (long long)count, accumulate, sc.partials,
                               sc.counter, kMaxPartials, dlambd, s, use_mb ? &mba : nullptr, plan->fused_adam.param ? &plan->fused_adam : nullptr));
@@ -2274,95 +2176,81 @@ dmel_status dmel_backward(dmel_plan* plan, const float* grad_out, const float* t
     return dmel_backward_ex(plan, grad_out, DMEL_DTYPE_F32, tangent, count, accumulate, dlambd, stream);
 }
 
-}  // extern "C"
-
 namespace {
-// lambd by value (lambd_dev == nullptr; n_fft derived from it) or on the device with the n_fft the caller's forward was issued for
-// saved_spec != nullptr: the (batch, n_fft_dev/2+1, n_time) power spectrogram the training forward wrote (dmel_forward_dev_fixed_spec):
-// no recompute, x and lambd are not touched
-// d lambd computed in the launch of the filterbank gradient (dmel_backward_fb_saved_dl)
-struct DotRider { const float* tangent; float* dlambd; void* scratch; };
+// lambd by value (lambd_dev == nullptr; n_fft derived from it) or on the device with the n_fft the caller's forward was issued for; saved_spec: the (batch,
+// n_fft_dev/2+1, n_time) power spectrogram the training forward wrote: no recompute; dlambd: d lambd computed in the same launch (dmel_backward_fb_saved_dl)
+struct FbGradCall {
+    const float* x = nullptr; int batch = 0; float lambd = 0.f; const float* lambd_dev = nullptr; int n_fft_dev = 0; uint32_t flags = 0;
+    const float* grad_out = nullptr; const float* out = nullptr; float* grad_fb = nullptr; const float* saved_spec = nullptr;
+    const float* tangent = nullptr; float* dlambd = nullptr; void* scratch = nullptr;
+};
 
-dmel_status backward_fb_impl(dmel_plan* plan, const float* x, int32_t batch, float lambd, const float* lambd_dev, int32_t n_fft_dev,
-                             uint32_t flags, const float* grad_out, const float* out, float* grad_fb, void* stream, const float* saved_spec = nullptr,
-                             const DotRider* rider = nullptr)
+dmel_status backward_fb_impl(dmel_plan* plan, const FbGradCall& c, void* stream)
 {
+    const int batch = c.batch;
+    const bool rider = c.dlambd != nullptr;
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
     if (batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch < 0");
-    if (!grad_fb || (batch > 0 && ((!x && !saved_spec) || !grad_out))) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_fb: x / grad_out / grad_fb is NULL");
-    if ((flags & DMEL_FLAG_LOG) && batch > 0 && !out)
+    if (!c.grad_fb || (batch > 0 && ((!c.x && !c.saved_spec) || !c.grad_out))) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_fb: x / grad_out / grad_fb is NULL");
+    if ((c.flags & DMEL_FLAG_LOG) && batch > 0 && !c.out)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_fb: DMEL_FLAG_LOG needs the saved log output");
-    { dmel_status sa = check_store_aligned("dmel_backward_fb", {{"grad_fb", grad_fb}, {"scratch", rider ? rider->scratch : nullptr}}); if (sa != DMEL_OK) return sa; }
-    if (!lambd_dev && !saved_spec && !std::isfinite(lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
-    const bool full = (flags & DMEL_FLAG_FULL_WINDOW) != 0;
-    if (lambd_dev && !full && (n_fft_dev < 1 || n_fft_dev > dmel::kMaxNfft || (n_fft_dev & (n_fft_dev - 1))))
+    { dmel_status sa = check_store_aligned("dmel_backward_fb", {{"grad_fb", c.grad_fb}, {"scratch", c.scratch}}); if (sa != DMEL_OK) return sa; }
+    if (!c.lambd_dev && !c.saved_spec && !std::isfinite(c.lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
+    const bool full = (c.flags & DMEL_FLAG_FULL_WINDOW) != 0;
+    if (c.lambd_dev && !full && (c.n_fft_dev < 1 || c.n_fft_dev > dmel::kMaxNfft || (c.n_fft_dev & (c.n_fft_dev - 1))))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be a power of two in [1, 16384]");
-    int n_over = 0, win_half = 0;
-    if (full) { n_over = 2 * plan->cfg.n_points; win_half = 1; }     // any clip length: the spectrogram pass takes the chirp-z path where it has to
-    const int N = n_over ? n_over : ((lambd_dev || saved_spec) ? n_fft_dev : dmel_n_fft(lambd));
+    const int n_over = full ? 2 * plan->cfg.n_points : 0;     // any clip length: the spectrogram pass takes the chirp-z path where it has to
+    const int N = n_over ? n_over : ((c.lambd_dev || c.saved_spec) ? c.n_fft_dev : dmel_n_fft(c.lambd));
     if (N > dmel::kMaxBigFft)
         return fail(DMEL_ERR_UNSUPPORTED, "n_fft = " + std::to_string(N) + " > " + std::to_string(dmel::kMaxBigFft) + " is not supported by the HIP kernels");
     const int F = N / 2 + 1, M = plan->cfg.n_mels, T = plan->T;
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (batch == 0) { DMEL_HIP(hipMemsetAsync(grad_fb, 0, (size_t)F * M * sizeof(float), s)); return DMEL_OK; }
-    {
-        dmel_status so = order_after_last_stream(plan, s);       // fbw is shared by every call on the plan
-        if (so != DMEL_OK) return so;
-    }
+    if (batch == 0) { DMEL_HIP(hipMemsetAsync(c.grad_fb, 0, (size_t)F * M * sizeof(float), s)); return DMEL_OK; }
+    dmel_status st = order_after_last_stream(plan, s);       // fbw is shared by every call on the plan
+    if (st != DMEL_OK) return st;
     int splits = dmel::fbgrad_splits(batch, F, M, T);
     // d lambd rides along unless the plan's reducer lives in the dot kernel (mailbox) or the launch has no room for it
     Scratch rsc;
     int dot_wgs = 0, dot_vblocks = 0;
     const long long dot_count = (long long)batch * M * T;
     if (rider) {
-        if (rider->scratch) rsc = carve(rider->scratch);
-        else { dmel_status sr = ensure_own_scratch(plan, batch, s, &rsc); if (sr != DMEL_OK) return sr; }
+        if ((st = select_scratch(plan, c.scratch, batch, s, &rsc)) != DMEL_OK) return st;
         if (!plan->mailbox) {
             dot_vblocks = dmel::dot_blocks_for(dot_count, kMaxPartials);
             const int left = dmel::fbgrad_fuse_dot(F, M, splits, dot_vblocks, &dot_wgs);
             if (left > 0) splits = left; else dot_wgs = 0;
         }
     }
-    const size_t spec_floats = saved_spec ? 0 : ((size_t)batch * F * T + 63) / 64 * 64;
-    const size_t part_floats = ((size_t)splits * F * M + 63) / 64 * 64;
-    const size_t gm_floats = 0;      // (gm = grad_out * exp(-out) is formed inside the GEMM kernel)
-    const size_t need = spec_floats + part_floats + gm_floats;
-    if (need > plan->fbw_floats) {
-        if (is_capturing(s)) return fail(DMEL_ERR_INVALID_ARGUMENT, "workspace must grow but the stream is capturing: run one call eagerly first");
-        DMEL_HIP(hipStreamSynchronize(s));
-        (void)hipFree(plan->fbw); plan->fbw = nullptr; plan->fbw_floats = 0;
-        DMEL_HIP(hipMalloc(&plan->fbw, need * sizeof(float)));
-        plan->fbw_floats = need;
-    }
+    const size_t spec_floats = c.saved_spec ? 0 : ((size_t)batch * F * T + 63) / 64 * 64;
+    const size_t part_floats = ((size_t)splits * F * M + 63) / 64 * 64;     // (gm = grad_out * exp(-out) is formed inside the GEMM kernel)
+    if ((st = grow_floats(&plan->fbw, &plan->fbw_floats, spec_floats + part_floats, s, "")) != DMEL_OK) return st;
     // the spectrogram the layer contracted at models.py:53 (DC removed, models.py:38): P is recomputed, not saved
-    dmel_status st;
-    if (saved_spec) {
+    FwdCall sp = spec_call(c.x, batch, plan->fbw, nullptr, DMEL_SPEC_REMOVE_DC | (full ? DMEL_SPEC_HALF_WINDOW : 0u));
+    if (c.saved_spec) {
         st = DMEL_OK;
-    } else if (lambd_dev && full) {
-        // n_fft = 2 n_points does not depend on lambd: the kernels take the window's width from the device value, nothing to check
-        st = run_forward_nolock(plan, x, batch, 0.f, 0u, 0.0, plan->fbw, nullptr, dmel::kSpec, 1, stream, n_over, win_half, nullptr, lambd_dev);
-    } else if (lambd_dev) {
+    } else if (c.lambd_dev && !full) {
         // lambd read on the device and checked against N: a mismatch (the forward of this step reported it) leaves NaN here too
         Scratch sc;
         if ((st = ensure_own_scratch(plan, batch, s, &sc)) != DMEL_OK) return st;
         dmel::LamArgs lam{};
-        lam.dev = lambd_dev; lam.n_expected = N; lam.role = dmel::kLamFirst | dmel::kLamLast;
+        lam.dev = c.lambd_dev; lam.n_expected = N; lam.role = dmel::kLamFirst | dmel::kLamLast;
         bool sums_done = false;
-        st = launch_forward_n(plan, x, batch, N, lam, 0u, 0.0, plan->fbw, nullptr, dmel::kSpec, 1, sc, s, 0, &sums_done);
+        st = launch_forward_n(plan, N, lam, sp, sc, s, &sums_done);
     } else {
-        st = run_forward_nolock(plan, x, batch, lambd, 0u, 0.0, plan->fbw, nullptr, dmel::kSpec, 1, stream, n_over, win_half);
+        // (on the device: n_fft = 2 n_points does not depend on lambd: the kernels take the window's width from the device value, nothing to check)
+        st = run_forward_nolock(plan, sp, c.lambd_dev ? 0.f : c.lambd, c.lambd_dev, n_over, nullptr, stream);
     }
     if (st != DMEL_OK) return st;
     dmel::FbGradParams fp{};
-    fp.spec = saved_spec ? saved_spec : plan->fbw; fp.grad_out = grad_out; fp.out = (flags & DMEL_FLAG_LOG) ? out : nullptr;
-    fp.partials = plan->fbw + spec_floats; fp.grad_fb = grad_fb;
+    fp.spec = c.saved_spec ? c.saved_spec : plan->fbw; fp.grad_out = c.grad_out; fp.out = (c.flags & DMEL_FLAG_LOG) ? c.out : nullptr;
+    fp.partials = plan->fbw + spec_floats; fp.grad_fb = c.grad_fb;
     fp.gm_ws = plan->fbw + spec_floats + part_floats;
     fp.B = batch; fp.F = F; fp.M = M; fp.T = T; fp.splits = splits;
-    fp.bf16x3 = (flags & DMEL_FLAG_MFMA_BF16X3) ? 1 : 0;
+    fp.bf16x3 = (c.flags & DMEL_FLAG_MFMA_BF16X3) ? 1 : 0;
     if (dot_wgs > 0) {
-        fp.dot_g = grad_out; fp.dot_t = rider->tangent; fp.dot_count = dot_count; fp.dot_partials = rsc.partials; fp.dot_counter = rsc.counter;
-        fp.dot_result = rider->dlambd; fp.dot_vblocks = dot_vblocks; fp.dot_wgs = dot_wgs; fp.dot_accumulate = 0;
+        fp.dot_g = c.grad_out; fp.dot_t = c.tangent; fp.dot_count = dot_count; fp.dot_partials = rsc.partials; fp.dot_counter = rsc.counter;
+        fp.dot_result = c.dlambd; fp.dot_vblocks = dot_vblocks; fp.dot_wgs = dot_wgs; fp.dot_accumulate = 0;
     }
     const size_t m0 = prof_mark(plan, s);
     DMEL_HIP(dmel::launch_fbgrad(fp, s));
@@ -2372,7 +2260,7 @@ dmel_status backward_fb_impl(dmel_plan* plan, const float* x, int32_t batch, flo
         const bool use_mb = plan->mailbox != nullptr;
         if (use_mb && !dmel::mailbox_args(plan->mailbox, &mba)) return fail(DMEL_ERR_INVALID_ARGUMENT, "the plan's mailbox is not connected");
         if (use_mb) { dmel_status ms = mailbox_status(plan); if (ms != DMEL_OK) return ms; }
-        DMEL_HIP(dmel::launch_dot(grad_out, 0, rider->tangent, dot_count, 0, rsc.partials, rsc.counter, kMaxPartials, rider->dlambd, s,
+        DMEL_HIP(dmel::launch_dot(c.grad_out, 0, c.tangent, dot_count, 0, rsc.partials, rsc.counter, kMaxPartials, c.dlambd, s,
                                   use_mb ? &mba : nullptr));
     }
     prof_span(plan, m0, prof_mark(plan, s), 2);
@@ -2380,19 +2268,21 @@ dmel_status backward_fb_impl(dmel_plan* plan, const float* x, int32_t batch, flo
 }
 }  // namespace
 
-extern "C" {
-
 dmel_status dmel_backward_fb(dmel_plan* plan, const float* x, int32_t batch, float lambd, uint32_t flags,
                              const float* grad_out, const float* out, float* grad_fb, void* stream)
 {
-    return backward_fb_impl(plan, x, batch, lambd, nullptr, 0, flags, grad_out, out, grad_fb, stream);
+    FbGradCall c;
+    c.x = x; c.batch = batch; c.lambd = lambd; c.flags = flags; c.grad_out = grad_out; c.out = out; c.grad_fb = grad_fb;
+    return backward_fb_impl(plan, c, stream);
 }
 
 dmel_status dmel_backward_fb_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft, uint32_t flags,
                                  const float* grad_out, const float* out, float* grad_fb, void* stream)
 {
     if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
-    return backward_fb_impl(plan, x, batch, 0.f, lambd_dev, n_fft, flags, grad_out, out, grad_fb, stream);
+    FbGradCall c;
+    c.x = x; c.batch = batch; c.lambd_dev = lambd_dev; c.n_fft_dev = n_fft; c.flags = flags; c.grad_out = grad_out; c.out = out; c.grad_fb = grad_fb;
+    return backward_fb_impl(plan, c, stream);
 }
 
 dmel_status dmel_backward_fb_saved(dmel_plan* plan, const float* spec, int32_t batch, int32_t n_fft, uint32_t flags,
@@ -2401,7 +2291,9 @@ dmel_status dmel_backward_fb_saved(dmel_plan* plan, const float* spec, int32_t b
     if (!spec) return fail(DMEL_ERR_INVALID_ARGUMENT, "spec is NULL");
     if (flags & DMEL_FLAG_FULL_WINDOW) return fail(DMEL_ERR_UNSUPPORTED, "dmel_backward_fb_saved: not with DMEL_FLAG_FULL_WINDOW");
     if (n_fft < 2 || (n_fft & 1)) return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be the (even) transform length the spectrogram was computed with");
-    return backward_fb_impl(plan, nullptr, batch, 0.f, nullptr, n_fft, flags, grad_out, out, grad_fb, stream, spec);
+    FbGradCall c;
+    c.batch = batch; c.n_fft_dev = n_fft; c.flags = flags; c.grad_out = grad_out; c.out = out; c.grad_fb = grad_fb; c.saved_spec = spec;
+    return backward_fb_impl(plan, c, stream);
 }
 
 dmel_status dmel_backward_fb_saved_dl(dmel_plan* plan, const float* spec, int32_t batch, int32_t n_fft, uint32_t flags,
@@ -2413,27 +2305,56 @@ dmel_status dmel_backward_fb_saved_dl(dmel_plan* plan, const float* spec, int32_
     if (batch <= 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_fb_saved_dl: batch must be positive");
     if (flags & DMEL_FLAG_FULL_WINDOW) return fail(DMEL_ERR_UNSUPPORTED, "dmel_backward_fb_saved_dl: not with DMEL_FLAG_FULL_WINDOW");
     if (n_fft < 2 || (n_fft & 1)) return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be the (even) transform length the spectrogram was computed with");
-    const DotRider rider{tangent, dlambd, scratch};
-    return backward_fb_impl(plan, nullptr, batch, 0.f, nullptr, n_fft, flags, grad_out, out, grad_fb, stream, spec, &rider);
+    FbGradCall c;
+    c.batch = batch; c.n_fft_dev = n_fft; c.flags = flags; c.grad_out = grad_out; c.out = out; c.grad_fb = grad_fb; c.saved_spec = spec;
+    c.tangent = tangent; c.dlambd = dlambd; c.scratch = scratch;
+    return backward_fb_impl(plan, c, stream);
 }
 
-}  // extern "C"
-
 namespace {
-// gradient w.r.t. the waveform on the power-of-two transforms: the mel layer (spec_mode 0; n_over / win_half describe the
-// optimized=False branch) and the spectrogram layer (spec_mode 1: grad_out is the gradient of the power spectrogram)
-// lambd_dev != nullptr: lambd is read by the kernels (window tables, the wave kernel's own window); the transform length then comes
-// from the caller (n_over), never from a host copy of lambd
-dmel_status backward_x_impl(dmel_plan* plan, const float* x, int32_t batch, float lambd, int n_over, int win_half, int spec_mode, bool log,
-                            const float* grad_out, const float* out, float* grad_x, void* stream, const float* lambd_dev = nullptr,
-                            bool check_nfft = false, const int32_t* lengths = nullptr)
+// The rows the x-gradient kernels leave in the workspace at n_fft N (mels = 0: the spectrogram layer).  n_fft 32 ... 2048: the wave-FFT kernel leaves one
+// overlap-added segment per tile of frames (and, for short clips with the plain Gaussian window, forms window and clip sum itself: own_prep); else a row per frame
+struct XgShape { bool wave, own_prep; int fpt, tiles, span, ts; size_t frame_floats, csum_doubles; };
+
+// false: the segment of a tile does not fit 30 bits (hop_length too large); the sizes are filled in either way
+bool xgrad_shape(const dmel_plan* pl, int N, int batch, int mels, int win_half, XgShape* r)
 {
-    if (lambd_dev && n_over <= 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd on the device needs an explicit n_fft");
-    { dmel_status sa = check_store_aligned(lengths ? "dmel_backward_x_lengths" : "dmel_backward_x", {{"grad_x", grad_x}}); if (sa != DMEL_OK) return sa; }
-    const int N = n_over > 0 ? n_over : dmel_n_fft(lambd);
+    const bool lds = N > dmel::kMaxNfft || (N & (N - 1));             // (dmel_big.hip, both directions: one row per frame too)
+    const int win_n = win_half ? N : N / 2 + 1;             // the plain Gaussian is symmetric about N/2 (the whole-clip window need not be)
+    r->fpt = 0;
+    r->wave = !lds && dmel::xgrad_wave_shape(N, mels, win_n, &r->fpt) && std::getenv("DMEL_XGRAD_LDS") == nullptr;
+    r->own_prep = r->wave && !win_half && !pl->cfg.normalize_window && pl->cfg.n_points <= 32768 && std::getenv("DMEL_XGRAD_PREP") == nullptr;
+    r->tiles = r->wave ? (pl->T + r->fpt - 1) / r->fpt : 0;
+    const long long span = r->wave ? (long long)(r->fpt - 1) * pl->cfg.hop_length + N : 0;
+    r->span = (int)span;
+    r->ts = r->wave ? r->fpt * pl->cfg.hop_length : 0;
+    const size_t rows = r->wave ? (size_t)r->tiles : (size_t)pl->T, row_len = r->wave ? (size_t)span : (size_t)N;
+    r->frame_floats = ((size_t)batch * rows * row_len + 63) / 64 * 64;
+    r->csum_doubles = (size_t)batch * rows;                 // one fp64 sum per frame / tile
+    return span <= 0x3fffffffLL;
+}
+
+// gradient w.r.t. the waveform: the mel layer (spec_mode 0; n_over / win_half describe the optimized=False branch) and the spectrogram layer (spec_mode 1:
+// grad_out is the gradient of the power spectrogram).  lambd_dev: lambd is read by the kernels; the transform length then comes from the caller (n_over)
+struct XgradCall {
+    const float* x = nullptr; int batch = 0; uint32_t flags = 0; const float* grad_out = nullptr; const float* out = nullptr; float* grad_x = nullptr;
+    float lambd = 0.f; const float* lambd_dev = nullptr; int n_over = 0, win_half = 0, spec_mode = 0; const int32_t* lengths = nullptr;   // the scalar layers
+    int channels = 0; const int32_t* edges = nullptr; const char* who = "";          // the K-window layers: validated band edges or nullptr, the entry point's name
+    XgradCall(const float* x_, int batch_, uint32_t flags_, const float* grad_out_, const float* out_, float* grad_x_)      // what every entry point fills alike
+        : x(x_), batch(batch_), flags(flags_), grad_out(grad_out_), out(out_), grad_x(grad_x_) {}
+    bool log() const { return (flags & DMEL_FLAG_LOG) != 0; }
+    bool check_nfft() const { return (flags & DMEL_FLAG_CHECK_NFFT) != 0; }
+};
+
+dmel_status backward_x_impl(dmel_plan* plan, const XgradCall& c, void* stream)
+{
+    const int batch = c.batch, win_half = c.win_half;
+    if (c.lambd_dev && c.n_over <= 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd on the device needs an explicit n_fft");
+    { dmel_status sa = check_store_aligned(c.lengths ? "dmel_backward_x_lengths" : "dmel_backward_x", {{"grad_x", c.grad_x}}); if (sa != DMEL_OK) return sa; }
+    const int N = c.n_over > 0 ? c.n_over : dmel_n_fft(c.lambd);
     const bool big = N > dmel::kMaxNfft || (N & (N - 1));              // dmel_big.hip: chirp-z / global-memory FFT, both directions
     // per-clip lengths (dmel_xgrad_len.hip): the range of the lengths forward, the mel layer's Gaussian window
-    if (lengths && (big || N < dmel::kMinFastNfft || spec_mode || win_half))
+    if (c.lengths && (big || N < dmel::kMinFastNfft || c.spec_mode || win_half))
         return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform with per-clip lengths: n_fft 32 ... 16384 (n_fft = " + std::to_string(N) + ")");
     if (N < 1 || N > dmel::kMaxBigFft || (big && (N & 1)))
         return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: n_fft = " + std::to_string(N) + " (even lengths up to " +
@@ -2450,74 +2371,58 @@ dmel_status backward_x_impl(dmel_plan* plan, const float* x, int32_t batch, floa
     dmel_plan::BigTab bt;
     const float2* big_tw = nullptr;
     if (big && (st = big_tables_for(plan, N, &bt, &big_tw)) != DMEL_OK) return st;
-    // n_fft 32 ... 2048: the wave-FFT kernel leaves one overlap-added segment per tile of frames; otherwise one row per frame
-    int fpt = 0;
-    const int win_n = win_half ? N : N / 2 + 1;             // the plain Gaussian is symmetric about N/2 (the whole-clip window need not be)
-    const bool wave_path = !big && dmel::xgrad_wave_shape(N, spec_mode ? 0 : plan->cfg.n_mels, win_n, &fpt) && std::getenv("DMEL_XGRAD_LDS") == nullptr;
-    const int tiles = wave_path ? (plan->T + fpt - 1) / fpt : 0;
-    const long long span = wave_path ? (long long)(fpt - 1) * plan->cfg.hop_length + N : 0;
-    if (span > 0x3fffffffLL) return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: hop_length too large");
-    const size_t rows = wave_path ? (size_t)tiles : (size_t)plan->T, row_len = wave_path ? (size_t)span : (size_t)N;
-    const size_t frame_floats = ((size_t)batch * rows * row_len + 63) / 64 * 64;
-    size_t need = frame_floats + 2 * (size_t)batch * rows + 16;    // + one fp64 sum per frame / tile
-    if (check_nfft && !is_capturing(s)) {
+    const int mels = c.spec_mode ? 0 : plan->cfg.n_mels;
+    XgShape sh;
+    if (!xgrad_shape(plan, N, batch, mels, win_half, &sh)) return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: hop_length too large");
+    size_t need = sh.frame_floats + 2 * sh.csum_doubles + 16;
+    if (c.check_nfft() && !is_capturing(s)) {
         // One call per candidate n_fft of a tracked forward (DMEL_FLAG_CHECK_NFFT): a step captured later may hold a neighbour -- 2 n_fft
         // or n_fft / 2 -- that no eager call has run yet (GraphedStep captures with the launches lambd can reach, not the ones the warm-up
         // happened to issue), and a workspace cannot grow under capture.  Size it here for the neighbours too (a re-capture
         // near an n_fft boundary raised in the middle of training).
         for (int nn : {N / 2, 2 * N}) {
+            XgShape s2;
             if (nn < 2 || nn > dmel::kMaxNfft || (nn & (nn - 1))) continue;
-            int fq = 0;
-            const bool wp = dmel::xgrad_wave_shape(nn, spec_mode ? 0 : plan->cfg.n_mels, win_half ? nn : nn / 2 + 1, &fq) && std::getenv("DMEL_XGRAD_LDS") == nullptr;
-            const size_t r2 = wp ? (size_t)((plan->T + fq - 1) / fq) : (size_t)plan->T;
-            const size_t l2 = wp ? (size_t)(fq - 1) * plan->cfg.hop_length + nn : (size_t)nn;
-            need = std::max(need, ((size_t)batch * r2 * l2 + 63) / 64 * 64 + 2 * (size_t)batch * r2 + 16);
+            xgrad_shape(plan, nn, batch, mels, win_half, &s2);
+            need = std::max(need, s2.frame_floats + 2 * s2.csum_doubles + 16);
         }
     }
-    if (need > plan->fbw_floats) {
-        if (is_capturing(s)) return fail(DMEL_ERR_INVALID_ARGUMENT, "workspace must grow but the stream is capturing: run one call eagerly first");
-        DMEL_HIP(hipStreamSynchronize(s));
-        (void)hipFree(plan->fbw); plan->fbw = nullptr; plan->fbw_floats = 0;
-        DMEL_HIP(hipMalloc(&plan->fbw, need * sizeof(float)));
-        plan->fbw_floats = need;
-    }
+    if ((st = grow_floats(&plan->fbw, &plan->fbw_floats, need, s, "")) != DMEL_OK) return st;
     // the big path's window table and (sequences longer than LDS) per-workgroup workspace are plan-owned, like the forward's
     const long long units = (long long)batch * ((plan->T + 1) / 2);
     const int big_grid = big ? dmel::big_grid(units, bt.M) : 0;
     if (big && (st = grow_big_workspace(plan, N, dmel::big_uses_global(bt.M) ? (size_t)big_grid * bt.M : 0, s)) != DMEL_OK) return st;
     // clip sums + window table (the tangent half of the table is not used here)
     dmel::PrepParams pp{};
-    pp.x = x; pp.psum = sc.psum; pp.win2 = big ? plan->big_win : sc.win;
+    pp.x = c.x; pp.psum = sc.psum; pp.win2 = big ? plan->big_win : sc.win;
     pp.B = batch; pp.L = plan->cfg.n_points; pp.nchunks = plan->nchunks; pp.chunk = plan->chunk;
     pp.N = N; pp.normalize = plan->cfg.normalize_window; pp.win_half = win_half;
     pp.center = window_center(N, win_half);
-    pp.lam.dev = lambd_dev; pp.lam.val = lambd_dev ? 0.f : lambd; pp.lam.role = dmel::kLamQuiet;
-    pp.lengths = lengths;                                   // the partial sums then stop at the clip's end, as in the forward
-    // short clips with the plain Gaussian window: the wave-FFT kernel evaluates the window and adds up its clip itself
-    const bool own_prep = wave_path && !win_half && !plan->cfg.normalize_window && plan->cfg.n_points <= 32768 && std::getenv("DMEL_XGRAD_PREP") == nullptr;
-    if (!own_prep) DMEL_HIP(dmel::launch_prep(pp, s));
+    pp.lam.dev = c.lambd_dev; pp.lam.val = c.lambd_dev ? 0.f : c.lambd; pp.lam.role = dmel::kLamQuiet;
+    pp.lengths = c.lengths;                                 // the partial sums then stop at the clip's end, as in the forward
+    if (!sh.own_prep) DMEL_HIP(dmel::launch_prep(pp, s));
     dmel::XgradParams xp{};
-    xp.own_prep = own_prep ? 1 : 0; xp.win_denom = std::fabs(lambd) + 1e-15f; xp.lam_dev = lambd_dev;
-    xp.check_nfft = (check_nfft && lambd_dev && !big) ? 1 : 0;
-    xp.x = x; xp.psum = sc.psum; xp.win2 = big ? plan->big_win : sc.win; xp.tw = big ? big_tw : tb->tw_long;
+    xp.own_prep = sh.own_prep ? 1 : 0; xp.win_denom = std::fabs(c.lambd) + 1e-15f; xp.lam_dev = c.lambd_dev;
+    xp.check_nfft = (c.check_nfft() && c.lambd_dev && !big) ? 1 : 0;
+    xp.x = c.x; xp.psum = sc.psum; xp.win2 = big ? plan->big_win : sc.win; xp.tw = big ? big_tw : tb->tw_long;
     xp.chirp = big ? bt.chirp : nullptr; xp.hbr = big ? bt.hbr : nullptr; xp.zws = plan->big_z; xp.Mfft = big ? bt.M : 0; xp.logM = big ? bt.logM : 0;
-    xp.fb = tb->fb_dense; xp.rowband = tb->rowband; xp.rowpk = tb->rowpk; xp.long_rows = tb->long_rows ? 1 : 0; xp.grad_out = grad_out; xp.out = log ? out : nullptr;
-    xp.frames = plan->fbw; xp.grad_x = grad_x;
-    xp.csum = reinterpret_cast<double*>(plan->fbw + frame_floats);      // 256-byte aligned: frame_floats is a multiple of 64
+    xp.fb = tb->fb_dense; xp.rowband = tb->rowband; xp.rowpk = tb->rowpk; xp.long_rows = tb->long_rows ? 1 : 0; xp.grad_out = c.grad_out; xp.out = c.log() ? c.out : nullptr;
+    xp.frames = plan->fbw; xp.grad_x = c.grad_x;
+    xp.csum = reinterpret_cast<double*>(plan->fbw + sh.frame_floats);      // 256-byte aligned: frame_floats is a multiple of 64
     xp.B = batch; xp.L = plan->cfg.n_points; xp.T = plan->T; xp.hop = plan->cfg.hop_length; xp.M = plan->cfg.n_mels;
-    xp.nchunks = plan->nchunks; xp.N = N; xp.F = tb->F; xp.remove_dc = 1; xp.spec_mode = spec_mode;
+    xp.nchunks = plan->nchunks; xp.N = N; xp.F = tb->F; xp.remove_dc = 1; xp.spec_mode = c.spec_mode;
     xp.logN = 0; while ((1 << xp.logN) < N) ++xp.logN;
     xp.inv_L = 1.0f / (float)plan->cfg.n_points;
     xp.tw1 = tb->tw1p; xp.tw2 = tb->tw2p;
-    xp.win_n = win_n; xp.tiles = tiles; xp.span = (int)span; xp.tile_step = wave_path ? fpt * plan->cfg.hop_length : 0;
+    xp.win_n = win_half ? N : N / 2 + 1; xp.tiles = sh.tiles; xp.span = sh.span; xp.tile_step = sh.ts;
     const size_t m0 = prof_mark(plan, s);
     if (big) {
         DMEL_HIP(dmel::launch_xgrad_big(xp, big_grid, s));
         DMEL_HIP(dmel::launch_xgrad_gather(xp, s));
-    } else if (lengths) {
+    } else if (c.lengths) {
         dmel::XgradLenParams lp{};
         static_cast<dmel::XgradParams&>(lp) = xp;
-        lp.lengths = lengths; lp.fpt = wave_path ? fpt : 0;
+        lp.lengths = c.lengths; lp.fpt = sh.wave ? sh.fpt : 0;
         DMEL_HIP(dmel::launch_xgrad_len(lp, s));
     } else {
         DMEL_HIP(dmel::launch_xgrad(xp, s));
@@ -2525,22 +2430,42 @@ dmel_status backward_x_impl(dmel_plan* plan, const float* x, int32_t batch, floa
     prof_span(plan, m0, prof_mark(plan, s), 2);
     return DMEL_OK;
 }
-}  // namespace
 
-extern "C" {
+// dmel_backward_x, _dev, _lengths, _dev_lengths: the same checks in the same order under four names.  dev: lambd on the device, c.n_over the n_fft
+// this step's forward was issued for; lens: the per-clip-lengths forms (their flags are checked: they have no DMEL_FLAG_FULL_WINDOW)
+dmel_status backward_x_mel(const char* who, dmel_plan* plan, XgradCall c, bool dev, bool lens, void* stream)
+{
+    const std::string w = who;
+    const int n_fft = c.n_over;
+    if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
+    if (dev && !c.lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
+    if (c.batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch < 0");
+    if (c.batch == 0) return DMEL_OK;
+    if (!c.x || (lens && !c.lengths) || !c.grad_out || !c.grad_x)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + (lens ? ": x / lengths / grad_out / grad_x is NULL" : ": x / grad_out / grad_x is NULL"));
+    if (lens && (c.flags & ~(DMEL_FLAG_LOG | (dev ? DMEL_FLAG_CHECK_NFFT : 0u))))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + (dev ? ": flags other than LOG, CHECK_NFFT" : ": flags other than LOG"));
+    if (c.log() && !c.out) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": DMEL_FLAG_LOG needs the saved log output");
+    if (!dev && !std::isfinite(c.lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
+    const bool full = !lens && (c.flags & DMEL_FLAG_FULL_WINDOW) != 0;               // optimized=False: n_fft = 2 L, window = the clip
+    if (dev && lens && (n_fft < 1 || (n_fft & (n_fft - 1))))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be a power of two (the n_fft this step's forward was issued for)");
+    if (dev && !lens && !full && (n_fft < 1 || n_fft > dmel::kMaxNfft || (n_fft & (n_fft - 1))))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be a power of two in [1, 16384] (the n_fft this step's forward was issued for)");
+    if (dev && full && c.check_nfft())
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": DMEL_FLAG_CHECK_NFFT has no meaning with DMEL_FLAG_FULL_WINDOW (n_fft = 2 n_points)");
+    if (!dev) c.flags &= DMEL_FLAG_LOG;                                             // (DMEL_FLAG_CHECK_NFFT belongs to the device forms)
+    c.n_over = full ? 2 * plan->cfg.n_points : (dev ? n_fft : 0); c.win_half = full ? 1 : 0;
+    return backward_x_impl(plan, c, stream);
+}
+}  // namespace
 
 dmel_status dmel_backward_x(dmel_plan* plan, const float* x, int32_t batch, float lambd, uint32_t flags,
                             const float* grad_out, const float* out, float* grad_x, void* stream)
 {
-    if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
-    if (batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch < 0");
-    if (batch == 0) return DMEL_OK;
-    if (!x || !grad_out || !grad_x) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x: x / grad_out / grad_x is NULL");
-    if ((flags & DMEL_FLAG_LOG) && !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x: DMEL_FLAG_LOG needs the saved log output");
-    if (!std::isfinite(lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
-    const bool full = (flags & DMEL_FLAG_FULL_WINDOW) != 0;                      // optimized=False: n_fft = 2 L, window = the clip
-    return backward_x_impl(plan, x, batch, lambd, full ? 2 * plan->cfg.n_points : 0, full ? 1 : 0, 0, (flags & DMEL_FLAG_LOG) != 0,
-                           grad_out, out, grad_x, stream);
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.lambd = lambd;
+    return backward_x_mel("dmel_backward_x", plan, c, false, false, stream);
 }
 
 dmel_status dmel_backward_x_spec(dmel_plan* plan, const float* x, int32_t batch, float lambd, int32_t n_fft, uint32_t flags,
@@ -2552,55 +2477,33 @@ dmel_status dmel_backward_x_spec(dmel_plan* plan, const float* x, int32_t batch,
     if (!x || !grad_spec || !grad_x) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_spec: x / grad_spec / grad_x is NULL");
     if (!(flags & DMEL_SPEC_REMOVE_DC)) return fail(DMEL_ERR_UNSUPPORTED, "dmel_backward_x_spec: only the DC-removed spectrogram (models.py:187) is differentiated");
     if (!std::isfinite(lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
-    return backward_x_impl(plan, x, batch, lambd, n_fft, (flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0, 1, false, grad_spec, nullptr, grad_x, stream);
+    XgradCall c(x, batch, 0u, grad_spec, nullptr, grad_x);
+    c.lambd = lambd; c.n_over = n_fft; c.win_half = (flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0; c.spec_mode = 1;
+    return backward_x_impl(plan, c, stream);
 }
 
 dmel_status dmel_backward_x_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft, uint32_t flags,
                                 const float* grad_out, const float* out, float* grad_x, void* stream)
 {
-    if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
-    if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
-    if (batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch < 0");
-    if (batch == 0) return DMEL_OK;
-    if (!x || !grad_out || !grad_x) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev: x / grad_out / grad_x is NULL");
-    if ((flags & DMEL_FLAG_LOG) && !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev: DMEL_FLAG_LOG needs the saved log output");
-    const bool full = (flags & DMEL_FLAG_FULL_WINDOW) != 0;
-    if (!full && (n_fft < 1 || n_fft > dmel::kMaxNfft || (n_fft & (n_fft - 1))))
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be a power of two in [1, 16384] (the n_fft this step's forward was issued for)");
-    if ((flags & DMEL_FLAG_CHECK_NFFT) && full)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev: DMEL_FLAG_CHECK_NFFT has no meaning with DMEL_FLAG_FULL_WINDOW (n_fft = 2 n_points)");
-    return backward_x_impl(plan, x, batch, 0.f, full ? 2 * plan->cfg.n_points : n_fft, full ? 1 : 0, 0, (flags & DMEL_FLAG_LOG) != 0,
-                           grad_out, out, grad_x, stream, lambd_dev, (flags & DMEL_FLAG_CHECK_NFFT) != 0);
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.lambd_dev = lambd_dev; c.n_over = n_fft;
+    return backward_x_mel("dmel_backward_x_dev", plan, c, true, false, stream);
 }
 
 dmel_status dmel_backward_x_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, float lambd, uint32_t flags,
                                     const float* grad_out, const float* out, float* grad_x, void* stream)
 {
-    if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
-    if (batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch < 0");
-    if (batch == 0) return DMEL_OK;
-    if (!x || !lengths || !grad_out || !grad_x) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_lengths: x / lengths / grad_out / grad_x is NULL");
-    if (flags & ~DMEL_FLAG_LOG) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_lengths: flags other than LOG");
-    if ((flags & DMEL_FLAG_LOG) && !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_lengths: DMEL_FLAG_LOG needs the saved log output");
-    if (!std::isfinite(lambd)) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd is not finite");
-    return backward_x_impl(plan, x, batch, lambd, 0, 0, 0, (flags & DMEL_FLAG_LOG) != 0, grad_out, out, grad_x, stream, nullptr, false, lengths);
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.lambd = lambd; c.lengths = lengths;
+    return backward_x_mel("dmel_backward_x_lengths", plan, c, false, true, stream);
 }
 
 dmel_status dmel_backward_x_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
                                         int32_t n_fft, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
 {
-    if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
-    if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd_dev is NULL");
-    if (batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch < 0");
-    if (batch == 0) return DMEL_OK;
-    if (!x || !lengths || !grad_out || !grad_x)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev_lengths: x / lengths / grad_out / grad_x is NULL");
-    if (flags & ~(DMEL_FLAG_LOG | DMEL_FLAG_CHECK_NFFT)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev_lengths: flags other than LOG, CHECK_NFFT");
-    if ((flags & DMEL_FLAG_LOG) && !out) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_dev_lengths: DMEL_FLAG_LOG needs the saved log output");
-    if (n_fft < 1 || (n_fft & (n_fft - 1)))
-        return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be a power of two (the n_fft this step's forward was issued for)");
-    return backward_x_impl(plan, x, batch, 0.f, n_fft, 0, 0, (flags & DMEL_FLAG_LOG) != 0, grad_out, out, grad_x, stream, lambd_dev,
-                           (flags & DMEL_FLAG_CHECK_NFFT) != 0, lengths);
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.lambd_dev = lambd_dev; c.n_over = n_fft; c.lengths = lengths;
+    return backward_x_mel("dmel_backward_x_dev_lengths", plan, c, true, true, stream);
 }
 
 dmel_status dmel_backward_x_spec_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t n_fft, uint32_t flags,
@@ -2612,54 +2515,35 @@ dmel_status dmel_backward_x_spec_dev(dmel_plan* plan, const float* x, int32_t ba
     if (batch == 0) return DMEL_OK;
     if (!x || !grad_spec || !grad_x) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_x_spec_dev: x / grad_spec / grad_x is NULL");
     if (!(flags & DMEL_SPEC_REMOVE_DC)) return fail(DMEL_ERR_UNSUPPORTED, "dmel_backward_x_spec_dev: only the DC-removed spectrogram (models.py:187) is differentiated");
-    return backward_x_impl(plan, x, batch, 0.f, n_fft, (flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0, 1, false, grad_spec, nullptr, grad_x, stream, lambd_dev);
+    XgradCall c(x, batch, 0u, grad_spec, nullptr, grad_x);
+    c.lambd_dev = lambd_dev; c.n_over = n_fft; c.win_half = (flags & DMEL_SPEC_HALF_WINDOW) ? 1 : 0; c.spec_mode = 1;
+    return backward_x_impl(plan, c, stream);
 }
-
-}  // extern "C"
 
 namespace {
-// the multi-window layer's gradient w.r.t. the waveform: at n_fft N every channel takes the path backward_x_impl takes for the scalar layer
-// (win_half = 0): the wave-FFT kernel when the shape fits, its own window and clip mean when own_prep; the LDS frames kernel otherwise
-struct XgShape { bool wave, own_prep; int tiles, span, ts; size_t frame_floats, csum_doubles; };
-
-dmel_status xgrad_multi_shape(const dmel_plan* pl, int N, int batch, XgShape* r)
+// The K-window layers' gradient w.r.t. the waveform: c.edges == nullptr: grad_out / out are (B, K, M, T); else ONE (B, 1, M, T) image -- channel c's mel
+// gradient is its rows [edges[c], edges[c + 1]) and +0.0 elsewhere.  At n_fft N every channel takes the path backward_x_impl takes for the scalar layer
+dmel_status check_x_multi_args(dmel_plan* pl, const XgradCall& c)
 {
-    int fpt = 0;
-    r->wave = dmel::xgrad_wave_shape(N, pl->cfg.n_mels, N / 2 + 1, &fpt) && std::getenv("DMEL_XGRAD_LDS") == nullptr;
-    r->own_prep = r->wave && !pl->cfg.normalize_window && pl->cfg.n_points <= 32768 && std::getenv("DMEL_XGRAD_PREP") == nullptr;
-    r->tiles = r->wave ? (pl->T + fpt - 1) / fpt : 0;
-    const long long span = r->wave ? (long long)(fpt - 1) * pl->cfg.hop_length + N : 0;
-    if (span > 0x3fffffffLL) return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: hop_length too large");
-    r->span = (int)span;
-    r->ts = r->wave ? fpt * pl->cfg.hop_length : 0;
-    const size_t rows = r->wave ? (size_t)r->tiles : (size_t)pl->T, row_len = r->wave ? (size_t)span : (size_t)N;
-    r->frame_floats = ((size_t)batch * rows * row_len + 63) / 64 * 64;
-    r->csum_doubles = (size_t)batch * rows;
-    return DMEL_OK;
-}
-
-dmel_status check_x_multi_args(dmel_plan* pl, const float* x, int batch, int channels, uint32_t flags, const float* grad_out,
-                               const float* out, float* grad_x, const char* who)
-{
+    const std::string who = c.who;
     if (!pl) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
-    if (batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": batch < 0");
-    if (channels < 1 || channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": channels must be 1 ... 8");
-    if (flags & ~(uint32_t)DMEL_FLAG_LOG) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": only DMEL_FLAG_LOG is accepted");
-    if (batch > 0 && (!x || !grad_out || !grad_x)) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": x / grad_out / grad_x is NULL");
-    if (batch > 0 && (flags & DMEL_FLAG_LOG) && !out) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": DMEL_FLAG_LOG needs the saved log output");
-    if ((long long)batch * channels > 65534) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch x channels > 65534 (split the call)");
+    if (c.batch < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": batch < 0");
+    if (c.channels < 1 || c.channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": channels must be 1 ... 8");
+    if (c.flags & ~(uint32_t)DMEL_FLAG_LOG) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": only DMEL_FLAG_LOG is accepted");
+    if (c.batch > 0 && (!c.x || !c.grad_out || !c.grad_x)) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": x / grad_out / grad_x is NULL");
+    if (c.batch > 0 && (c.flags & DMEL_FLAG_LOG) && !c.out) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": DMEL_FLAG_LOG needs the saved log output");
+    if ((long long)c.batch * c.channels > 65534) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch x channels > 65534 (split the call)");
     return DMEL_OK;
 }
 
-// ns / mask / nl: the launch list (checked by the caller); lam_host (K values) or lam_dev (K device words) -- exactly one of them.
-// edges (K + 1 validated band edges) or nullptr: the band-split layer, whose grad_out / out are ONE (B, 1, M, T) image -- channel c's mel
-// gradient is its rows [edges[c], edges[c + 1]) and +0.0 elsewhere -- or the multi-window layer's (B, K, M, T)
-dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, const float* lam_host, const float* lam_dev, int channels,
-                                  const int* ns, const uint32_t* mask, int nl, bool log, const float* grad_out, const float* out,
-                                  float* grad_x, void* stream, const int32_t* edges = nullptr)
+// ll: the launch list (checked by the caller); lam_host (K values) or lam_dev (K device words) -- exactly one of them
+dmel_status backward_x_multi_impl(dmel_plan* plan, const XgradCall& xc, const float* lam_host, const float* lam_dev, const LaunchList& ll, void* stream)
 {
+    const int batch = xc.batch, channels = xc.channels, nl = ll.nl;
+    const int* ns = ll.ns; const uint32_t* mask = ll.mask;
+    const int32_t* edges = xc.edges;
     const std::string who = edges ? "dmel_backward_x_band" : "dmel_backward_x_multi";
-    { dmel_status sa = check_store_aligned(who.c_str(), {{"grad_x", grad_x}}); if (sa != DMEL_OK) return sa; }
+    { dmel_status sa = check_store_aligned(who.c_str(), {{"grad_x", xc.grad_x}}); if (sa != DMEL_OK) return sa; }
     { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2675,7 +2559,7 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
         for (int n : {ns[i], ns[i] / 2, 2 * ns[i]}) {
             if (!multi_in_range(n) || shape.count(n) || (capturing && n != ns[i])) continue;      // eager: the neighbours too (see below)
             XgShape sh;
-            if ((st = xgrad_multi_shape(plan, n, batch, &sh)) != DMEL_OK) return st;
+            if (!xgrad_shape(plan, n, batch, plan->cfg.n_mels, 0, &sh)) return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: hop_length too large");
             shape[n] = sh;
         }
     NfftTables* tb[3 * dmel::kMaxChannels] = {};
@@ -2699,13 +2583,7 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
     const size_t win_floats = any_prep ? (size_t)channels * dmel::kXgMaxCand * dmel::kMaxNfft * 2 : 0;
     const size_t stage_floats = any_lds ? (2 * bmt + 63) / 64 * 64 : 0;
     const size_t need = (size_t)channels * region + win_floats + stage_floats + 16;
-    if (need > plan->xmw_floats) {
-        if (capturing) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": the workspace must grow but the stream is capturing: run one call eagerly first");
-        DMEL_HIP(hipStreamSynchronize(s));
-        (void)hipFree(plan->xmw); plan->xmw = nullptr; plan->xmw_floats = 0;
-        DMEL_HIP(hipMalloc(&plan->xmw, need * sizeof(float)));
-        plan->xmw_floats = need;
-    }
+    if ((st = grow_floats(&plan->xmw, &plan->xmw_floats, need, s, who + ": the ")) != DMEL_OK) return st;
     float* frames[dmel::kMaxChannels] = {};
     double* csum[dmel::kMaxChannels] = {};
     for (int c = 0; c < channels; ++c) {
@@ -2728,7 +2606,7 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
             for (int c = 0; c < channels; ++c) {
                 if (!(mask[i] >> c & 1u)) continue;
                 dmel::PrepParams pp{};
-                pp.x = x; pp.psum = sc.psum; pp.win2 = table(c, N);
+                pp.x = xc.x; pp.psum = sc.psum; pp.win2 = table(c, N);
                 pp.B = batch; pp.L = L; pp.nchunks = plan->nchunks; pp.chunk = plan->chunk;
                 pp.N = N; pp.normalize = plan->cfg.normalize_window; pp.win_half = 0; pp.center = (float)N / 2.0f;
                 pp.lam.dev = lam_dev ? lam_dev + c : nullptr; pp.lam.val = lam_dev ? 0.f : lam_host[c]; pp.lam.role = dmel::kLamQuiet;
@@ -2736,9 +2614,9 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
             }
         dmel::XgradParams xp{};
         xp.own_prep = sh.own_prep ? 1 : 0; xp.lam_dev = lam_dev; xp.check_nfft = lam_dev ? 1 : 0;
-        xp.x = x; xp.psum = sc.psum; xp.tw = tb[i]->tw_long;
+        xp.x = xc.x; xp.psum = sc.psum; xp.tw = tb[i]->tw_long;
         xp.fb = tb[i]->fb_dense; xp.rowband = tb[i]->rowband; xp.rowpk = tb[i]->rowpk; xp.long_rows = tb[i]->long_rows ? 1 : 0;
-        xp.grad_out = grad_out; xp.out = log ? out : nullptr; xp.grad_x = grad_x;
+        xp.grad_out = xc.grad_out; xp.out = xc.log() ? xc.out : nullptr; xp.grad_x = xc.grad_x;
         xp.B = batch; xp.L = L; xp.T = T; xp.hop = plan->cfg.hop_length; xp.M = M;
         xp.nchunks = plan->nchunks; xp.N = N; xp.F = tb[i]->F; xp.remove_dc = 1; xp.spec_mode = 0;
         xp.logN = 0; while ((1 << xp.logN) < N) ++xp.logN;
@@ -2759,22 +2637,21 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
             if ((long long)batch * sh.tiles * mp.count > 0x7fffffffLL) return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: grid too large");
             DMEL_HIP(edges ? dmel::launch_xgrad_wave_band(mp, s) : dmel::launch_xgrad_wave_multi(mp, s));
         } else {
-            // the LDS path (cold): per channel, its rows of grad_out / out staged as (B, M, T) -- a strided copy of its image, or the
-            // band-split layer's masking kernel over the one image -- then the scalar frames kernel
+            // the LDS path (cold): per channel, its rows of grad_out / out staged as (B, M, T) -- strided copy or the band layer's masking kernel -- then the frames kernel
             for (int c = 0; c < channels; ++c) {
                 if (!(mask[i] >> c & 1u)) continue;
                 const size_t row = (size_t)M * T * sizeof(float);
                 if (edges) {
                     dmel::XgradBandStageParams sp{};
-                    sp.grad_out = grad_out; sp.out = log ? out : nullptr; sp.stage_grad = stage; sp.stage_out = stage + bmt;
+                    sp.grad_out = xc.grad_out; sp.out = xc.log() ? xc.out : nullptr; sp.stage_grad = stage; sp.stage_out = stage + bmt;
                     sp.M = M; sp.T = T; sp.e_lo = edges[c]; sp.e_hi = edges[c + 1]; sp.n = (long long)bmt;
                     DMEL_HIP(dmel::launch_xgrad_band_stage(sp, s));
                 } else {
-                    DMEL_HIP(hipMemcpy2DAsync(stage, row, grad_out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
-                    if (log) DMEL_HIP(hipMemcpy2DAsync(stage + bmt, row, out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
+                    DMEL_HIP(hipMemcpy2DAsync(stage, row, xc.grad_out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
+                    if (xc.log()) DMEL_HIP(hipMemcpy2DAsync(stage + bmt, row, xc.out + (size_t)c * M * T, row * channels, row, batch, hipMemcpyDeviceToDevice, s));
                 }
                 dmel::XgradParams q = xp;
-                q.grad_out = stage; q.out = log ? stage + bmt : nullptr;
+                q.grad_out = stage; q.out = xc.log() ? stage + bmt : nullptr;
                 q.win2 = table(c, N); q.frames = frames[c]; q.csum = csum[c];
                 q.lam_dev = lam_dev ? lam_dev + c : nullptr;
                 DMEL_HIP(dmel::launch_xgrad_frames(q, s));
@@ -2783,7 +2660,7 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
     }
     // one combine: the channels' terms in ascending channel order
     dmel::XgradCombineMultiParams cp{};
-    cp.grad_x = grad_x; cp.lam_dev = lam_dev; cp.L = L; cp.T = T; cp.hop = plan->cfg.hop_length; cp.channels = channels;
+    cp.grad_x = xc.grad_x; cp.lam_dev = lam_dev; cp.L = L; cp.T = T; cp.hop = plan->cfg.hop_length; cp.channels = channels;
     for (int c = 0; c < channels; ++c) {
         cp.ncand[c] = ncand[c]; cp.frames[c] = frames[c]; cp.csum[c] = csum[c];
         for (int j = 0; j < ncand[c]; ++j) {
@@ -2795,48 +2672,32 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const float* x, int batch, co
     prof_span(plan, m0, prof_mark(plan, s), 2);
     return DMEL_OK;
 }
-}  // namespace
 
-extern "C" {
-
-}  // extern "C"
-
-namespace {
-// dmel_backward_x_multi / dmel_backward_x_band (edges: validated, or nullptr)
-dmel_status backward_x_multi_host(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels, const int32_t* edges,
-                                  uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream, const std::string& who)
+// dmel_backward_x_multi / dmel_backward_x_band (c.edges: validated, or nullptr)
+dmel_status backward_x_multi_host(dmel_plan* plan, const XgradCall& c, const float* lambd_host, void* stream)
 {
-    dmel_status st = check_x_multi_args(plan, x, batch, channels, flags, grad_out, out, grad_x, who.c_str());
+    dmel_status st = check_x_multi_args(plan, c);
     if (st != DMEL_OK) return st;
-    if (!lambd_host) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": lambd_host is NULL");
-    std::map<int, uint32_t> u;
-    for (int c = 0; c < channels; ++c) {
-        if (!std::isfinite(lambd_host[c])) return fail(DMEL_ERR_INVALID_ARGUMENT, "lambd of channel " + std::to_string(c) + " is not finite");
-        const int n = dmel_n_fft(lambd_host[c]);
-        if (!multi_in_range(n))
-            return fail(DMEL_ERR_UNSUPPORTED, "channel " + std::to_string(c) + ": lambd = " + std::to_string(lambd_host[c]) + " gives n_fft " +
-                        std::to_string(n) + ", the multi-window layer serves 32 ... 16384");
-        u[n] |= 1u << c;
-    }
-    if (batch == 0) return DMEL_OK;
-    int ns[dmel::kMaxChannels]; uint32_t mask[dmel::kMaxChannels]; int nl = 0;
-    for (const auto& kv : u) { ns[nl] = kv.first; mask[nl] = kv.second; ++nl; }
-    return backward_x_multi_impl(plan, x, batch, lambd_host, nullptr, channels, ns, mask, nl, (flags & DMEL_FLAG_LOG) != 0, grad_out, out,
-                                 grad_x, stream, edges);
+    if (!lambd_host) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(c.who) + ": lambd_host is NULL");
+    if ((st = check_lambd_multi(lambd_host, c.channels)) != DMEL_OK) return st;
+    if (c.batch == 0) return DMEL_OK;
+    return backward_x_multi_impl(plan, c, lambd_host, nullptr, group_host_values(lambd_host, c.channels), stream);
 }
 
-// dmel_backward_x_multi_dev / dmel_backward_x_band_dev (edges: validated, or nullptr)
-dmel_status backward_x_multi_devlist(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels, const int32_t* edges,
-                                     const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count, uint32_t flags,
-                                     const float* grad_out, const float* out, float* grad_x, void* stream, const std::string& who)
+// dmel_backward_x_multi_dev / dmel_backward_x_band_dev (c.edges: validated, or nullptr)
+dmel_status backward_x_multi_devlist(dmel_plan* plan, const XgradCall& c, const float* lambd_dev, const int32_t* n_ffts,
+                                     const uint32_t* channel_masks, int32_t count, void* stream)
 {
-    dmel_status st = check_x_multi_args(plan, x, batch, channels, flags, grad_out, out, grad_x, who.c_str());
+    const std::string who = c.who;
+    const int channels = c.channels;
+    dmel_status st = check_x_multi_args(plan, c);
     if (st != DMEL_OK) return st;
     if (!lambd_dev) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": lambd_dev is NULL");
     if (!n_ffts || !channel_masks || count < 1 || count > 3 * dmel::kMaxChannels)
         return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": the launch list (n_ffts, channel_masks, count) is missing or empty");
     uint32_t seen = 0;
     int per[dmel::kMaxChannels] = {};
+    LaunchList ll;
     for (int i = 0; i < count; ++i) {
         const int n = n_ffts[i];
         if (!multi_in_range(n) || (n & (n - 1)))
@@ -2846,31 +2707,33 @@ dmel_status backward_x_multi_devlist(dmel_plan* plan, const float* x, int32_t ba
         if (channel_masks[i] == 0 || (channels < 32 && (channel_masks[i] >> channels) != 0))
             return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": channel_masks[" + std::to_string(i) + "] is empty or names a channel >= channels");
         seen |= channel_masks[i];
-        for (int c = 0; c < channels; ++c)
-            if ((channel_masks[i] >> c & 1u) && ++per[c] > dmel::kXgMaxCand)
-                return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": channel " + std::to_string(c) + " is in more than 3 launches");
+        for (int ch = 0; ch < channels; ++ch)
+            if ((channel_masks[i] >> ch & 1u) && ++per[ch] > dmel::kXgMaxCand)
+                return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": channel " + std::to_string(ch) + " is in more than 3 launches");
+        ll.ns[i] = n; ll.mask[i] = channel_masks[i]; ll.nl = i + 1;
     }
     if (seen != (1u << channels) - 1u) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": a channel is in no launch");
-    if (batch == 0) return DMEL_OK;
-    return backward_x_multi_impl(plan, x, batch, nullptr, lambd_dev, channels, n_ffts, channel_masks, count, (flags & DMEL_FLAG_LOG) != 0,
-                                 grad_out, out, grad_x, stream, edges);
+    if (c.batch == 0) return DMEL_OK;
+    return backward_x_multi_impl(plan, c, nullptr, lambd_dev, ll, stream);
 }
-}  // namespace
 
-extern "C" {
+}  // namespace
 
 dmel_status dmel_backward_x_multi(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels,
                                   uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
 {
-    return backward_x_multi_host(plan, x, batch, lambd_host, channels, nullptr, flags, grad_out, out, grad_x, stream, "dmel_backward_x_multi");
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.channels = channels; c.who = "dmel_backward_x_multi";
+    return backward_x_multi_host(plan, c, lambd_host, stream);
 }
 
 dmel_status dmel_backward_x_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
                                       const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count, uint32_t flags,
                                       const float* grad_out, const float* out, float* grad_x, void* stream)
 {
-    return backward_x_multi_devlist(plan, x, batch, lambd_dev, channels, nullptr, n_ffts, channel_masks, count, flags, grad_out, out, grad_x,
-                                    stream, "dmel_backward_x_multi_dev");
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.channels = channels; c.who = "dmel_backward_x_multi_dev";
+    return backward_x_multi_devlist(plan, c, lambd_dev, n_ffts, channel_masks, count, stream);
 }
 
 // the band-split layer's gradient w.r.t. the waveform: dmel_backward_x_multi(_dev) over ONE (B, 1, M, T) cotangent (and saved log output),
@@ -2878,25 +2741,26 @@ dmel_status dmel_backward_x_multi_dev(dmel_plan* plan, const float* x, int32_t b
 dmel_status dmel_backward_x_band(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_host, int32_t channels,
                                  const int32_t* band_edges, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
 {
-    dmel_status st = check_band_edges(band_edges, channels, "dmel_backward_x_band");
+    BandEdges be;
+    const dmel_status st = take_band_edges(plan, band_edges, channels, "dmel_backward_x_band", &be);
     if (st != DMEL_OK) return st;
-    if ((st = check_band_plan(plan, band_edges, channels, "dmel_backward_x_band")) != DMEL_OK) return st;
-    int32_t edges[dmel::kMaxChannels + 1];
-    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
-    return backward_x_multi_host(plan, x, batch, lambd_host, channels, edges, flags, grad_out, out, grad_x, stream, "dmel_backward_x_band");
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.channels = channels; c.who = "dmel_backward_x_band";
+    c.edges = be.e;
+    return backward_x_multi_host(plan, c, lambd_host, stream);
 }
 
 dmel_status dmel_backward_x_band_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
                                      const int32_t* band_edges, const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count,
                                      uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
 {
-    dmel_status st = check_band_edges(band_edges, channels, "dmel_backward_x_band_dev");
+    BandEdges be;
+    const dmel_status st = take_band_edges(plan, band_edges, channels, "dmel_backward_x_band_dev", &be);
     if (st != DMEL_OK) return st;
-    if ((st = check_band_plan(plan, band_edges, channels, "dmel_backward_x_band_dev")) != DMEL_OK) return st;
-    int32_t edges[dmel::kMaxChannels + 1];
-    for (int c = 0; c <= channels; ++c) edges[c] = band_edges[c];
-    return backward_x_multi_devlist(plan, x, batch, lambd_dev, channels, edges, n_ffts, channel_masks, count, flags, grad_out, out, grad_x,
-                                    stream, "dmel_backward_x_band_dev");
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.channels = channels; c.who = "dmel_backward_x_band_dev";
+    c.edges = be.e;
+    return backward_x_multi_devlist(plan, c, lambd_dev, n_ffts, channel_masks, count, stream);
 }
 
 dmel_status dmel_plan_last_multi_launch(dmel_plan* plan, int32_t* n_ffts, uint32_t* channel_masks, int32_t* count)

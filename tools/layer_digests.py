@@ -1,10 +1,12 @@
 """SHA-256 digests of what the Python layer returns, for comparing two versions of the host code (layer.py, capi.py) bit for bit.
 
     python tools/layer_digests.py --package OLD_PKG_DIR --package differentiable-mel-spectrogram_amd [--lib-dir DIR] [--out FILE]
+    python tools/layer_digests.py --package PKG --lib-dir OLD_LIB_DIR --package PKG --lib-dir NEW_LIB_DIR
 
 Every ``--package`` is a directory holding the package's Python files; each is imported as ``dmel_amd`` in a fresh child process (with a
 time limit) and runs against the SAME shared objects: ``libdmel_hip.so`` / ``libdmel_torch.so`` of ``--lib-dir`` (default: the
-repository's package directory; ``DMEL_LIB`` still overrides the first).  A child prints one digest per tensor -- ``out``,
+repository's package directory; ``DMEL_LIB`` still overrides the first).  ``--lib-dir`` may repeat, once per ``--package`` and paired with
+them in order: the same Python files then run against two builds of the libraries (two versions of the C++ host code).  A child prints one digest per tensor -- ``out``,
 ``lambd.grad`` and, where the path has one, ``x.grad`` / ``mel_fb.grad`` -- for seeded inputs (3 clips of 2000 samples, 16 mel bands, hop
 100, 16 kHz; lambd 10 and 40; log on and off; fp32 and bf16 output) over every path of the four layer classes and ``dmel_log_mel``.  An
 exception is digested as its type and message, so the refusals that need a device are compared too.  NaN rows are hashed like any other
@@ -162,21 +164,32 @@ def _moved(layer):
     return layer
 
 
+def pair_lib_dirs(ap, packages, lib_dirs):
+    """one library directory per package: the default, the one given for all, or as many as packages, in order"""
+    lib_dirs = lib_dirs or [DEFAULT_PKG]
+    if len(lib_dirs) == 1:
+        return lib_dirs * len(packages)
+    if len(lib_dirs) != len(packages):
+        ap.error(f"{len(lib_dirs)} --lib-dir for {len(packages)} --package: give one, or one per package")
+    return lib_dirs
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--package", action="append", help="package directory to import as dmel_amd (give two to compare)")
-    ap.add_argument("--lib-dir", default=DEFAULT_PKG, help="directory of libdmel_hip.so and libdmel_torch.so")
+    ap.add_argument("--lib-dir", action="append", help="directory of libdmel_hip.so and libdmel_torch.so: one for all packages, or one per package")
     ap.add_argument("--timeout", type=float, default=240.0, help="time limit of one child, seconds")
     ap.add_argument("--out", help="also write the table here")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     packages = args.package or [DEFAULT_PKG]
+    lib_dirs = pair_lib_dirs(ap, packages, args.lib_dir)
     if args.child:
-        child(packages[0], args.lib_dir)
+        child(packages[0], lib_dirs[0])
         return 0
     tables = []
-    for pkg in packages:
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--package", pkg, "--lib-dir", args.lib_dir]
+    for pkg, lib_dir in zip(packages, lib_dirs):
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--package", pkg, "--lib-dir", lib_dir]
         try:
             res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=args.timeout)
         except subprocess.TimeoutExpired:

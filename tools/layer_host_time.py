@@ -1,6 +1,7 @@
 """Host time of the eager layer for two versions of the Python host code (layer.py, capi.py) on the same shared objects.
 
     python tools/layer_host_time.py --package OLD_PKG_DIR --package differentiable-mel-spectrogram_amd [--rounds 5] [--calls 2000]
+    python tools/layer_host_time.py --package PKG --lib-dir OLD_LIB_DIR --package PKG --lib-dir NEW_LIB_DIR
 
 The packages are imported as ``tools/layer_digests.py`` does, alternating, each round in a fresh child process with a time limit.  A child
 times three loops at the digest shapes (3 clips of 2000 samples, 16 mel bands, hop 100, lambd 40, log on, fp32): ``layer(x)`` under
@@ -8,6 +9,7 @@ times three loops at the digest shapes (3 clips of 2000 samples, 16 mel bands, h
 step with ``x.requires_grad`` (the tracked path through a Python autograd Function).  Wall time over one train of ``--calls`` calls, one
 ``torch.cuda.synchronize()`` before and after it.  The first package is the yardstick: the report gives both medians per loop and the
 first package's own min-to-max spread over its rounds, and says whether the second median exceeds the first by more than that spread.
+``--lib-dir`` may repeat, paired with ``--package`` in order, to time two builds of the shared objects under the same Python files.
 """
 import argparse
 import json
@@ -18,7 +20,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from layer_digests import B, DEFAULT_PKG, HOP, M, N, SR, import_package  # noqa: E402
+from layer_digests import B, DEFAULT_PKG, HOP, M, N, SR, import_package, pair_lib_dirs  # noqa: E402
 
 LOOPS = ("no_grad", "train_step", "train_step_xgrad")
 
@@ -57,7 +59,7 @@ def child(pkg_dir, lib_dir, calls):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--package", action="append", help="package directory to import as dmel_amd (give two: yardstick, candidate)")
-    ap.add_argument("--lib-dir", default=DEFAULT_PKG)
+    ap.add_argument("--lib-dir", action="append", help="one for all packages, or one per package")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--calls", type=int, default=2000)
     ap.add_argument("--timeout", type=float, default=120.0, help="time limit of one child, seconds")
@@ -65,13 +67,14 @@ def main():
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     packages = args.package or [DEFAULT_PKG]
+    lib_dirs = pair_lib_dirs(ap, packages, args.lib_dir)
     if args.child:
-        child(packages[0], args.lib_dir, args.calls)
+        child(packages[0], lib_dirs[0], args.calls)
         return 0
-    times = {pkg: {k: [] for k in LOOPS} for pkg in packages}
+    times = [{k: [] for k in LOOPS} for _ in packages]           # (by position: the same package may be given twice)
     for _ in range(args.rounds):
-        for pkg in packages:
-            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--package", pkg, "--lib-dir", args.lib_dir, "--calls", str(args.calls)]
+        for i, (pkg, lib_dir) in enumerate(zip(packages, lib_dirs)):
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--package", pkg, "--lib-dir", lib_dir, "--calls", str(args.calls)]
             try:
                 res = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=args.timeout)
             except subprocess.TimeoutExpired:
@@ -83,16 +86,15 @@ def main():
                 print(f"{pkg}: the child ended with status {res.returncode}, stopping", flush=True)
                 return 2
             for k, v in json.loads(line[0][6:]).items():
-                times[pkg][k].append(v)
-            print(pkg, line[0], flush=True)
+                times[i][k].append(v)
+            print(pkg, lib_dir, line[0], flush=True)
     report = {"unit": "us per call", "calls": args.calls, "rounds": args.rounds, "loops": {}}
-    base = packages[0]
     for k in LOOPS:
-        entry = {"yardstick_median": statistics.median(times[base][k]), "yardstick_spread": max(times[base][k]) - min(times[base][k]),
-                 "yardstick_runs": times[base][k]}
-        for pkg in packages[1:]:
-            entry["candidate_median"] = statistics.median(times[pkg][k])
-            entry["candidate_runs"] = times[pkg][k]
+        entry = {"yardstick_median": statistics.median(times[0][k]), "yardstick_spread": max(times[0][k]) - min(times[0][k]),
+                 "yardstick_runs": times[0][k]}
+        for cand in times[1:]:
+            entry["candidate_median"] = statistics.median(cand[k])
+            entry["candidate_runs"] = cand[k]
             entry["within_spread"] = entry["candidate_median"] <= entry["yardstick_median"] + entry["yardstick_spread"]
         report["loops"][k] = entry
     text = json.dumps(report, indent=1)
