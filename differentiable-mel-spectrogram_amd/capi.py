@@ -146,6 +146,8 @@ _SIGNATURES = {
     "dmel_decide_launch_multi": (status, [fp, fp, i32, f32, i32p, u32p, i32p]),
     "dmel_backward_x_multi": (status, [vp, vp, i32, fp, i32, u32, vp, vp, vp, vp]),
     "dmel_backward_x_multi_dev": (status, [vp, vp, i32, vp, i32, i32p, u32p, i32, u32, vp, vp, vp, vp]),
+    "dmel_backward_x_multi_lengths": (status, [vp, vp, vp, i32, fp, i32, u32, vp, vp, vp, vp]),
+    "dmel_backward_x_multi_dev_lengths": (status, [vp, vp, vp, i32, vp, i32, i32p, u32p, i32, u32, vp, vp, vp, vp]),
     "dmel_plan_last_multi_launch": (status, [vp, i32p, u32p, i32p]),
     "dmel_forward_band": (status, [vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_band_dev": (status, [vp, vp, i32, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
@@ -154,6 +156,8 @@ _SIGNATURES = {
     "dmel_backward_band": (status, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp]),
     "dmel_backward_x_band": (status, [vp, vp, i32, fp, i32, vp, u32, vp, vp, vp, vp]),
     "dmel_backward_x_band_dev": (status, [vp, vp, i32, vp, i32, vp, i32p, u32p, i32, u32, vp, vp, vp, vp]),
+    "dmel_backward_x_band_lengths": (status, [vp, vp, vp, i32, fp, i32, vp, u32, vp, vp, vp, vp]),
+    "dmel_backward_x_band_dev_lengths": (status, [vp, vp, vp, i32, vp, i32, vp, i32p, u32p, i32, u32, vp, vp, vp, vp]),
     "dmel_plan_get_info": (status, [vp, P(DmelPlanInfo)]),
     "dmel_plan_set_profiling": (status, [vp, i32]),
     "dmel_plan_get_profile": (status, [vp, P(DmelProfile)]),
@@ -493,41 +497,50 @@ class Plan:
                                          len(edges) - 1, ed, int(accumulate), dlambd_ptr, scratch_ptr, stream))
 
     def backward_x_multi(self, x_ptr: int, batch: int, lambd, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int, log: bool, stream: int,
-                         edges=None):
+                         edges=None, lengths_ptr: int | None = None):
         """dmel_backward_x_multi: grad_x = sum over channels (ascending) of the scalar layer's waveform gradient; lambd: the K host values;
         grad_ptr / out_ptr: (B, K, M, T) fp32.  With ``edges`` (K + 1 host integers) dmel_backward_x_band: grad_ptr / out_ptr are ONE
-        (B, 1, M, T) image and channel k's cotangent is its rows edges[k] ... edges[k + 1] - 1, +0.0 elsewhere."""
+        (B, 1, M, T) image and channel k's cotangent is its rows edges[k] ... edges[k + 1] - 1, +0.0 elsewhere.  With ``lengths_ptr`` the
+        *_lengths entry points (see forward_multi)."""
         lam = _floats(lambd)
         flags = DMEL_FLAG_LOG if log else 0
+        head = (self._h, x_ptr) if lengths_ptr is None else (self._h, x_ptr, lengths_ptr)
+        tail = (flags, grad_ptr, out_ptr, grad_x_ptr, stream)
         if edges is None:
-            _check(load().dmel_backward_x_multi(self._h, x_ptr, batch, lam, len(lambd), flags, grad_ptr, out_ptr, grad_x_ptr, stream))
+            fn = load().dmel_backward_x_multi if lengths_ptr is None else load().dmel_backward_x_multi_lengths
+            _check(fn(*head, batch, lam, len(lambd), *tail))
         else:
-            _check(load().dmel_backward_x_band(self._h, x_ptr, batch, lam, len(lambd), _ints(edges), flags, grad_ptr, out_ptr, grad_x_ptr, stream))
+            fn = load().dmel_backward_x_band if lengths_ptr is None else load().dmel_backward_x_band_lengths
+            _check(fn(*head, batch, lam, len(lambd), _ints(edges), *tail))
 
     def backward_x_multi_dev(self, x_ptr: int, batch: int, lambd_ptr: int, channels: int, launches, grad_ptr: int, out_ptr: int | None,
-                             grad_x_ptr: int, log: bool, stream: int, edges=None):
+                             grad_x_ptr: int, log: bool, stream: int, edges=None, lengths_ptr: int | None = None):
         """dmel_backward_x_multi_dev: lambd read on the device; launches: [(n_fft, channel mask), ...] of the forward whose gradient
         this is (last_multi_launch() right after it).  With ``edges``: dmel_backward_x_band_dev (see backward_x_multi)."""
         k = max(len(launches), 1)
         ns = (C.c_int32 * k)(*[int(n) for n, _ in launches])
         masks = (C.c_uint32 * k)(*[int(m) for _, m in launches])
         flags = DMEL_FLAG_LOG if log else 0
+        head = (self._h, x_ptr) if lengths_ptr is None else (self._h, x_ptr, lengths_ptr)
+        tail = (ns, masks, len(launches), flags, grad_ptr, out_ptr, grad_x_ptr, stream)
         if edges is None:
-            _check(load().dmel_backward_x_multi_dev(self._h, x_ptr, batch, lambd_ptr, int(channels), ns, masks, len(launches), flags,
-                                                    grad_ptr, out_ptr, grad_x_ptr, stream))
+            fn = load().dmel_backward_x_multi_dev if lengths_ptr is None else load().dmel_backward_x_multi_dev_lengths
+            _check(fn(*head, batch, lambd_ptr, int(channels), *tail))
         else:
-            _check(load().dmel_backward_x_band_dev(self._h, x_ptr, batch, lambd_ptr, int(channels), _ints(edges), ns, masks, len(launches),
-                                                   flags, grad_ptr, out_ptr, grad_x_ptr, stream))
+            fn = load().dmel_backward_x_band_dev if lengths_ptr is None else load().dmel_backward_x_band_dev_lengths
+            _check(fn(*head, batch, lambd_ptr, int(channels), _ints(edges), *tail))
 
-    def backward_x_band(self, x_ptr: int, batch: int, lambd, edges, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int, log: bool, stream: int):
-        """dmel_backward_x_band: the band-split layer's waveform gradient, lambd as K host values"""
-        self.backward_x_multi(x_ptr, batch, lambd, grad_ptr, out_ptr, grad_x_ptr, log, stream, edges=edges)
+    def backward_x_band(self, x_ptr: int, batch: int, lambd, edges, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int, log: bool, stream: int,
+                        lengths_ptr: int | None = None):
+        """dmel_backward_x_band(_lengths): the band-split layer's waveform gradient, lambd as K host values"""
+        self.backward_x_multi(x_ptr, batch, lambd, grad_ptr, out_ptr, grad_x_ptr, log, stream, edges=edges, lengths_ptr=lengths_ptr)
 
     def backward_x_band_dev(self, x_ptr: int, batch: int, lambd_ptr: int, edges, launches, grad_ptr: int, out_ptr: int | None,
-                            grad_x_ptr: int, log: bool, stream: int):
-        """dmel_backward_x_band_dev: lambd read on the device; launches: last_multi_launch() right after the forward_band_dev whose
-        gradient this is"""
-        self.backward_x_multi_dev(x_ptr, batch, lambd_ptr, len(edges) - 1, launches, grad_ptr, out_ptr, grad_x_ptr, log, stream, edges=edges)
+                            grad_x_ptr: int, log: bool, stream: int, lengths_ptr: int | None = None):
+        """dmel_backward_x_band_dev(_lengths): lambd read on the device; launches: last_multi_launch() right after the forward_band_dev
+        whose gradient this is"""
+        self.backward_x_multi_dev(x_ptr, batch, lambd_ptr, len(edges) - 1, launches, grad_ptr, out_ptr, grad_x_ptr, log, stream, edges=edges,
+                                  lengths_ptr=lengths_ptr)
 
     def last_multi_launch(self) -> list[tuple[int, int]]:
         """[(n_fft, channel mask), ...] in ascending n_fft: what the most recent forward_multi(_dev) / forward_band(_dev) on this plan issued

@@ -1842,7 +1842,8 @@ dmel_status issue_multi(dmel_plan* pl, const LaunchList& ll, const dmel::LamArgs
 struct BandEdges { int32_t e[dmel::kMaxChannels + 1] = {}; };
 
 // 0 = e_0 < e_1 < ... < e_K = n_mels (every group non-empty)
-dmel_status take_band_edges(const dmel_plan* pl, const int32_t* edges, int channels, const char* who, BandEdges* out)
+// (the part of take_band_edges that needs no plan)
+dmel_status band_edges_shape(const int32_t* edges, int channels, const char* who)
 {
     if (channels < 1 || channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": channels must be 1 ... 8");
     if (!edges) return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges is NULL");
@@ -1850,6 +1851,12 @@ dmel_status take_band_edges(const dmel_plan* pl, const int32_t* edges, int chann
     for (int c = 0; c < channels; ++c)
         if (edges[c + 1] <= edges[c])
             return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges must be strictly ascending (group " + std::to_string(c) + " is empty)");
+    return DMEL_OK;
+}
+
+dmel_status take_band_edges(const dmel_plan* pl, const int32_t* edges, int channels, const char* who, BandEdges* out)
+{
+    if (const dmel_status st = band_edges_shape(edges, channels, who); st != DMEL_OK) return st;
     if (!pl) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");
     if (edges[channels] != pl->cfg.n_mels)
         return fail(DMEL_ERR_INVALID_ARGUMENT, std::string(who) + ": band_edges must end at n_mels = " + std::to_string(pl->cfg.n_mels) + " (got " +
@@ -2340,6 +2347,7 @@ struct XgradCall {
     const float* x = nullptr; int batch = 0; uint32_t flags = 0; const float* grad_out = nullptr; const float* out = nullptr; float* grad_x = nullptr;
     float lambd = 0.f; const float* lambd_dev = nullptr; int n_over = 0, win_half = 0, spec_mode = 0; const int32_t* lengths = nullptr;   // the scalar layers
     int channels = 0; const int32_t* edges = nullptr; const char* who = "";          // the K-window layers: validated band edges or nullptr, the entry point's name
+    bool lens = false;                                                               // ... and whether it is a *_lengths form (then lengths must not be NULL)
     XgradCall(const float* x_, int batch_, uint32_t flags_, const float* grad_out_, const float* out_, float* grad_x_)      // what every entry point fills alike
         : x(x_), batch(batch_), flags(flags_), grad_out(grad_out_), out(out_), grad_x(grad_x_) {}
     bool log() const { return (flags & DMEL_FLAG_LOG) != 0; }
@@ -2531,6 +2539,7 @@ dmel_status check_x_multi_args(dmel_plan* pl, const XgradCall& c)
     if (c.channels < 1 || c.channels > dmel::kMaxChannels) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": channels must be 1 ... 8");
     if (c.flags & ~(uint32_t)DMEL_FLAG_LOG) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": only DMEL_FLAG_LOG is accepted");
     if (c.batch > 0 && (!c.x || !c.grad_out || !c.grad_x)) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": x / grad_out / grad_x is NULL");
+    if (c.batch > 0 && c.lens && !c.lengths) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": lengths is NULL");
     if (c.batch > 0 && (c.flags & DMEL_FLAG_LOG) && !c.out) return fail(DMEL_ERR_INVALID_ARGUMENT, who + ": DMEL_FLAG_LOG needs the saved log output");
     if ((long long)c.batch * c.channels > 65534) return fail(DMEL_ERR_INVALID_ARGUMENT, "batch x channels > 65534 (split the call)");
     return DMEL_OK;
@@ -2542,7 +2551,8 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const XgradCall& xc, const fl
     const int batch = xc.batch, channels = xc.channels, nl = ll.nl;
     const int* ns = ll.ns; const uint32_t* mask = ll.mask;
     const int32_t* edges = xc.edges;
-    const std::string who = edges ? "dmel_backward_x_band" : "dmel_backward_x_multi";
+    const int32_t* lengths = xc.lengths;                          // per-clip lengths (dmel_xgrad_klen.hip) or nullptr
+    const std::string who = lengths ? xc.who : edges ? "dmel_backward_x_band" : "dmel_backward_x_multi";
     { dmel_status sa = check_store_aligned(who.c_str(), {{"grad_x", xc.grad_x}}); if (sa != DMEL_OK) return sa; }
     { dmel_status sd = check_device(plan); if (sd != DMEL_OK) return sd; }
     std::lock_guard<std::mutex> lock(plan->mu);
@@ -2610,6 +2620,7 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const XgradCall& xc, const fl
                 pp.B = batch; pp.L = L; pp.nchunks = plan->nchunks; pp.chunk = plan->chunk;
                 pp.N = N; pp.normalize = plan->cfg.normalize_window; pp.win_half = 0; pp.center = (float)N / 2.0f;
                 pp.lam.dev = lam_dev ? lam_dev + c : nullptr; pp.lam.val = lam_dev ? 0.f : lam_host[c]; pp.lam.role = dmel::kLamQuiet;
+                pp.lengths = lengths;                               // the partial sums then stop at the clip's end, as backward_x_impl
                 DMEL_HIP(dmel::launch_prep(pp, s));
             }
         dmel::XgradParams xp{};
@@ -2625,8 +2636,8 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const XgradCall& xc, const fl
         xp.win_n = N / 2 + 1; xp.tiles = sh.tiles; xp.span = sh.span; xp.tile_step = sh.ts;
         if (sh.wave) {
             // one launch for every channel of this n_fft
-            dmel::XgradBandParams mp{};                                       // (the multi-window layer launches its XgradMultiParams part)
-            mp.p = xp;
+            dmel::XgradBandLenParams mp{};                                    // (every launcher takes the part of it that is its own)
+            mp.p = xp; mp.lengths = lengths; mp.fpt = sh.fpt;
             for (int c = 0; c < channels; ++c) {
                 mp.win2[c] = table(c, N); mp.frames[c] = frames[c]; mp.csum[c] = csum[c];
                 mp.win_denom[c] = lam_host ? std::fabs(lam_host[c]) + 1e-15f : 0.f;
@@ -2635,7 +2646,13 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const XgradCall& xc, const fl
             mp.ch_grid = batch * sh.tiles; mp.ch_out = edges ? 1 : channels;
             for (int c = 0; edges && c <= dmel::kMaxChannels; ++c) mp.band_edges[c] = edges[std::min(c, channels)];
             if ((long long)batch * sh.tiles * mp.count > 0x7fffffffLL) return fail(DMEL_ERR_UNSUPPORTED, "gradient w.r.t. the waveform: grid too large");
-            DMEL_HIP(edges ? dmel::launch_xgrad_wave_band(mp, s) : dmel::launch_xgrad_wave_multi(mp, s));
+            if (lengths) {
+                dmel::XgradMultiLenParams ml{};                               // (no base of mp: there the lengths lie behind the edges)
+                static_cast<dmel::XgradMultiParams&>(ml) = mp; ml.lengths = lengths; ml.fpt = sh.fpt;
+                DMEL_HIP(edges ? dmel::launch_xgrad_wave_band_len(mp, s) : dmel::launch_xgrad_wave_multi_len(ml, s));
+            } else {
+                DMEL_HIP(edges ? dmel::launch_xgrad_wave_band(mp, s) : dmel::launch_xgrad_wave_multi(mp, s));
+            }
         } else {
             // the LDS path (cold): per channel, its rows of grad_out / out staged as (B, M, T) -- strided copy or the band layer's masking kernel -- then the frames kernel
             for (int c = 0; c < channels; ++c) {
@@ -2654,21 +2671,29 @@ dmel_status backward_x_multi_impl(dmel_plan* plan, const XgradCall& xc, const fl
                 q.grad_out = stage; q.out = xc.log() ? stage + bmt : nullptr;
                 q.win2 = table(c, N); q.frames = frames[c]; q.csum = csum[c];
                 q.lam_dev = lam_dev ? lam_dev + c : nullptr;
-                DMEL_HIP(dmel::launch_xgrad_frames(q, s));
+                if (lengths) {
+                    dmel::XgradLenParams lq{};
+                    static_cast<dmel::XgradParams&>(lq) = q; lq.lengths = lengths; lq.fpt = 0;
+                    DMEL_HIP(dmel::launch_xgrad_frames_len(lq, s));
+                } else {
+                    DMEL_HIP(dmel::launch_xgrad_frames(q, s));
+                }
             }
         }
     }
     // one combine: the channels' terms in ascending channel order
-    dmel::XgradCombineMultiParams cp{};
+    dmel::XgradCombineMultiLenParams cp{};                        // (without lengths: its XgradCombineMultiParams part)
+    cp.lengths = lengths;
     cp.grad_x = xc.grad_x; cp.lam_dev = lam_dev; cp.L = L; cp.T = T; cp.hop = plan->cfg.hop_length; cp.channels = channels;
     for (int c = 0; c < channels; ++c) {
         cp.ncand[c] = ncand[c]; cp.frames[c] = frames[c]; cp.csum[c] = csum[c];
         for (int j = 0; j < ncand[c]; ++j) {
             const XgShape& sh = shape[cand[c][j]];
             cp.n[c][j] = cand[c][j]; cp.tiles[c][j] = sh.tiles; cp.span[c][j] = sh.span; cp.tile_step[c][j] = sh.ts;
+            cp.fpt[c][j] = sh.wave ? sh.fpt : 0;
         }
     }
-    DMEL_HIP(dmel::launch_xgrad_combine_multi(cp, batch, s));
+    DMEL_HIP(lengths ? dmel::launch_xgrad_combine_multi_len(cp, batch, s) : dmel::launch_xgrad_combine_multi(cp, batch, s));
     prof_span(plan, m0, prof_mark(plan, s), 2);
     return DMEL_OK;
 }
@@ -2759,6 +2784,60 @@ dmel_status dmel_backward_x_band_dev(dmel_plan* plan, const float* x, int32_t ba
     if (st != DMEL_OK) return st;
     XgradCall c(x, batch, flags, grad_out, out, grad_x);
     c.channels = channels; c.who = "dmel_backward_x_band_dev";
+    c.edges = be.e;
+    return backward_x_multi_devlist(plan, c, lambd_dev, n_ffts, channel_masks, count, stream);
+}
+
+namespace {
+// the *_lengths band forms: the edges' own shape, then every argument check that needs no plan's contents, then the edges against the plan's n_mels
+dmel_status take_band_edges_x(dmel_plan* plan, const XgradCall& c, const int32_t* band_edges, BandEdges* be)
+{
+    dmel_status st = band_edges_shape(band_edges, c.channels, c.who);
+    if (st == DMEL_OK) st = check_x_multi_args(plan, c);
+    return st != DMEL_OK ? st : take_band_edges(plan, band_edges, c.channels, c.who, be);
+}
+}  // namespace
+
+// the four forms above over clips of per-clip lengths (dmel_xgrad_klen.hip): clip b is x[b, :lengths[b]], read by the kernels when they run
+dmel_status dmel_backward_x_multi_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
+                                          int32_t channels, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.channels = channels; c.who = "dmel_backward_x_multi_lengths"; c.lengths = lengths; c.lens = true;
+    return backward_x_multi_host(plan, c, lambd_host, stream);
+}
+
+dmel_status dmel_backward_x_multi_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                              int32_t channels, const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count,
+                                              uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.channels = channels; c.who = "dmel_backward_x_multi_dev_lengths"; c.lengths = lengths; c.lens = true;
+    return backward_x_multi_devlist(plan, c, lambd_dev, n_ffts, channel_masks, count, stream);
+}
+
+dmel_status dmel_backward_x_band_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
+                                         int32_t channels, const int32_t* band_edges, uint32_t flags, const float* grad_out, const float* out,
+                                         float* grad_x, void* stream)
+{
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.channels = channels; c.who = "dmel_backward_x_band_lengths"; c.lengths = lengths; c.lens = true;
+    BandEdges be;
+    const dmel_status st = take_band_edges_x(plan, c, band_edges, &be);
+    if (st != DMEL_OK) return st;
+    c.edges = be.e;
+    return backward_x_multi_host(plan, c, lambd_host, stream);
+}
+
+dmel_status dmel_backward_x_band_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                             int32_t channels, const int32_t* band_edges, const int32_t* n_ffts, const uint32_t* channel_masks,
+                                             int32_t count, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream)
+{
+    XgradCall c(x, batch, flags, grad_out, out, grad_x);
+    c.channels = channels; c.who = "dmel_backward_x_band_dev_lengths"; c.lengths = lengths; c.lens = true;
+    BandEdges be;
+    const dmel_status st = take_band_edges_x(plan, c, band_edges, &be);
+    if (st != DMEL_OK) return st;
     c.edges = be.e;
     return backward_x_multi_devlist(plan, c, lambd_dev, n_ffts, channel_masks, count, stream);
 }

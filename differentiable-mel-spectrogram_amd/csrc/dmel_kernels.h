@@ -620,6 +620,29 @@ struct XgradBandStageParams {
 };
 hipError_t launch_xgrad_band_stage(const XgradBandStageParams& p, hipStream_t s);
 
+// dmel_xgrad_klen.hip: the K-window layers' gradient w.r.t. the waveform over clips of per-clip lengths (dmel_backward_x_multi_lengths,
+// dmel_backward_x_band_lengths and their _dev forms): the launches above with the clip bounds of XgradLenParams.  fpt: frames per tile of
+// p.N (checked by the launcher); clip b's tiles are q < ceil(Tc / fpt), the others are neither written nor read.
+struct XgradMultiLenParams : XgradMultiParams {
+    const int* lengths;         // (B) device, read by the kernels when they run
+    int fpt;
+};
+struct XgradBandLenParams : XgradBandParams {
+    const int* lengths;
+    int fpt;
+};
+// dmel_xgrad_combine_multi_len_kernel: dmel_xgrad_combine_multi_kernel with the per-clip rules of dmel_xgrad_combine_len_kernel (tiles > 0)
+// and dmel_xgrad_gather_len_kernel (tiles == 0) per channel and candidate; grad_x[b, lengths[b]:] = +0.0, an invalid length: the row is NaN
+struct XgradCombineMultiLenParams : XgradCombineMultiParams {
+    const int* lengths;
+    int fpt[kMaxChannels][kXgMaxCand];
+};
+hipError_t launch_xgrad_wave_multi_len(const XgradMultiLenParams& p, hipStream_t s);
+hipError_t launch_xgrad_wave_band_len(const XgradBandLenParams& p, hipStream_t s);
+hipError_t launch_xgrad_combine_multi_len(const XgradCombineMultiLenParams& p, int batch, hipStream_t s);
+// dmel_xgrad_len.hip's LDS radix-2 frames kernel alone (no gather): the K-window layers' LDS path runs it per channel on the staged rows
+hipError_t launch_xgrad_frames_len(const XgradLenParams& p, hipStream_t s);
+
 // gradient w.r.t. the filterbank matrix of models.py:53 (adjoint of  mel = spec^T @ fb):
 //   grad_fb[f][m] = sum_{b,t} spec[b][f][t] * gm[b][m][t],   gm = grad_out            (linear output)
 //                                                            gm = grad_out * exp(-out) (log output: d log(s+eps) = ds / (s+eps))
@@ -727,12 +750,13 @@ hipError_t forward_band_len_prepare_attributes();
 hipError_t xgrad_prepare_attributes();
 hipError_t xgrad_len_prepare_attributes();
 hipError_t xgrad_band_prepare_attributes();
+hipError_t xgrad_klen_prepare_attributes();
 hipError_t big_prepare_attributes();
 inline hipError_t prepare_attributes()
 {
     for (auto unit : {forward_prepare_attributes, forward_len_prepare_attributes, forward_band_prepare_attributes, forward_multi_len_prepare_attributes,
                       forward_band_len_prepare_attributes, xgrad_prepare_attributes,
-                      xgrad_len_prepare_attributes, xgrad_band_prepare_attributes, big_prepare_attributes})
+                      xgrad_len_prepare_attributes, xgrad_band_prepare_attributes, xgrad_klen_prepare_attributes, big_prepare_attributes})
         if (const hipError_t e = unit(); e != hipSuccess) return e;
     return hipSuccess;
 }

@@ -38,4 +38,11 @@ hipError_t launch_xgrad_len(const XgradLenParams& p, hipStream_t s)
     return xgrad_launch(p, s);
 }
 
+// the frames kernel alone (no gather): the K-window layers run it per channel and gather in dmel_xgrad_combine_multi_len_kernel
+hipError_t launch_xgrad_frames_len(const XgradLenParams& p, hipStream_t s)
+{
+    if (!p.lengths || p.spec_mode) return hipErrorInvalidValue;
+    return xgrad_launch_frames(p, s);
+}
+
 }  // namespace dmel

@@ -5,10 +5,20 @@
 // kernels of dmel_xgrad.hip, to exactly the tokens they were written with, so that their code does not change.
 // dmel_xgrad_band.hip includes it a fourth time with DMEL_XG_MULTI = 1 and DMEL_XG_BAND = 1: dmel_xgrad_wave_band_kernel, the multi kernel's
 // channel slot with ONE image behind grad_out / out (XgradBandParams): a channel stages only its own rows of it, every other row of gm is +0.0.
-#if DMEL_XG_BAND
+// dmel_xgrad_klen.hip includes it twice more with DMEL_XG_MULTI = 1 and DMEL_XG_LEN = 1, without and with DMEL_XG_BAND:
+// dmel_xgrad_wave_multi_len_kernel and dmel_xgrad_wave_band_len_kernel, the K-window layers over clips of per-clip lengths.
+#if DMEL_XG_BAND && DMEL_XG_LEN
+#define XG_KERNEL dmel_xgrad_wave_band_len_kernel
+#define XG_PARAMS XgradBandLenParams mp
+#define XG_BO b
+#elif DMEL_XG_BAND
 #define XG_KERNEL dmel_xgrad_wave_band_kernel
 #define XG_PARAMS XgradBandParams mp
 #define XG_BO b
+#elif DMEL_XG_MULTI && DMEL_XG_LEN
+#define XG_KERNEL dmel_xgrad_wave_multi_len_kernel
+#define XG_PARAMS XgradMultiLenParams mp
+#define XG_BO bo
 #elif DMEL_XG_MULTI
 #define XG_KERNEL dmel_xgrad_wave_multi_kernel
 #define XG_PARAMS XgradMultiParams mp
@@ -25,6 +35,11 @@
 // sample-space bounds of a clip: L (also the row stride of x) and fl32(1 / L), or the clip's own length Lc (dmel_xgrad_wave_len_kernel); its
 // frames: T (also the row stride of grad_out / out), or Tc
 #if DMEL_XG_LEN
+#if DMEL_XG_MULTI
+#define XG_LENGTHS mp.lengths
+#else
+#define XG_LENGTHS p.lengths
+#endif
 #define XG_LC Lc
 #define XG_PSUM_L Lc
 #define XG_INV_L inv_Lc
@@ -96,8 +111,8 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
 #if DMEL_XG_LEN
     // the clip is x[b, :Lc] (one scalar load: uniform over the workgroup) with Tc = Lc / hop + 1 frames; the frames past them are pad frames
     // (zero mel gradient).  A tile whose first frame is a pad frame, and every tile of a clip whose length is outside 1 ... L, does nothing:
-    // dmel_xgrad_combine_len_kernel reads neither its segment nor its sum.
-    const ClipLen cl = clip_len(p.lengths, b, L, hop);
+    // dmel_xgrad_combine_len_kernel (dmel_xgrad_combine_multi_len_kernel) reads neither its segment nor its sum.
+    const ClipLen cl = clip_len(XG_LENGTHS, b, L, hop);
     const int Lc = cl.Lc, Tc = cl.Tc;
     const float inv_Lc = 1.0f / (float)Lc;
     if (!cl.ok || tile * FPT >= Tc) return;
@@ -444,6 +459,7 @@ __global__ void __launch_bounds__((XgPlan<N>::THREADS), (XgPlan<N>::MINW)) XG_KE
 #undef XG_PARAMS
 #undef XG_BO
 #undef XG_LC
+#undef XG_LENGTHS
 #undef XG_PSUM_L
 #undef XG_INV_L
 #undef XG_TC

@@ -742,7 +742,8 @@ class _MultiFunction(torch.autograd.Function):
     backward: dmel_backward_multi (K dot products in one launch) and, for a waveform that requires grad (waveform_grad=True),
     dmel_backward_x_multi(_dev): one x-gradient for all K channels, the sum of the K scalar layers' in ascending channel order.
     With ``lengths`` (per_clip_lengths=True; int32 on x's device) the forward is dmel_forward_multi(_dev)_lengths; the backward is the same
-    dot over its tangent, whose pad frames are zero.  (No waveform gradient with lengths: the layer refuses it.)"""
+    dot over its tangent, whose pad frames are zero, and for a waveform that requires grad (lengths_waveform_grad=True)
+    dmel_backward_x_multi(_dev)_lengths: ``lengths`` is then saved too."""
 
     @staticmethod
     def forward(ctx, x, lambd, plan, lam_host, log, eps, out_dtype, want_tangent, lengths=None):
@@ -766,7 +767,8 @@ class _MultiFunction(torch.autograd.Function):
         ctx.launches = plan.last_multi_launch() if (want_x and lam_host is None) else None
         saved = [tangent, scratch] if want_tangent else []
         if want_x:
-            saved += [x] + ([lam] if lam is not None else []) + ([out] if log else [])
+            saved += [x] + ([lengths] if lengths is not None else []) + ([lam] if lam is not None else []) + ([out] if log else [])
+        ctx.has_lengths = lengths is not None
         ctx.save_for_backward(*saved)
         return out.to(torch.bfloat16) if round_later else out
 
@@ -784,16 +786,17 @@ class _MultiFunction(torch.autograd.Function):
                 dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
             if ctx.want_x:
                 x = saved.pop(0)
+                lengths = saved.pop(0) if ctx.has_lengths else None
                 lam = saved.pop(0) if ctx.lam_host is None else None
                 out = saved.pop(0) if ctx.log else None
                 g32 = g.to(torch.float32)
                 gx = torch.empty_like(x)
                 if lam is None:
                     ctx.plan.backward_x_multi(x.data_ptr(), x.shape[0], ctx.lam_host, g32.data_ptr(), _ptr(out), gx.data_ptr(), ctx.log,
-                                              _stream_ptr(g.device))
+                                              _stream_ptr(g.device), lengths_ptr=_ptr(lengths))
                 else:
                     ctx.plan.backward_x_multi_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.K, ctx.launches, g32.data_ptr(), _ptr(out),
-                                                  gx.data_ptr(), ctx.log, _stream_ptr(g.device))
+                                                  gx.data_ptr(), ctx.log, _stream_ptr(g.device), lengths_ptr=_ptr(lengths))
         return gx, dl, None, None, None, None, None, None, None
 
 
@@ -802,7 +805,7 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
 
         MultiWindowMelSpectrogram(init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1,
                                   normalize_window=False, *, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False,
-                                  waveform_grad=False, per_clip_lengths=False)
+                                  waveform_grad=False, per_clip_lengths=False, lengths_waveform_grad=False)
         forward(x: (B, n_points)) -> (B, K, n_mels, n_points // hop_length + 1)
 
     ``y[:, k:k+1]`` is what ``MelSpectrogramLayer(lambd[k], ..., optimized=True)`` returns for the same ``x``, bit for bit (each
@@ -818,15 +821,25 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
     the kernels only, so the sync-free step stays capturable), and ``y[:, k:k+1]`` is what that scalar forward returns at ``lambd[k]``, bit for
     bit -- each clip's own mean, pad frames (``0`` or ``log(0 + eps)``, no gradient) from ``frame_lengths(lengths)[b]`` on, tiles of pad
     frames not transformed, ``x[b, lengths[b]:]`` never read, a length outside ``1 ... n_points`` NaN in every channel of that clip.
-    ``lambd.grad`` comes through the same backward.  ``forward(x)`` is unchanged.  Per-clip lengths have no waveform gradient on this
-    layer yet: ``x.requires_grad`` together with ``lengths`` raises, with or without ``waveform_grad``.
+    ``lambd.grad`` comes through the same backward.  ``forward(x)`` is unchanged.
+    ``lengths_waveform_grad=True`` (keyword-only, off by default, needs ``per_clip_lengths=True``; the name and meaning are
+    ``MelSpectrogramLayer``'s) lets ``forward(x, lengths)`` take an ``x`` that requires grad; ``waveform_grad`` keeps governing ``forward(x)``
+    only.  The output and ``lambd.grad`` keep their bits and ``x.grad`` is ``0 + gx_0 + ... + gx_{K-1}`` in ascending channel order, ``gx_k``
+    the ``x.grad`` of ``MelSpectrogramLayer(lambd[k], ..., optimized=True, lengths_waveform_grad=True)(x, lengths)`` for ``g[:, k:k+1]``, bit
+    for bit: ``x.grad[b, lengths[b]:]`` is ``+0.0``, the gradient's own mean is taken over the clip's samples, the cotangent of pad frames is
+    never read, and a length outside ``1 ... n_points`` makes the row ``x.grad[b]`` NaN.  With ``lambd_sync=False`` the step has no host read
+    and can be captured; a channel no launch covered makes all of ``x.grad`` NaN.  Without the flag ``x.requires_grad`` together with
+    ``lengths`` raises, with or without ``waveform_grad``.
     Not supported: ``SlotInput``, ``GraphedStep`` and ``LambdAdam(fused_into_backward=...)``."""
 
     MAX_CHANNELS = 8
 
     def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
-                 log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False, per_clip_lengths=False):
+                 log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False, per_clip_lengths=False,
+                 lengths_waveform_grad=False):
         super().__init__()
+        if lengths_waveform_grad and not per_clip_lengths:
+            raise ValueError("lengths_waveform_grad=True is the waveform gradient of forward(x, lengths): it needs per_clip_lengths=True")
         lam = init_lambd.detach().clone() if torch.is_tensor(init_lambd) else torch.tensor([float(v) for v in init_lambd])
         if lam.dim() != 1:
             raise ValueError(f"init_lambd must be 1-D (K values), got shape {tuple(lam.shape)}")
@@ -850,6 +863,8 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
         self.log, self.eps, self.out_dtype, self.lambd_sync = bool(log), float(eps), out_dtype, bool(lambd_sync)
         self.waveform_grad = bool(waveform_grad)
         self.per_clip_lengths = bool(per_clip_lengths)                # forward(x, lengths) is taken (opt-in: without it lengths are refused)
+        self.lengths_waveform_grad = bool(lengths_waveform_grad)      # ... and accepts an x that requires grad (opt-in: that forward keeps
+                                                                      # x, lengths and the fp32 output alive until the backward)
 
     @property
     def channels(self) -> int:
@@ -868,9 +883,11 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
         check = None
         if self.per_clip_lengths:
             check = lambda x_, l_: _lengths_for_kernels(x_, l_, self.n_points)      # noqa: E731
-            if lengths is not None:
-                refuse_x_grad = (f"per-clip lengths have no waveform gradient on {name} yet: pass x.detach() "
-                                 "(MelSpectrogramLayer(lengths_waveform_grad=True) has one)")
+            if lengths is not None:                                                # (waveform_grad governs forward(x) only)
+                refuse_x_grad = None
+                if not self.lengths_waveform_grad:
+                    refuse_x_grad = (f"per-clip lengths have no waveform gradient on {name} yet: pass x.detach() "
+                                     "(MelSpectrogramLayer(lengths_waveform_grad=True) has one)")
         lengths = _check_input(name, x, self.lambd, lengths, n_points=self.n_points, check_lengths=check, refuse_slot=refuse_slot,
                                refuse_x_grad=refuse_x_grad)
         xf = _as_f32_contiguous(x, lengths)
@@ -889,7 +906,8 @@ class MultiWindowMelSpectrogram(_PlanCachingModule):
     def extra_repr(self):
         return (f"channels={self.channels}, n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
                 f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}, "
-                f"waveform_grad={self.waveform_grad}, per_clip_lengths={self.per_clip_lengths}")
+                f"waveform_grad={self.waveform_grad}, per_clip_lengths={self.per_clip_lengths}, "
+                f"lengths_waveform_grad={self.lengths_waveform_grad}")
 
 
 class _BandFunction(torch.autograd.Function):
@@ -897,7 +915,7 @@ class _BandFunction(torch.autograd.Function):
     (B, 1, M, T) image and of its tangent; backward: dmel_backward_band (the K row-group dot products in one launch) and, for a waveform
     that requires grad (waveform_grad=True), dmel_backward_x_band(_dev): every channel's x-gradient from its own rows of the ONE cotangent,
     summed in ascending channel order (what _MultiFunction saves for it, this one saves too).  With ``lengths``:
-    dmel_forward_band(_dev)_lengths, as _MultiFunction."""
+    dmel_forward_band(_dev)_lengths and, for the waveform, dmel_backward_x_band(_dev)_lengths, as _MultiFunction."""
 
     @staticmethod
     def forward(ctx, x, lambd, plan, lam_host, edges, log, eps, out_dtype, want_tangent, lengths=None):
@@ -921,7 +939,8 @@ class _BandFunction(torch.autograd.Function):
         ctx.launches = plan.last_multi_launch() if (want_x and lam_host is None) else None
         saved = [tangent, scratch] if want_tangent else []
         if want_x:
-            saved += [x] + ([lam] if lam is not None else []) + ([out] if log else [])
+            saved += [x] + ([lengths] if lengths is not None else []) + ([lam] if lam is not None else []) + ([out] if log else [])
+        ctx.has_lengths = lengths is not None
         ctx.save_for_backward(*saved)
         return out.to(torch.bfloat16) if round_later else out
 
@@ -939,16 +958,17 @@ class _BandFunction(torch.autograd.Function):
                 dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
             if ctx.want_x:
                 x = saved.pop(0)
+                lengths = saved.pop(0) if ctx.has_lengths else None
                 lam = saved.pop(0) if ctx.lam_host is None else None
                 out = saved.pop(0) if ctx.log else None
                 g32 = g.to(torch.float32)
                 gx = torch.empty_like(x)
                 if lam is None:
                     ctx.plan.backward_x_band(x.data_ptr(), x.shape[0], ctx.lam_host, ctx.edges, g32.data_ptr(), _ptr(out), gx.data_ptr(), ctx.log,
-                                             _stream_ptr(g.device))
+                                             _stream_ptr(g.device), lengths_ptr=_ptr(lengths))
                 else:
                     ctx.plan.backward_x_band_dev(x.data_ptr(), x.shape[0], lam.data_ptr(), ctx.edges, ctx.launches, g32.data_ptr(), _ptr(out),
-                                                 gx.data_ptr(), ctx.log, _stream_ptr(g.device))
+                                                 gx.data_ptr(), ctx.log, _stream_ptr(g.device), lengths_ptr=_ptr(lengths))
         return gx, dl, None, None, None, None, None, None, None, None
 
 
@@ -957,7 +977,7 @@ class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
 
         BandSplitMelSpectrogram(init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
                                 band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False,
-                                per_clip_lengths=False)
+                                per_clip_lengths=False, lengths_waveform_grad=False)
         forward(x: (B, n_points)) -> (B, 1, n_mels, n_points // hop_length + 1)
 
     ``band_edges`` are K + 1 integers ``0 = e_0 < e_1 < ... < e_K = n_mels`` (default ``e_k = (k * n_mels) // K``).  Rows
@@ -990,15 +1010,20 @@ class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
     ``0`` / ``log(0 + eps)`` and no gradient from ``frame_lengths(lengths)[b]`` on, pad tiles not transformed, ``x[b, lengths[b]:]`` never
     read, a length outside ``1 ... n_points`` NaN in every group's rows of that clip); a channel writes pad and NaN rows into its own rows
     only.  The values are read by the kernels only: the sync-free step stays capturable.  ``forward(x)`` is unchanged.
-    Out of scope, not forgotten (each raises and says what to use instead): the waveform gradient of per-clip ``lengths``
-    (``x.requires_grad`` together with ``lengths`` raises, with or without ``waveform_grad``), ``SlotInput``, ``GraphedStep`` and
+    ``lengths_waveform_grad=True`` (keyword-only, off by default, needs ``per_clip_lengths=True``) lets ``forward(x, lengths)`` take an ``x``
+    that requires grad, as on ``MultiWindowMelSpectrogram``: ``x.grad`` is the same sum with ``gx_k`` the ``x.grad`` of
+    ``MelSpectrogramLayer(lambd[k], ..., optimized=True, lengths_waveform_grad=True)(x, lengths)`` for ``G_k``, bit for bit; a channel loads
+    only its own rows of the cotangent and of the saved log output, and only the clip's own frames of them.  Without the flag
+    ``x.requires_grad`` together with ``lengths`` raises, with or without ``waveform_grad``.
+    Out of scope, not forgotten (each raises and says what to use instead): ``SlotInput``, ``GraphedStep`` and
     ``LambdAdam(fused_into_backward=...)``; band edges and the filterbank are not trainable."""
 
     def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1, normalize_window=False, *,
                  band_edges=None, log=False, eps=1e-10, out_dtype=torch.float32, lambd_sync=False, waveform_grad=False,
-                 per_clip_lengths=False):
+                 per_clip_lengths=False, lengths_waveform_grad=False):
         super().__init__(init_lambd, n_mels, n_points, sample_rate, f_min, f_max, hop_length, normalize_window, log=log, eps=eps,
-                         out_dtype=out_dtype, lambd_sync=lambd_sync, waveform_grad=waveform_grad, per_clip_lengths=per_clip_lengths)
+                         out_dtype=out_dtype, lambd_sync=lambd_sync, waveform_grad=waveform_grad, per_clip_lengths=per_clip_lengths,
+                         lengths_waveform_grad=lengths_waveform_grad)
         K = self.lambd.shape[0]
         if band_edges is None:
             if K > n_mels:
@@ -1027,7 +1052,8 @@ class BandSplitMelSpectrogram(MultiWindowMelSpectrogram):
     def extra_repr(self):
         return (f"band_edges={list(self.band_edges)}, n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
                 f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, normalize_window={self.normalize_window}, log={self.log}, "
-                f"waveform_grad={self.waveform_grad}, per_clip_lengths={self.per_clip_lengths}")
+                f"waveform_grad={self.waveform_grad}, per_clip_lengths={self.per_clip_lengths}, "
+                f"lengths_waveform_grad={self.lengths_waveform_grad}")
 
 
 class _DspecFunction(torch.autograd.Function):

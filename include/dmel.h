@@ -516,6 +516,17 @@ dmel_status dmel_backward_x_multi(dmel_plan* plan, const float* x, int32_t batch
 dmel_status dmel_backward_x_multi_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
                                       const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count, uint32_t flags,
                                       const float* grad_out, const float* out, float* grad_x, void* stream);
+/* dmel_backward_x_multi(_dev) over clips of per-clip lengths, the backward of dmel_forward_multi(_dev)_lengths: gx_k is what
+ * dmel_backward_x(_dev)_lengths gives for lambd[k], bit for bit.  lengths: `batch` device integers, read when the kernels run (a captured call
+ * takes new values on replay).  grad_x[b, lengths[b]:] = +0.0; a length outside 1 ... n_points makes row b NaN and changes no other row;
+ * samples past a clip, and grad_out / out of its pad frames, are never read; pad tiles and pad pairs are not transformed and the combine
+ * (dmel_xgrad_combine_multi_len_kernel) reads nothing of them from the plan-owned workspace.  lengths == NULL: DMEL_ERR_INVALID_ARGUMENT;
+ * every other rule is dmel_backward_x_multi(_dev)'s. */
+dmel_status dmel_backward_x_multi_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
+                                          int32_t channels, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream);
+dmel_status dmel_backward_x_multi_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                              int32_t channels, const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count,
+                                              uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream);
 /* What the most recent dmel_forward_multi(_dev), dmel_forward_band(_dev) or their _lengths forms on this plan issued (host bookkeeping, captured calls included):
  * count entries in ascending n_fft with their channel masks; arrays of 24 (3 x 8) entries.  count = 0 before the first such call. */
 dmel_status dmel_plan_last_multi_launch(dmel_plan* plan, int32_t* n_ffts, uint32_t* channel_masks, int32_t* count);
@@ -559,6 +570,15 @@ dmel_status dmel_backward_x_band(dmel_plan* plan, const float* x, int32_t batch,
 dmel_status dmel_backward_x_band_dev(dmel_plan* plan, const float* x, int32_t batch, const float* lambd_dev, int32_t channels,
                                      const int32_t* band_edges, const int32_t* n_ffts, const uint32_t* channel_masks, int32_t count,
                                      uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream);
+/* dmel_backward_x_band(_dev) over clips of per-clip lengths, the backward of dmel_forward_band(_dev)_lengths: gx_k is what
+ * dmel_backward_x(_dev)_lengths gives for lambd[k] and G_k, bit for bit (dmel_xgrad_wave_band_len_kernel: a channel's own rows, the clip's own
+ * frames).  lengths and the clip rules as dmel_backward_x_multi(_dev)_lengths; everything else as dmel_backward_x_band(_dev). */
+dmel_status dmel_backward_x_band_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_host,
+                                         int32_t channels, const int32_t* band_edges, uint32_t flags, const float* grad_out, const float* out,
+                                         float* grad_x, void* stream);
+dmel_status dmel_backward_x_band_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                             int32_t channels, const int32_t* band_edges, const int32_t* n_ffts, const uint32_t* channel_masks,
+                                             int32_t count, uint32_t flags, const float* grad_out, const float* out, float* grad_x, void* stream);
 
 /* Introspection for tests / benchmarks */
 typedef struct dmel_plan_info {
