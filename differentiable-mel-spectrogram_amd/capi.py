@@ -98,6 +98,7 @@ _SIGNATURES = {
     "dmel_forward_dev_fixed_spec": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp, vp]),
     "dmel_forward_lengths": (status, [vp, vp, vp, i32, f32, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_dev_lengths": (status, [vp, vp, vp, i32, vp, u32, f64, vp, vp, vp, vp]),
+    "dmel_forward_dev_fixed_lengths": (status, [vp, vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp, vp]),
     "dmel_plan_lambd_status": (status, [vp, P(DmelLambdStatus)]),
     "dmel_plan_lambd_report": (status, [vp, u32, fp, i32p]),
     "dmel_decide_launch": (status, [f32, f32, f32, i32p, i32p]),
@@ -111,6 +112,8 @@ _SIGNATURES = {
     "dmel_backward_fb_dev": (status, [vp, vp, i32, vp, i32, u32, vp, vp, vp, vp]),
     "dmel_backward_fb_saved": (status, [vp, vp, i32, i32, u32, vp, vp, vp, vp]),
     "dmel_backward_fb_saved_dl": (status, [vp, vp, i32, i32, u32, vp, vp, vp, vp, vp, vp, vp]),
+    "dmel_backward_fb_dev_lengths": (status, [vp, vp, vp, i32, vp, i32, u32, vp, vp, vp, vp]),
+    "dmel_backward_fb_saved_lengths": (status, [vp, vp, vp, i32, i32, u32, vp, vp, vp, vp, vp, vp, vp]),
     "dmel_backward_x": (status, [vp, vp, i32, f32, u32, vp, vp, vp, vp]),
     "dmel_backward_x_spec": (status, [vp, vp, i32, f32, i32, u32, vp, vp, vp]),
     "dmel_backward_x_dev": (status, [vp, vp, i32, vp, i32, u32, vp, vp, vp, vp]),
@@ -404,6 +407,29 @@ class Plan:
         """dmel_backward_fb_dev: dmel_backward_fb with lambd read on the device."""
         _check(load().dmel_backward_fb_dev(self._h, x_ptr, batch, lambd_ptr, int(n_fft_), (DMEL_FLAG_LOG if log else 0) | int(extra_flags), grad_ptr,
                                            out_ptr if log else None, grad_fb_ptr, stream))
+
+    def forward_dev_fixed_lengths(self, x_ptr: int, lengths_ptr: int, batch: int, lambd_ptr: int, n_fft_: int, out_ptr: int,
+                                  tangent_ptr: int | None, spec_ptr: int | None, log: bool, eps: float, stream: int,
+                                  scratch_ptr: int | None = None, extra_flags: int = 0):
+        """dmel_forward_dev_fixed_lengths: forward_dev_fixed(_spec) over clips of per-clip lengths (a trained filterbank on a zero-padded batch)."""
+        _check(load().dmel_forward_dev_fixed_lengths(self._h, x_ptr, lengths_ptr, batch, lambd_ptr, int(n_fft_),
+                                                     (DMEL_FLAG_LOG if log else 0) | int(extra_flags), float(eps), out_ptr, tangent_ptr, spec_ptr,
+                                                     scratch_ptr, stream))
+
+    def backward_fb_dev_lengths(self, x_ptr: int, lengths_ptr: int, batch: int, lambd_ptr: int, n_fft_: int, grad_ptr: int, out_ptr: int | None,
+                                grad_fb_ptr: int, log: bool, stream: int, extra_flags: int = 0):
+        """dmel_backward_fb_dev_lengths: the filterbank gradient of clips of per-clip lengths, spectrogram recomputed."""
+        _check(load().dmel_backward_fb_dev_lengths(self._h, x_ptr, lengths_ptr, batch, lambd_ptr, int(n_fft_),
+                                                   (DMEL_FLAG_LOG if log else 0) | int(extra_flags), grad_ptr, out_ptr if log else None, grad_fb_ptr,
+                                                   stream))
+
+    def backward_fb_saved_lengths(self, spec_ptr: int, lengths_ptr: int, batch: int, n_fft_: int, grad_ptr: int, out_ptr: int | None,
+                                  tangent_ptr: int | None, grad_fb_ptr: int, dlambd_ptr: int | None, scratch_ptr: int | None, log: bool,
+                                  stream: int, extra_flags: int = 0):
+        """dmel_backward_fb_saved_lengths: ... on the saved spectrogram; with tangent_ptr and dlambd_ptr, d lambd in the same launch."""
+        _check(load().dmel_backward_fb_saved_lengths(self._h, spec_ptr, lengths_ptr, batch, int(n_fft_),
+                                                     (DMEL_FLAG_LOG if log else 0) | int(extra_flags), grad_ptr, out_ptr if log else None,
+                                                     tangent_ptr, grad_fb_ptr, dlambd_ptr, scratch_ptr, stream))
 
     def backward_x_dev(self, x_ptr: int, batch: int, lambd_ptr: int, n_fft_: int, grad_ptr: int, out_ptr: int | None, grad_x_ptr: int,
                        log: bool, stream: int, extra_flags: int = 0):

@@ -819,6 +819,7 @@ struct FwdCall {
     const float* x = nullptr; int batch = 0; unsigned flags = 0; double eps = 0.0; float* out = nullptr; float* tangent = nullptr;
     int mode = dmel::kInfer, remove_dc = 1, win_half = 0;
     float* spec_out = nullptr; const int32_t* lengths = nullptr;       // dmel_forward_dev_fixed_spec: the spectrogram is saved too; per-clip lengths (device)
+    bool fb_len = false;        // lengths through a trained bank (dmel_forward_dev_fixed_lengths, dmel_backward_fb_dev_lengths): dmel_fwd_fb_len_kernel -- kTrainH, kSpec, spec_out
     MultiLaunch ml;
     bool multi() const { return ml.channels > 0; }
     // DMEL_FLAG_X_INDIRECT: x is a pointer cell that holds the batch's address, read by every kernel of the forward
@@ -965,7 +966,7 @@ dmel_status forward_fused(dmel_plan* pl, NfftTables* tb, const dmel::LamArgs& la
     fp.B = c.batch; fp.L = pl->cfg.n_points; fp.T = pl->T; fp.hop = pl->cfg.hop_length; fp.M = pl->cfg.n_mels;
     fp.nchunks = pl->nchunks; fp.groups = tb->groups; fp.xch_groups = tb->xch_groups;
     // DMEL_FLAG_MFMA_BF16X3: the training forward through a caller-supplied (dense) bank contracts on the bf16 matrix pipe
-    const bool hsplit = (flags & DMEL_FLAG_MFMA_BF16X3) && mode == dmel::kTrain && tb->ent_h != nullptr && !c.lengths;
+    const bool hsplit = (flags & DMEL_FLAG_MFMA_BF16X3) && mode == dmel::kTrain && tb->ent_h != nullptr && (!c.lengths || c.fb_len);
     if (hsplit) mode = dmel::kTrainH;
     // the wave-local contraction where it is built (n_fft 1024, up to 512 mel bands): DMEL_WLC=0 keeps the round-4 kernel, DMEL_WLC=1
     // the 8-wave workgroups, DMEL_WLC=2 the 16-wave ones where they are built (diagnostics).
@@ -1009,9 +1010,15 @@ dmel_status forward_fused(dmel_plan* pl, NfftTables* tb, const dmel::LamArgs& la
     dmel::FwdBandParams bp{};
     dmel::FwdBandLenParams blp{};
     blp.lengths = c.lengths;
+    dmel::FwdFbLenParams flp{};
+    flp.lengths = c.lengths;
+    // (a trained bank's lengths: kInfer -- a forward without a tangent -- is dmel_fwd_len_kernel's, which contracts through whatever tables the plan holds;
+    // the wave-local contraction, never chosen for a dense bank at the sizes it is built for, has no build in that unit)
+    const bool fbk = c.fb_len && !ml && (mode == dmel::kTrain || mode == dmel::kTrainH || mode == dmel::kSpec);
+    if (c.lengths && c.spec_out && !fbk) return fail(DMEL_ERR_UNSUPPORTED, "per-clip lengths: the spectrogram is saved by the kTrain / kTrainH kernels of a trained bank only");
     for (int ch = 0; band && ch <= dmel::kMaxChannels; ++ch) blp.band_edges[ch] = bp.band_edges[ch] = ml->edges[std::min(ch, ml->channels)];
     auto launch = [&](auto& q) { static_cast<dmel::FwdParams&>(q) = fp; return dmel::launch_forward(N, mode, tpw, q, (int)grid, s); };
-    DMEL_HIP(c.lengths ? (band ? launch(blp) : ml ? launch(mlp) : launch(lp)) : band ? launch(bp) : launch(fp));
+    DMEL_HIP(c.lengths ? (band ? launch(blp) : ml ? launch(mlp) : fbk ? launch(flp) : launch(lp)) : band ? launch(bp) : launch(fp));
     info->kernel_path = 0; info->frames_per_tile = fpt; info->grid_fwd = (int)grid;
     info->fb_blocks = tb->n_entries; info->fb_blocks_dense = tb->n_dense;
     info->lds_bytes = dmel::forward_lds_bytes(N, mode);
@@ -1029,7 +1036,8 @@ dmel_status launch_forward_n(dmel_plan* pl, int N, const dmel::LamArgs& lam, con
     const bool pow2 = (N & (N - 1)) == 0;
     const bool big = !pow2 || N > dmel::kMaxNfft;
     // per-clip lengths (dmel_fwd_len_kernel; multi-window: dmel_fwd_multi_len_kernel / dmel_fwd_band_len_kernel): the fused kernel's range, the HTK bank
-    if (c.lengths && (big || N < dmel::kMinFastNfft || c.spec_out || c.win_half))
+    // (a saved spectrogram and the spectrogram modes: the calls of a trained bank, c.fb_len, alone)
+    if (c.lengths && (big || N < dmel::kMinFastNfft || ((c.spec_out || c.mode == dmel::kSpec) && !c.fb_len) || c.win_half))
         return fail(DMEL_ERR_UNSUPPORTED, "per-clip lengths run the fused kernel only: n_fft 32 ... 16384 (n_fft = " + std::to_string(N) + ")");
     if (c.multi() && (big || N < dmel::kMinFastNfft || c.spec_out))
         return fail(DMEL_ERR_UNSUPPORTED, "the multi-window layer runs n_fft 32 ... 16384 only (n_fft = " + std::to_string(N) + ")");
@@ -1568,6 +1576,8 @@ size_t dmel_scratch_bytes(const dmel_plan* plan, int32_t batch)
     return scratch_bytes(plan, batch);
 }
 
+static dmel_status forward_dev_fixed_issue(dmel_plan* plan, const FwdCall& c, const float* lambd_dev, int32_t n_fft, void* scratch, void* stream);
+
 // dmel_forward_dev and dmel_forward_dev_lengths (c.lengths: the launches stay in the fused kernel's range): K = 1 of the host steps dmel_forward_multi_dev runs
 static dmel_status forward_dev_impl(dmel_plan* plan, const FwdCall& c, const float* lambd_dev, void* scratch, void* stream)
 {
@@ -1686,6 +1696,14 @@ dmel_status dmel_forward_dev_fixed_spec(dmel_plan* plan, const float* x, int32_t
         if (n_fft < 1 || n_fft > dmel::kMaxNfft || (n_fft & (n_fft - 1)))
             return fail(DMEL_ERR_INVALID_ARGUMENT, "n_fft must be a power of two in [1, 16384]");
     }
+    return forward_dev_fixed_issue(plan, c, lambd_dev, n_fft, scratch, stream);
+}
+
+// the launch of the fixed-n_fft forwards (dmel_forward_dev_fixed, _spec, _lengths), their arguments checked: lambd is read and checked against n_fft on the device
+static dmel_status forward_dev_fixed_issue(dmel_plan* plan, const FwdCall& c, const float* lambd_dev, int32_t n_fft, void* scratch, void* stream)
+{
+    dmel_status st = DMEL_OK;
+    const int batch = c.batch;
     std::lock_guard<std::mutex> lock(plan->mu);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const Tracked t{&plan->track, plan->host_words, 1, false};
@@ -1706,6 +1724,25 @@ dmel_status dmel_forward_dev_fixed_spec(dmel_plan* plan, const float* x, int32_t
     plan->track.last_guards = 0;
     bool sums_done = false;
     return launch_forward_n(plan, n_fft, lam, c, sc, s, &sums_done);
+}
+
+// dmel_forward_dev_fixed(_spec) over clips of per-clip lengths: the forward of a trained filterbank on a zero-padded batch
+dmel_status dmel_forward_dev_fixed_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev, int32_t n_fft,
+                                           uint32_t flags, double eps, void* out, float* tangent, float* spec, void* scratch, void* stream)
+{
+    if (!plan || !x || !lengths || !out || !lambd_dev)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_fixed_lengths: plan / x / lengths / lambd_dev / out is NULL");
+    if (spec && !tangent) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_fixed_lengths: tangent is NULL (the training forward saves the spectrogram)");
+    if (flags & ~(DMEL_FLAG_LOG | DMEL_FLAG_OUT_BF16 | DMEL_FLAG_MFMA_BF16X3))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_forward_dev_fixed_lengths: flags other than LOG, OUT_BF16, MFMA_BF16X3");
+    dmel_status st = check_store_aligned("dmel_forward_dev_fixed_lengths", {{"out", out}, {"tangent", tangent}, {"spec", spec}, {"scratch", scratch}});
+    if (st != DMEL_OK) return st;
+    if (n_fft < dmel::kMinFastNfft || n_fft > dmel::kMaxFastNfft || (n_fft & (n_fft - 1)))
+        return fail(DMEL_ERR_UNSUPPORTED, "dmel_forward_dev_fixed_lengths: n_fft must be a power of two in [32, 16384]");
+    if ((st = check_forward_args(plan, x, batch, out)) != DMEL_OK) return st;
+    FwdCall c = mel_call(x, batch, flags, eps, out, tangent);
+    c.spec_out = spec; c.lengths = lengths; c.fb_len = true;
+    return forward_dev_fixed_issue(plan, c, lambd_dev, n_fft, scratch, stream);
 }
 
 dmel_status dmel_plan_lambd_status(dmel_plan* plan, dmel_lambd_status* status)
@@ -2190,6 +2227,7 @@ struct FbGradCall {
     const float* x = nullptr; int batch = 0; float lambd = 0.f; const float* lambd_dev = nullptr; int n_fft_dev = 0; uint32_t flags = 0;
     const float* grad_out = nullptr; const float* out = nullptr; float* grad_fb = nullptr; const float* saved_spec = nullptr;
     const float* tangent = nullptr; float* dlambd = nullptr; void* scratch = nullptr;
+    const int32_t* lengths = nullptr;       // per-clip lengths (device): dmel_backward_fb_dev_lengths, dmel_backward_fb_saved_lengths
 };
 
 dmel_status backward_fb_impl(dmel_plan* plan, const FbGradCall& c, void* stream)
@@ -2234,6 +2272,7 @@ dmel_status backward_fb_impl(dmel_plan* plan, const FbGradCall& c, void* stream)
     if ((st = grow_floats(&plan->fbw, &plan->fbw_floats, spec_floats + part_floats, s, "")) != DMEL_OK) return st;
     // the spectrogram the layer contracted at models.py:53 (DC removed, models.py:38): P is recomputed, not saved
     FwdCall sp = spec_call(c.x, batch, plan->fbw, nullptr, DMEL_SPEC_REMOVE_DC | (full ? DMEL_SPEC_HALF_WINDOW : 0u));
+    sp.lengths = c.lengths; sp.fb_len = c.lengths != nullptr;      // (the recompute pass over clips of Lc samples: dmel_fwd_fb_len_kernel, kSpec)
     if (c.saved_spec) {
         st = DMEL_OK;
     } else if (c.lambd_dev && !full) {
@@ -2255,6 +2294,7 @@ dmel_status backward_fb_impl(dmel_plan* plan, const FbGradCall& c, void* stream)
     fp.gm_ws = plan->fbw + spec_floats + part_floats;
     fp.B = batch; fp.F = F; fp.M = M; fp.T = T; fp.splits = splits;
     fp.bf16x3 = (c.flags & DMEL_FLAG_MFMA_BF16X3) ? 1 : 0;
+    fp.lengths = c.lengths; fp.hop = plan->cfg.hop_length;
     if (dot_wgs > 0) {
         fp.dot_g = c.grad_out; fp.dot_t = c.tangent; fp.dot_count = dot_count; fp.dot_partials = rsc.partials; fp.dot_counter = rsc.counter;
         fp.dot_result = c.dlambd; fp.dot_vblocks = dot_vblocks; fp.dot_wgs = dot_wgs; fp.dot_accumulate = 0;
@@ -2315,6 +2355,48 @@ dmel_status dmel_backward_fb_saved_dl(dmel_plan* plan, const float* spec, int32_
     FbGradCall c;
     c.batch = batch; c.n_fft_dev = n_fft; c.flags = flags; c.grad_out = grad_out; c.out = out; c.grad_fb = grad_fb; c.saved_spec = spec;
     c.tangent = tangent; c.dlambd = dlambd; c.scratch = scratch;
+    return backward_fb_impl(plan, c, stream);
+}
+
+// the two filterbank gradients over clips of per-clip lengths: the recompute path (a kSpec pass with lengths in front of the GEMM) and the saved spectrogram
+static dmel_status fb_lengths_args(const char* who, dmel_plan* plan, const void* first, const int32_t* lengths, int32_t batch, int32_t n_fft, uint32_t flags,
+                                   const float* grad_out, const float* out, float* grad_fb)
+{
+    const std::string w(who);
+    if (!plan || !first || !lengths || !grad_out || !grad_fb)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": plan / " + (w.find("saved") != std::string::npos ? "spec" : "x / lambd_dev") + " / lengths / grad_out / grad_fb is NULL");
+    if (batch <= 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": batch must be positive");
+    if (flags & ~(DMEL_FLAG_LOG | DMEL_FLAG_MFMA_BF16X3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": flags other than LOG, MFMA_BF16X3");
+    if ((flags & DMEL_FLAG_LOG) && !out) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": DMEL_FLAG_LOG needs the saved log output");
+    if (n_fft < dmel::kMinFastNfft || n_fft > dmel::kMaxFastNfft || (n_fft & (n_fft - 1)))
+        return fail(DMEL_ERR_UNSUPPORTED, w + ": n_fft must be a power of two in [32, 16384]");
+    return DMEL_OK;
+}
+
+dmel_status dmel_backward_fb_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev, int32_t n_fft,
+                                         uint32_t flags, const float* grad_out, const float* out, float* grad_fb, void* stream)
+{
+    dmel_status st = fb_lengths_args("dmel_backward_fb_dev_lengths", plan, (x && lambd_dev) ? (const void*)x : nullptr, lengths, batch, n_fft, flags, grad_out, out, grad_fb);
+    if (st != DMEL_OK) return st;
+    if ((st = check_store_aligned("dmel_backward_fb_dev_lengths", {{"grad_fb", grad_fb}})) != DMEL_OK) return st;
+    FbGradCall c;
+    c.x = x; c.batch = batch; c.lambd_dev = lambd_dev; c.n_fft_dev = n_fft; c.flags = flags; c.grad_out = grad_out; c.out = out; c.grad_fb = grad_fb;
+    c.lengths = lengths;
+    return backward_fb_impl(plan, c, stream);
+}
+
+dmel_status dmel_backward_fb_saved_lengths(dmel_plan* plan, const float* spec, const int32_t* lengths, int32_t batch, int32_t n_fft, uint32_t flags,
+                                           const float* grad_out, const float* out, const float* tangent, float* grad_fb, float* dlambd,
+                                           void* scratch, void* stream)
+{
+    dmel_status st = fb_lengths_args("dmel_backward_fb_saved_lengths", plan, spec, lengths, batch, n_fft, flags, grad_out, out, grad_fb);
+    if (st != DMEL_OK) return st;
+    if ((tangent == nullptr) != (dlambd == nullptr))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_backward_fb_saved_lengths: tangent and dlambd are given together (d lambd in the same launch) or both NULL");
+    if ((st = check_store_aligned("dmel_backward_fb_saved_lengths", {{"grad_fb", grad_fb}, {"scratch", scratch}})) != DMEL_OK) return st;
+    FbGradCall c;
+    c.batch = batch; c.n_fft_dev = n_fft; c.flags = flags; c.grad_out = grad_out; c.out = out; c.grad_fb = grad_fb; c.saved_spec = spec;
+    c.tangent = tangent; c.dlambd = dlambd; c.scratch = scratch; c.lengths = lengths;
     return backward_fb_impl(plan, c, stream);
 }
 

@@ -5,6 +5,7 @@
 //                    cross-check of the wave-FFT kernel; same semantics (models.py:33-56, :73).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include "dmel_kernels.h"
 #include "dmel_ldsfft.h"
 
@@ -653,6 +654,7 @@ template <int B, int E, class Fn> __device__ __forceinline__ void unrolled(Fn&& 
     if constexpr (B < E) { f(IdxC<B>{}); unrolled<B + 1, E>(f); }
 }
 struct __attribute__((packed, aligned(4))) f4u { float v[4]; };       // 16-byte load that only needs 4-byte alignment
+typedef float f4v __attribute__((ext_vector_type(4), aligned(4)));       // ... as a vector value
 
 // One workgroup of 8 waves owns a 64 (freq) x 128 (mel) tile of grad_fb for one slice of the batch: wave (wf, wm) the 32 x 32
 // sub-tile (2 x 2 MFMA tiles).  A K-block is 16 time steps of one clip: spec[b][f0 .. f0+63][t .. t+15] and gm[b][0 .. 127][t .. t+15]
@@ -770,7 +772,13 @@ __device__ void fbgrad_dot_body(const FbGradParams& p, int wg)
     }
 }
 
-template <bool LOG, bool TINY, bool BF16X3 = false>
+// LEN (FbGradParams::lengths; dmel_backward_fb_*_lengths): clip b has Tc = lengths[b] / hop + 1 frames.  The slices stay the static cuts of the
+// padded grid B x ceil(T / 16); inside its slice a workgroup walks only the K-blocks that hold a frame of their clip (16 nblk < Tc) -- the
+// others are neither requested nor multiplied -- so that with every length at n_points the requests, their order and the sums are those of
+// the build without lengths.  Tc is read once per clip, when the walk enters it (one scalar load: uniform over the workgroup); the row-end
+// clamp and the shift of in_place take Tc for T, and a clip shorter than a 16-byte piece (Tc < 4 in a launch with T >= 4) is requested
+// element by element: min(t, Tc - 4) would start in front of the row.  Nothing of spec, grad_out or out is loaded at t >= Tc.
+template <bool LOG, bool TINY, bool BF16X3 = false, bool LEN = false>
 __global__ void __launch_bounds__(kFbgThreads) dmel_fbgrad_lds_kernel(FbGradParams p)
 {
     if (p.dot_wgs > 0 && (int)blockIdx.y >= p.splits) {
@@ -796,8 +804,25 @@ __global__ void __launch_bounds__(kFbgThreads) dmel_fbgrad_lds_kernel(FbGradPara
     // first request -- 9 k cycles from the first instruction to the first load issued, a quarter of a wave's life at config 2)
     const int ntc = p.ntc;
     const int blk_lo = split * p.blk_base + min(split, p.blk_rem);
-    const int total = p.blk_base + (split < p.blk_rem ? 1 : 0);
+    const int total_all = p.blk_base + (split < p.blk_rem ? 1 : 0);
     const int b_lo = (int)((unsigned)blk_lo / (unsigned)ntc);
+    // LEN: frames of clip b (T for a length the forward refused: that clip's spectrogram is NaN over all T frames, and so is the gradient)
+    auto clip_frames = [&](int b) -> int {
+        const int lc = *(const __attribute__((address_space(4))) int*)(p.lengths + b);
+        const int q = lc / p.hop;
+        return __builtin_amdgcn_readfirstlane((lc >= 1 && q < T) ? q + 1 : T);
+    };
+    int total_len = 0;                                              // LEN: the K-blocks of this slice that hold a frame
+    [[maybe_unused]] int tc_cur = T, nvb = ntc;                     // LEN: frames and K-blocks with a frame of the clip the requests are in
+    if constexpr (LEN) {
+        const int blk_hi = blk_lo + total_all;
+        for (int b = b_lo; b * ntc < blk_hi; ++b) {                 // (b < B: blk_hi <= B ntc)
+            const int nv = (clip_frames(b) + 15) >> 4;
+            total_len += max(min(min(blk_hi - b * ntc, ntc), nv) - max(blk_lo - b * ntc, 0), 0);
+        }
+        if (total_all > 0) { tc_cur = clip_frames(b_lo); nvb = (tc_cur + 15) >> 4; }
+    }
+    const int total = LEN ? total_len : total_all;
     // staging roles: every thread one 16-byte piece of the B tile (row tid / 4, piece tid % 4), threads 0 .. 255 one of the A tile
     const int srow = tid >> 2, sc = tid & 3;
     const int mrow = min(m0 + srow, M - 1);                       // rows past the edge: valid memory, results never stored
@@ -826,10 +851,48 @@ __global__ void __launch_bounds__(kFbgThreads) dmel_fbgrad_lds_kernel(FbGradPara
     // the compiler loaded into temporaries and moved them (s_waitcnt vmcnt right behind every request): the ring never held
     // more than one block in flight, 2 k cycles per request in the prologue alone (tools/fstamps.py).  Every thread requests a
     // piece of A (threads that park none re-read one row: 16 bytes of L1 traffic).  Rows shorter than a piece: TINY, element-wise.
-    int ring_t[DEPTH];
-    auto fetch = [&](float4& ra, float4& rg, float4& ry, int& rt) {
+    // (LEN: a request carries the end of its row next to t -- .x = t, .y = Tc, or for a piece requested element by element, already in
+    // place, an end that in_place leaves alone)
+    using ReqT = std::conditional_t<LEN, int2, int>;
+    ReqT ring_t[DEPTH];
+    [[maybe_unused]] int b_cur = b_lo;                              // LEN: the clip the requests are in
+    auto fetch = [&](float4& ra, float4& rg, float4& ry, ReqT& rt) {
         if (left <= 0) return;
         --left;
+        if constexpr (LEN) {
+            // the walk leaves a clip behind its last block with a frame (left > 0: the slice holds another such block, so the next clip
+            // exists and, having a frame, starts with one)
+            if (nblk >= nvb) {
+                nblk = 0; ++b_cur; pg += step_g; pa += step_a; if constexpr (LOG) py += step_g;
+                tc_cur = clip_frames(b_cur); nvb = (tc_cur + 15) >> 4;
+            }
+            const int t = nblk * 16 + 4 * sc;
+            const int Tc = tc_cur;
+            const bool wide = !TINY && Tc >= 4;                     // (uniform over the workgroup)
+            rt = make_int2(t, wide ? Tc : 0x3fffffff);
+            // (both paths leave plain floats and the ring's float4 is put together behind them: assigned as aggregates under the branch, or loaded
+            // as the f4u copies of the build without lengths, the ring lived in scratch memory)
+            float g0, g1, g2, g3, a0, a1, a2, a3, y0 = 0.f, y1 = 0.f, y2 = 0.f, y3 = 0.f;
+            if (wide) {
+                const int tl = min(t, Tc - 4);
+                const f4v g = *reinterpret_cast<const f4v*>(pg + tl);
+                const f4v a = *reinterpret_cast<const f4v*>(pa + tl);
+                g0 = g.x; g1 = g.y; g2 = g.z; g3 = g.w;
+                a0 = a.x; a1 = a.y; a2 = a.z; a3 = a.w;
+                if constexpr (LOG) { const f4v y = *reinterpret_cast<const f4v*>(py + tl); y0 = y.x; y1 = y.y; y2 = y.z; y3 = y.w; }
+            } else {
+                // entry t + u of the row, or 0 behind its end (the load is clamped into the row: nothing at or past Tc is read)
+                auto elem = [&](const float* q, int u) -> float { const float v = q[min(t + u, Tc - 1)]; return t + u < Tc ? v : 0.f; };
+                g0 = elem(pg, 0); g1 = elem(pg, 1); g2 = elem(pg, 2); g3 = elem(pg, 3);
+                a0 = elem(pa, 0); a1 = elem(pa, 1); a2 = elem(pa, 2); a3 = elem(pa, 3);
+                if constexpr (LOG) { y0 = elem(py, 0); y1 = elem(py, 1); y2 = elem(py, 2); y3 = elem(py, 3); }
+            }
+            rg = make_float4(g0, g1, g2, g3);
+            ra = make_float4(a0, a1, a2, a3);
+            ry = make_float4(y0, y1, y2, y3);
+            ++nblk;
+            return;
+        } else {
         const int t = nblk * 16 + 4 * sc;
         rt = t;
         if constexpr (!TINY) {
@@ -855,17 +918,25 @@ __global__ void __launch_bounds__(kFbgThreads) dmel_fbgrad_lds_kernel(FbGradPara
             ra = make_float4(ga[0], ga[1], ga[2], ga[3]);
         }
         if (++nblk == ntc) { nblk = 0; pg += step_g; pa += step_a; if constexpr (LOG) py += step_g; }
+        }
     };
     // entries t .. t + 3 of a row of T, of which the request fetched min(t, T - 4) .. : shift left by sh = t - (T - 4), zeros behind
-    auto in_place = [&](float4 v, int t) -> float4 {
-        const int sh = t - (T - 4);
+    // (LEN: of a row of Tc)
+    auto in_place = [&](float4 v, ReqT t) -> float4 {
+        int sh;
+        if constexpr (LEN) {
+            // (the same shift as below, written as selects per component)
+            sh = t.x - (t.y - 4);
+            auto pick = [&](float e0, float e1, float e2, float e3) { return sh <= 0 ? e0 : sh == 1 ? e1 : sh == 2 ? e2 : sh == 3 ? e3 : 0.f; };
+            return make_float4(pick(v.x, v.y, v.z, v.w), pick(v.y, v.z, v.w, 0.f), pick(v.z, v.w, 0.f, 0.f), pick(v.w, 0.f, 0.f, 0.f));
+        } else sh = t - (T - 4);
         if (TINY || sh <= 0) return v;
         if (sh == 1) return make_float4(v.y, v.z, v.w, 0.f);
         if (sh == 2) return make_float4(v.z, v.w, 0.f, 0.f);
         if (sh == 3) return make_float4(v.w, 0.f, 0.f, 0.f);
         return make_float4(0.f, 0.f, 0.f, 0.f);
     };
-    auto park = [&](int buf, float4 ra, float4 rg, float4 ry, int t) {
+    auto park = [&](int buf, float4 ra, float4 rg, float4 ry, ReqT t) {
         ra = in_place(ra, t); rg = in_place(rg, t);
         float4 rb = rg;
         if constexpr (LOG) {
@@ -905,7 +976,7 @@ __global__ void __launch_bounds__(kFbgThreads) dmel_fbgrad_lds_kernel(FbGradPara
         const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
         unrolled<0, DEPTH>([&](auto dd) {
             constexpr int d = decltype(dd)::value;
-            ring_a[d] = zero; ring_g[d] = zero; ring_y[d] = zero; ring_t[d] = 0;
+            ring_a[d] = zero; ring_g[d] = zero; ring_y[d] = zero; ring_t[d] = ReqT{};
             fetch(ring_a[d], ring_g[d], ring_y[d], ring_t[d]);
         });
         FSTAMP(1);   // first requests issued
@@ -1107,6 +1178,19 @@ hipError_t launch_fbgrad(const FbGradParams& p_in, hipStream_t s)
     const int row_tiles = fbgrad_row_tiles(p.F);
     const int dot_rows = p.dot_wgs > 0 ? (p.dot_wgs + row_tiles - 1) / row_tiles : 0;      // (the caller made sure grid.z is 1 then)
     const dim3 grid(row_tiles, p.splits + dot_rows, (p.M + kFbgBM - 1) / kFbgBM);
+    if (p.lengths) {
+        // the length-aware build of each of the eight kernels below
+        if (p.hop < 1) return hipErrorInvalidValue;
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(kFbgThreads), 0, s, p); };
+        const bool tiny = p.T < 4;
+        if (p.bf16x3) {
+            if (tiny) { if (p.out) go(dmel_fbgrad_lds_kernel<true, true, true, true>); else go(dmel_fbgrad_lds_kernel<false, true, true, true>); }
+            else { if (p.out) go(dmel_fbgrad_lds_kernel<true, false, true, true>); else go(dmel_fbgrad_lds_kernel<false, false, true, true>); }
+        } else {
+            if (tiny) { if (p.out) go(dmel_fbgrad_lds_kernel<true, true, false, true>); else go(dmel_fbgrad_lds_kernel<false, true, false, true>); }
+            else { if (p.out) go(dmel_fbgrad_lds_kernel<true, false, false, true>); else go(dmel_fbgrad_lds_kernel<false, false, false, true>); }
+        }
+    } else
     if (p.bf16x3) {
         if (p.T < 4) {
             if (p.out) hipLaunchKernelGGL((dmel_fbgrad_lds_kernel<true, true, true>), grid, dim3(kFbgThreads), 0, s, p);

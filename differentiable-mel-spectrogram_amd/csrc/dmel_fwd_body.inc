@@ -5,6 +5,8 @@
 // dmel_fwd_band.hip includes it with DMEL_FWD_MULTI = 1 and DMEL_FWD_BAND = 1: dmel_fwd_band_kernel (BandSplitMelSpectrogram, FwdBandParams) -- the
 // multi-window kernel's channel addressing, but all channels write ONE (B, 1, M, T) image and channel c only its rows [e_c, e_c+1): the
 // contraction work of the other rows is skipped where a whole tile / phase lies outside them and every store site is confined to them.
+// dmel_fwd_fb_len.hip includes it with DMEL_FWD_LEN = 1 and DMEL_FWD_FB = 1: dmel_fwd_fb_len_kernel (FwdFbLenParams), the length-aware builds a trained
+// filterbank needs -- kTrainH, kSpec and a kTrain whose saved spectrogram follows the lengths; what differs sits behind DMEL_FWD_FB.
 // The two axes compose: DMEL_FWD_LEN = 1 on top of DMEL_FWD_MULTI (and DMEL_FWD_BAND) makes dmel_fwd_multi_len_kernel (dmel_fwd_multi_len.hip,
 // FwdMultiLenParams) and dmel_fwd_band_len_kernel (dmel_fwd_band_len.hip, FwdBandLenParams): the K-window layers over clips of per-clip lengths.
 #if DMEL_FWD_MULTI
@@ -30,7 +32,10 @@
 #define FWD_LAM p.lam
 #define FWD_WIN2 p.win2
 #define FWD_LEADER blockIdx.x == 0
-#if DMEL_FWD_LEN
+#if DMEL_FWD_LEN && DMEL_FWD_FB
+#define FWD_KERNEL dmel_fwd_fb_len_kernel
+#define FWD_PARAMS FwdFbLenParams
+#elif DMEL_FWD_LEN
 #define FWD_KERNEL dmel_fwd_len_kernel
 #define FWD_PARAMS FwdLenParams
 #else
@@ -410,8 +415,20 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
         LamState ls1 = ls0;
         if constexpr (TRAINLIKE || MODE == kSpecTrain) { if (!p.normalize) ls1 = lam_clip_scale(ls0, g.WIN_LDS ? FWD_LC : p.L); }      // (the modes that write a tangent)
         const LamState ls = ls1;
+#if DMEL_FWD_LEN && DMEL_FWD_FB
+        // the trained bank's builds: a length outside 1 ... L takes the NaN loop of an uncovered launch -- the clip's rows and tangent, and its whole
+        // (F, T) spectrogram (kSpec's output, or spec_out): the filterbank gradient sums such a clip over all T frames.  (A loop of its own behind
+        // the coverage check cost kSpec 4 ... 6 spilled registers more than dmel_fwd_kernel's at n_fft 2048 ... 8192.)
+        // A pad tile leaves through the same exit (one more return behind the coverage check cost as much).
+        const bool bad_len = ls.action == kLamRun && !len_ok;
+        const bool pad_tile = ls.action == kLamRun && len_ok && tile0 * FPT >= Tc;
+        if (ls.action != kLamRun || bad_len || pad_tile) {
+            if constexpr (!IS_SPEC) { if (pad_tile) fill_rows(tile0 * FPT, (tile0 + TPW) * FPT, true); }      // (kSpec: nothing -- the filterbank gradient stops at Tc)
+            if (ls.action == kLamPoison || bad_len) {
+#else
         if (ls.action != kLamRun) {
             if (ls.action == kLamPoison) {
+#endif
                 // no launch of this forward matched the device lambd: NaN instead of stale memory (the host raises too)
 #if DMEL_FWD_BAND
                 const int rows = p.M, nrows = e_hi - e_lo, row0 = e_lo;              // this channel's rows only: the other groups' stay as they are
@@ -443,10 +460,12 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
 #if DMEL_FWD_LEN
         // a workgroup whose first frame lies past the clip transforms nothing: it writes its pad rows (or NaN rows for an invalid length) and is
         // done.  (Behind the coverage check: only the launch whose n_fft the device lambd selects writes.)
+#if !DMEL_FWD_FB
         if (!len_ok || tile0 * FPT >= Tc) {
             fill_rows(tile0 * FPT, (tile0 + TPW) * FPT, len_ok);
             return;
         }
+#endif
 #endif
         if constexpr (WPF > 1) {
             if (tid < 4) fctr[tid] = 0u;                                  // the frames' meeting counters (sync_frame)
@@ -755,8 +774,16 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                     // samples of the clip only; a pad frame (Tc <= t < T) is all zero: its spectrum, mel power and tangent are exactly 0.  Frames
                     // past the output (t >= T, never written) keep the default path's samples: the pair modes' two frames of a complex FFT share
                     // its rounding, and with Lc = L every frame must come out as dmel_fwd_kernel's
+#if DMEL_FWD_FB
+                    // (kSpec of a trained bank's build: the filterbank gradient never loads the column of a pad frame, so such a frame keeps the
+                    // clip's samples it overlaps -- one uniform bound, as dmel_fwd_kernel's p.L, instead of two per lane: at n_fft 2048 ... 8192 the
+                    // per-lane bounds cost 4 ... 6 spilled registers more than dmel_fwd_kernel's kSpec)
+                    const int lim_a = (IS_SPEC || tA < Tc || tA >= p.T) ? Lc : 0;
+                    [[maybe_unused]] const int lim_b = (IS_SPEC || tA + 1 < Tc || tA + 1 >= p.T) ? Lc : 0;
+#else
                     const int lim_a = (tA < Tc || tA >= p.T) ? Lc : 0;
                     [[maybe_unused]] const int lim_b = (tA + 1 < Tc || tA + 1 >= p.T) ? Lc : 0;
+#endif
 #define FWD_LIM_A lim_a
 #define FWD_LIM_B lim_b
 #else
@@ -784,7 +811,12 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                 // (radix-8 and radix-4 plans, n_fft 32 ... 128: the windowed samples are materialised before the transform.  Without this the
                 // backend fused two window products into the first butterflies (two v_pk_mul_f32 + v_pk_add_f32 became v_pk_fma_f32), which
                 // dmel_fwd_kernel does not: full-length clips came out 1 - 2 ulp off the default path.  With it both round alike.)
+                // (kSpec of a trained bank's build, DMEL_FWD_FB: not there -- dmel_fwd_kernel's kSpec does fuse them)
+#if DMEL_FWD_FB
+                if constexpr (R <= 8 && !IS_SPEC) {
+#else
                 if constexpr (R <= 8) {
+#endif
 #pragma unroll
                     for (int a = 0; a < R; ++a) asm volatile("" : "+v"(z[a]));
                 }

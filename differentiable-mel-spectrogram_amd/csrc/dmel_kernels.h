@@ -452,6 +452,11 @@ struct FwdMultiLenParams : FwdParams {
 struct FwdBandLenParams : FwdBandParams {
     const int* lengths;         // (B) device, as FwdLenParams::lengths
 };
+// dmel_fwd_fb_len_kernel (csrc/dmel_fwd_fb_len.hip): the scalar layer's launch over clips of per-clip lengths through a trained (dense) filterbank --
+// kTrainH, kSpec (the filterbank gradient's recompute pass) and kTrain with spec_out.  A type of its own: the kernel follows the parameter type.
+struct FwdFbLenParams : FwdParams {
+    const int* lengths;         // (B) device, as FwdLenParams::lengths
+};
 
 struct PrepParams {
     const float* x; float* psum; float2* win2;
@@ -466,12 +471,13 @@ struct PrepParams {
 
 hipError_t launch_prep(const PrepParams& p, hipStream_t s);
 // the fused forward: the kernel is picked by the parameter type (dmel_fwd.hip, dmel_fwd_len.hip, dmel_fwd_band.hip, dmel_fwd_multi_len.hip,
-// dmel_fwd_band_len.hip)
+// dmel_fwd_band_len.hip, dmel_fwd_fb_len.hip)
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdParams& p, int grid, hipStream_t s);
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdLenParams& p, int grid, hipStream_t s);    // kTrain, kTrainW, kInfer
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdBandParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdMultiLenParams& p, int grid, hipStream_t s);   // kTrain, kTrainW, kInfer
 hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdBandLenParams& p, int grid, hipStream_t s);    // kTrain, kTrainW, kInfer
+hipError_t launch_forward(int n_fft, int mode, int tiles_per_wg, const FwdFbLenParams& p, int grid, hipStream_t s);      // kTrain, kTrainH, kSpec
 int forward_tiles_per_wg(int n_fft, int mode, int batch, int tiles_per_clip);          // 1 or 2: what launch_forward should be given
 bool forward_two_tiles(int n_fft, int mode);          // the two-tiles-per-workgroup instantiation exists for this size and mode
 int forward_lds_bytes(int n_fft, int mode);
@@ -663,6 +669,10 @@ struct FbGradParams {
     // the same order of additions, the same bits -- four virtual blocks each.  dot_wgs = 0: no such workgroups.
     const float* dot_g; const float* dot_t; long long dot_count; double* dot_partials; unsigned* dot_counter; float* dot_result;
     int dot_vblocks, dot_wgs, dot_accumulate;
+    // per-clip lengths (dmel_backward_fb_*_lengths; behind every other field: the kernels without lengths keep their argument layout): clip b has
+    // Tc = lengths[b] / hop + 1 frames (T for a length that gives none or more than T: the forward made that clip's spectrogram NaN); spec,
+    // grad_out and out are not loaded at t >= Tc.  nullptr: every clip has T frames
+    const int* lengths; int hop;
 };
 int dot_blocks_for(long long count, int max_partials);      // workgroups launch_dot uses for `count` elements
 int fbgrad_fuse_dot(int F, int M, int splits, int vblocks, int* dot_wgs);   // slices left when the launch also carries d lambd (0: do not)
@@ -747,6 +757,7 @@ hipError_t forward_len_prepare_attributes();
 hipError_t forward_band_prepare_attributes();
 hipError_t forward_multi_len_prepare_attributes();
 hipError_t forward_band_len_prepare_attributes();
+hipError_t forward_fb_len_prepare_attributes();
 hipError_t xgrad_prepare_attributes();
 hipError_t xgrad_len_prepare_attributes();
 hipError_t xgrad_band_prepare_attributes();
@@ -755,7 +766,7 @@ hipError_t big_prepare_attributes();
 inline hipError_t prepare_attributes()
 {
     for (auto unit : {forward_prepare_attributes, forward_len_prepare_attributes, forward_band_prepare_attributes, forward_multi_len_prepare_attributes,
-                      forward_band_len_prepare_attributes, xgrad_prepare_attributes,
+                      forward_band_len_prepare_attributes, forward_fb_len_prepare_attributes, xgrad_prepare_attributes,
                       xgrad_len_prepare_attributes, xgrad_band_prepare_attributes, xgrad_klen_prepare_attributes, big_prepare_attributes})
         if (const hipError_t e = unit(); e != hipSuccess) return e;
     return hipSuccess;

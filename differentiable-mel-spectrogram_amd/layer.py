@@ -190,13 +190,18 @@ class _DmelFbDevFunction(torch.autograd.Function):
     filterbank (its row count fixes n_fft: dmel_forward_dev_fixed checks lambd against it on the device) and the optimized=False
     branch (n_fft = 2 n_points whatever lambd is), with or without the gradients w.r.t. the filterbank (dmel_backward_fb_dev) and the
     waveform (dmel_backward_x_dev).  No host read anywhere: the step queues without waiting and can be captured into a HIP graph.
+    With ``lengths`` (a trainable filterbank with ``lengths_learnable_fb=True``; int32 on x's device) the forward is
+    dmel_forward_dev_fixed_lengths and the filterbank gradient dmel_backward_fb_saved_lengths / dmel_backward_fb_dev_lengths, which stop at
+    each clip's last frame; ``lengths`` is kept for the backward next to ``x`` and ``lam``.
 
     ``n_fft == 0`` (HTK bank, optimized=True, x.requires_grad): the tracked forward dmel_forward_dev -- one launch per candidate n_fft,
     the device value of lambd picks the one that works -- and a waveform gradient issued the same way (_tracked_backward_x)."""
 
     @staticmethod
-    def forward(ctx, x, lambd, plan, n_fft, log, eps, fb, out_dtype, full_window=False, mfma_flags=0, save_spec=False):
+    def forward(ctx, x, lambd, plan, n_fft, log, eps, fb, out_dtype, full_window=False, mfma_flags=0, save_spec=False, lengths=None):
         B = x.shape[0]
+        if lengths is not None and (n_fft == 0 or full_window or fb is None or ctx.needs_input_grad[0]):
+            raise ValueError("lengths here are a trainable filterbank's (fixed n_fft, optimized=True, no waveform gradient)")
         want_x, want_tangent = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         want_fb = fb is not None and ctx.needs_input_grad[6]
         tracked = n_fft == 0
@@ -211,7 +216,10 @@ class _DmelFbDevFunction(torch.autograd.Function):
         spec = torch.empty((B, n_fft // 2 + 1, plan.n_time), dtype=torch.float32, device=x.device) if keep_spec else None
         ctx.cands = None
         with _on_device(x.device):
-            if tracked:
+            if lengths is not None:
+                plan.forward_dev_fixed_lengths(x.data_ptr(), lengths.data_ptr(), B, lam.data_ptr(), n_fft, out.data_ptr(), _ptr(tangent), _ptr(spec),
+                                               log, eps, _stream_ptr(x.device), scratch.data_ptr(), extra_flags=flags | _out_flag(out))
+            elif tracked:
                 plan.forward_dev(x.data_ptr(), B, lam.data_ptr(), out.data_ptr(), _ptr(tangent), log, eps, _stream_ptr(x.device),
                                  scratch.data_ptr(), extra_flags=_out_flag(out))
                 ctx.cands = _launched_for(plan)
@@ -225,11 +233,14 @@ class _DmelFbDevFunction(torch.autograd.Function):
         ctx.lambd_shape, ctx.lambd_dtype = lambd.shape, lambd.dtype
         ctx.want_tangent, ctx.want_fb, ctx.want_x = want_tangent, want_fb, want_x
         ctx.fb_meta = None if fb is None else (tuple(fb.shape), fb.dtype)
+        ctx.has_lengths = lengths is not None
         saved = [scratch]
         if want_tangent:
             saved.append(tangent)
         if want_fb or want_x:
             saved += [x, lam]
+            if lengths is not None:
+                saved.append(lengths)
             if log:
                 saved.append(out)
         if keep_spec:
@@ -255,6 +266,7 @@ class _DmelFbDevFunction(torch.autograd.Function):
                     ctx.plan.backward_scratch(g.data_ptr(), tangent.data_ptr(), g.numel(), dl.data_ptr(), stream, scratch.data_ptr(), grad_bf16=bf16)
             if ctx.want_fb or ctx.want_x:
                 x, lam = saved.pop(0), saved.pop(0)
+                lengths = saved.pop(0) if ctx.has_lengths else None
                 out = saved.pop(0).to(torch.float32) if ctx.log else None
                 g32 = g.to(torch.float32)
             if ctx.want_x and ctx.cands is not None and max(ctx.cands) > 16384:
@@ -270,7 +282,14 @@ class _DmelFbDevFunction(torch.autograd.Function):
             if ctx.want_fb:
                 fb_shape, fb_dtype = ctx.fb_meta
                 gfb = torch.empty(fb_shape, dtype=torch.float32, device=g.device)
-                if ride:
+                if lengths is not None and spec is not None:
+                    ctx.plan.backward_fb_saved_lengths(spec.data_ptr(), lengths.data_ptr(), x.shape[0], ctx.n_fft, g32.data_ptr(), _ptr(out),
+                                                       tangent.data_ptr() if ride else None, gfb.data_ptr(), dl.data_ptr() if ride else None,
+                                                       scratch.data_ptr(), ctx.log, stream, extra_flags=ctx.flags)
+                elif lengths is not None:
+                    ctx.plan.backward_fb_dev_lengths(x.data_ptr(), lengths.data_ptr(), x.shape[0], lam.data_ptr(), ctx.n_fft, g32.data_ptr(),
+                                                     _ptr(out), gfb.data_ptr(), ctx.log, stream, extra_flags=ctx.flags)
+                elif ride:
                     ctx.plan.backward_fb_saved_dl(spec.data_ptr(), x.shape[0], ctx.n_fft, g32.data_ptr(), _ptr(out), tangent.data_ptr(),
                                                   gfb.data_ptr(), dl.data_ptr(), scratch.data_ptr(), ctx.log, stream, extra_flags=ctx.flags)
                 elif spec is not None:
@@ -282,7 +301,7 @@ class _DmelFbDevFunction(torch.autograd.Function):
                 gfb = gfb.to(fb_dtype)
             if dl is not None:
                 dl = _dl_like(dl, ctx.lambd_shape, ctx.lambd_dtype)
-        return gx, dl, None, None, None, None, gfb, None, None, None, None
+        return gx, dl, None, None, None, None, gfb, None, None, None, None, None
 
 
 class _DmelLenXFunction(torch.autograd.Function):
@@ -581,12 +600,27 @@ class MelSpectrogramLayer(_PlanCachingModule):
     the cotangent of pad frames is never read, and a length outside ``1 ... n_points`` makes the row ``x.grad[b]`` NaN.  With
     ``lambd_sync=False`` the step has no host read and can be captured.  A ``SlotInput`` carries no gradient (it is an address, not a
     tensor of the graph); ``learnable_fb`` and ``optimized=False`` refuse ``lengths`` with or without the flag.
+    ``lengths_learnable_fb=True`` (keyword-only, off by default, needs ``learnable_fb=True``) makes ``forward(x, lengths)`` run through
+    the trained ``mel_fb``: clip b is ``x[b, :lengths[b]]`` alone (its own mean, pad frames as above) contracted through the current
+    matrix, with ``mfma="fp32"`` or ``"bf16x3"``, fp32 or bf16 output.  ``lambd.grad`` is the usual dot over the tangent (zero in pad
+    frames); ``mel_fb.grad`` is ``sum_b sum_{t < frame_lengths(lengths)[b]} spec_b[f, t] * gm_b[m, t]`` with ``spec_b`` the spectrogram of
+    the clip at its own length -- the cotangent, the saved output and the spectrogram are never loaded in pad frames, and an invalid
+    length makes every element of ``mel_fb.grad`` NaN.  With every length at ``n_points`` the output and both gradients have the bits of
+    ``forward(x)``.  No host read of ``lengths`` (nor, with ``lambd_sync=False``, of ``lambd``): the step can be captured, and a replay
+    sees what ``lengths`` holds when it runs.  With ``lambd_sync=True`` the layer reads ``lambd`` and compares it with the bank's row
+    count as ``forward(x)`` does, then issues the same device-checked launches with what that ``forward(x)`` uses: the exact contraction and a
+    recomputed spectrogram.  There is no waveform gradient (``x.requires_grad`` raises), no ``SlotInput`` and no ``optimized=False``.
     """
 
     def __init__(self, init_lambd, n_mels, n_points, sample_rate, f_min=0, f_max=None, hop_length=1,
                  device="cpu", optimized=False, normalize_window=False, *, log=False, eps=1e-10, learnable_fb=False,
-                 out_dtype=torch.float32, lambd_sync=False, mfma="fp32", save_spec=True, lengths_waveform_grad=False):
+                 out_dtype=torch.float32, lambd_sync=False, mfma="fp32", save_spec=True, lengths_waveform_grad=False,
+                 lengths_learnable_fb=False):
         super().__init__()
+        if lengths_learnable_fb and not learnable_fb:
+            raise ValueError("lengths_learnable_fb=True is forward(x, lengths) through the trained filterbank: it needs learnable_fb=True")
+        self.lengths_learnable_fb = bool(lengths_learnable_fb)        # forward(x, lengths) runs through mel_fb (opt-in: without it a trained
+                                                                      # bank refuses lengths)
         self.lengths_waveform_grad = bool(lengths_waveform_grad)      # forward(x, lengths) accepts an x that requires grad (opt-in: that
                                                                       # forward keeps x, lengths and the fp32 output alive until the backward)
         if not torch.is_tensor(init_lambd):
@@ -665,7 +699,7 @@ class MelSpectrogramLayer(_PlanCachingModule):
         """Whether this layer takes per-clip lengths, then shape, dtype and device of ``lengths`` (_lengths_for_kernels); returns them as the
         kernels read them (int32, contiguous, on x's device).  Their values never leave the device."""
         want_x = self.lengths_waveform_grad and torch.is_grad_enabled() and not isinstance(x, SlotInput) and x.requires_grad
-        if self.mel_fb is not None:
+        if self.mel_fb is not None and not self.lengths_learnable_fb:
             raise RuntimeError("per-clip lengths run the HTK bank only: learnable_fb=True does not take lengths"
                                + (" (and has no waveform gradient with them)" if want_x else ""))
         if not self.optimized:
@@ -678,6 +712,8 @@ class MelSpectrogramLayer(_PlanCachingModule):
         """forward(x, lengths), both checked: torch.ops.dmel.mel_spectrogram_lengths (the hot path's C++ autograd node over
         dmel_forward_dev_lengths, or dmel_forward_lengths with lambd_sync).  With ``lengths_waveform_grad=True`` an ``x`` that requires
         grad takes _DmelLenXFunction instead: the same launches, and a backward to the waveform."""
+        if self.mel_fb is not None:
+            return self._forward_lengths_fb(x, lengths)
         flags = capi.DMEL_FLAG_LOG if self.log else 0
         bf16 = self.out_dtype == torch.bfloat16
         plan, lam = self._plan_for(x.device), _lambd_for_op(self.lambd)
@@ -690,8 +726,28 @@ class MelSpectrogramLayer(_PlanCachingModule):
                                            self.out_dtype)
         return _len_op()(xf, lengths, lam, plan.handle, flags, self.eps, self.lambd_sync, bf16)
 
+    def _forward_lengths_fb(self, x, lengths):
+        """forward(x, lengths) through the trained filterbank (lengths_learnable_fb=True), both checked: _DmelFbDevFunction with lengths.
+        The bank's row count fixes n_fft; lambd is read and checked against it on the device (one that has left it gives NaN now and
+        "tied to one n_fft" at the next forward).  lambd_sync: the layer reads lambd and compares first, as forward(x) does, and keeps that
+        path's arithmetic (exact contraction, spectrogram recomputed in the backward)."""
+        fb, plan = self.mel_fb, self._plan_for(x.device)
+        n = 2 * (fb.shape[0] - 1)
+        if self.lambd_sync:
+            lam_host = self._lambd_host()
+            if fb.shape[0] != capi.n_fft(lam_host) // 2 + 1:
+                raise RuntimeError(f"mel_fb was built for n_fft={n} but lambd={lam_host} now gives n_fft={capi.n_fft(lam_host)}; "
+                                   "a learnable filterbank is tied to one n_fft")
+        xf = _as_f32_contiguous(x, lengths)
+        self._sync_filterbank(plan, n, x)
+        bf16x3 = self.mfma == "bf16x3" and not self.lambd_sync
+        return _DmelFbDevFunction.apply(xf, self.lambd, plan, n, self.log, self.eps, fb, self.out_dtype, False,
+                                        capi.DMEL_FLAG_MFMA_BF16X3 if bf16x3 else 0, self.save_spec and not self.lambd_sync, lengths)
+
     def forward(self, x, lengths=None):
         no_x_grad = None if lengths is None or self.lengths_waveform_grad else "per-clip lengths have no waveform gradient: pass x.detach()"
+        if lengths is not None and self.mel_fb is not None and self.lengths_learnable_fb:
+            no_x_grad = "learnable_fb with per-clip lengths has no waveform gradient: pass x.detach()"
         lam = self.lambd                # (read once: a parameter is found through nn.Module.__getattr__, a quarter of a microsecond)
         lengths = _check_input("MelSpectrogramLayer", x, lam, lengths, n_points=self.n_points, check_lengths=self._check_lengths,
                                slot_config_ok=self._slot_config_ok, refuse_x_grad=no_x_grad)
@@ -734,7 +790,8 @@ class MelSpectrogramLayer(_PlanCachingModule):
     def extra_repr(self):
         return (f"n_mels={self.n_mels}, n_points={self.n_points}, sample_rate={self.sample_rate}, "
                 f"hop_length={self.hop_length}, f_min={self.f_min}, f_max={self.f_max}, "
-                f"normalize_window={self.normalize_window}, log={self.log}")
+                f"normalize_window={self.normalize_window}, log={self.log}"
+                + (", lengths_learnable_fb=True" if self.lengths_learnable_fb else ""))
 
 
 class _MultiFunction(torch.autograd.Function):

@@ -225,6 +225,19 @@ dmel_status dmel_forward_lengths(dmel_plan* plan, const float* x, const int32_t*
                                  double eps, void* out, float* tangent, void* scratch, void* stream);
 dmel_status dmel_forward_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
                                      uint32_t flags, double eps, void* out, float* tangent, void* scratch, void* stream);
+/* Per-clip lengths through a TRAINED filterbank (dmel_plan_set_filterbank_dev; the reference's AudioMNIST loader pads its clips,
+ * datasets.py:175, and a bank trained on them contracts at models.py:53): dmel_forward_dev_fixed / dmel_forward_dev_fixed_spec over clips
+ * x[b, :lengths[b]].  Clip b loses its own mean (models.py:38 over lengths[b] samples), its frames t >= lengths[b] / hop_length + 1 are pad
+ * frames (0, or the kernel's log(0 + eps); tangent 0; models.py:73), x[b, lengths[b]:] is never read, and a length outside 1 ... n_points makes
+ * the clip's rows, its tangent and -- with `spec` -- its whole (n_fft/2+1, n_time) spectrogram NaN.  One launch for `n_fft`, a power of two
+ * in 32 ... 16384; lambd is read and checked on the device as dmel_forward_dev_fixed does (no host read of lambd or lengths: capturable).
+ * spec: NULL, or (batch, n_fft/2+1, n_time) fp32 for dmel_backward_fb_saved_lengths (then tangent != NULL); its columns of pad frames
+ * are not meaningful.  Flags: DMEL_FLAG_LOG, DMEL_FLAG_OUT_BF16, DMEL_FLAG_MFMA_BF16X3 (the dense contraction on the bf16 matrix pipe,
+ * n_fft 64 ... 4096).  With every length at n_points the results have the bits of dmel_forward_dev_fixed(_spec).  NULL handles and
+ * pointers, a misaligned out / tangent / spec / scratch: DMEL_ERR_INVALID_ARGUMENT before any device call. */
+dmel_status dmel_forward_dev_fixed_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                           int32_t n_fft, uint32_t flags, double eps, void* out, float* tangent, float* spec, void* scratch,
+                                           void* stream);
 
 /* Every forward that EXECUTES on a plan (an eager dmel_forward_dev, or one replay of a captured one) draws the next
  * EXECUTION NUMBER from a device counter and reports (number, lambd as it read it) into a pinned ring of 64 entries. */
@@ -322,6 +335,25 @@ dmel_status dmel_backward_fb_saved(dmel_plan* plan, const float* spec, int32_t b
 dmel_status dmel_backward_fb_saved_dl(dmel_plan* plan, const float* spec, int32_t batch, int32_t n_fft, uint32_t flags,
                                       const float* grad_out, const float* out, const float* tangent, float* grad_fb, float* dlambd,
                                       void* scratch, void* stream);
+/* The filterbank gradient of a forward with per-clip lengths (dmel_forward_dev_fixed_lengths; models.py:53 for a batch the loader
+ * padded, datasets.py:175):
+ *   grad_fb[f][m] = sum_b sum_{t < Tc_b} spec_b[f][t] * gm_b[m][t],   Tc_b = lengths[b] / hop_length + 1,
+ * spec_b the spectrogram of x[b, :lengths[b]] (DC removed over the clip, models.py:38), gm as dmel_backward_fb (models.py:73 with
+ * DMEL_FLAG_LOG).  grad_out, out and the spectrogram are never loaded at t >= Tc_b: NaN or inf there reaches nothing.  A length
+ * outside 1 ... n_points makes every element of grad_fb NaN (that clip is summed over all n_time frames of a NaN spectrogram).  The
+ * batch is cut into the slices of dmel_backward_fb whatever the lengths, and K-blocks without a frame are skipped inside them, so with
+ * every length at n_points the result has the bits of dmel_backward_fb_dev / dmel_backward_fb_saved(_dl).  lengths: device, `batch`
+ * int32 values read by the kernels when they run.  n_fft: a power of two in 32 ... 16384.  flags: DMEL_FLAG_LOG, DMEL_FLAG_MFMA_BF16X3.
+ * dmel_backward_fb_dev_lengths recomputes the spectrogram from x (lambd read on the device and checked against n_fft);
+ * dmel_backward_fb_saved_lengths contracts the one the forward saved and, when `tangent` and `dlambd` are given (both or neither),
+ * carries d lambd = sum(grad_out * tangent) in the same launch as dmel_backward_fb_saved_dl does (over all frames: the tangent of a pad
+ * frame is zero).  NULL handles and pointers, a misaligned grad_fb / scratch: DMEL_ERR_INVALID_ARGUMENT before any device call. */
+dmel_status dmel_backward_fb_dev_lengths(dmel_plan* plan, const float* x, const int32_t* lengths, int32_t batch, const float* lambd_dev,
+                                         int32_t n_fft, uint32_t flags, const float* grad_out, const float* out, float* grad_fb,
+                                         void* stream);
+dmel_status dmel_backward_fb_saved_lengths(dmel_plan* plan, const float* spec, const int32_t* lengths, int32_t batch, int32_t n_fft,
+                                           uint32_t flags, const float* grad_out, const float* out, const float* tangent, float* grad_fb,
+                                           float* dlambd, void* scratch, void* stream);
 
 /*
  * Backward to the waveform: what torch autograd returns for x.requires_grad through models.py:38 (DC removal),
