@@ -1387,6 +1387,20 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                 constexpr int srow0 = 0;
 #endif
                 const int total = 2 * srows * QPR;
+                // DMEL_WL_WT: the whole 16-byte pieces leave as write-through buffer stores (sc1) -- 1 = those of out, 2 = those of the
+                // tangent, 3 = both, 0 = plain stores.  A plain store stays dirty in the XCD's L2 until the end-of-kernel release writes
+                // 16 KB per workgroup back while nothing computes; a write-through one leaves while other workgroups still contract.
+                // One descriptor per tensor and clip (in the band build: the shared image), M T 4 bytes; a clip image beyond what its
+                // 32-bit range holds keeps the plain stores.  The shape guards below stay: a buffer store out of range is dropped silently.
+#ifndef DMEL_WL_WT
+#define DMEL_WL_WT 3
+#endif
+#if DMEL_WL_WT
+                const unsigned long long img_bytes = (unsigned long long)p.M * (unsigned long long)p.T * 4ull;
+                const bool wt_fits = img_bytes <= 0xffffffffull;
+                const __amdgpu_buffer_rsrc_t r_out = make_rsrc(out_clip, wt_fits ? (unsigned)img_bytes : 0u);
+                const __amdgpu_buffer_rsrc_t r_tan = make_rsrc(tan_clip, wt_fits ? (unsigned)img_bytes : 0u);
+#endif
                 for (int idx = tid; idx < total; idx += THREADS) {
                     const int rw = idx / QPR, c = idx % QPR;
                     const int pl = rw >= srows ? 1 : 0, mm = srow0 + rw - pl * srows;
@@ -1402,8 +1416,16 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                     }
                     float* dst = (pl ? tan_clip : out_clip) + (unsigned)mm * (unsigned)p.T + t0 + 4 * c;
                     const int t = t0 + 4 * c;
-                    if (t + 3 < p.T) *reinterpret_cast<float4*>(dst) = v;
-                    else { if (t < p.T) dst[0] = v.x; if (t + 1 < p.T) dst[1] = v.y; if (t + 2 < p.T) dst[2] = v.z; }
+                    if (t + 3 < p.T) {
+#if DMEL_WL_WT
+                        // (a branch per tensor, not a descriptor chosen per lane: that would be a loop over the lanes' descriptors)
+                        const unsigned eo = (unsigned)mm * (unsigned)p.T + t0 + 4 * c;   // element offset inside the clip's image
+                        if ((DMEL_WL_WT & 1) && wt_fits && pl == 0) buf_store_wt_f4(r_out, eo * 4u, v);
+                        else if ((DMEL_WL_WT & 2) && wt_fits && pl != 0) buf_store_wt_f4(r_tan, eo * 4u, v);
+                        else
+#endif
+                        *reinterpret_cast<float4*>(dst) = v;
+                    } else { if (t < p.T) dst[0] = v.x; if (t + 1 < p.T) dst[1] = v.y; if (t + 2 < p.T) dst[2] = v.z; }
                 }
             }
             STAMP(16 * ti + 11);

@@ -195,6 +195,13 @@ __device__ __forceinline__ float buf_f32(__amdgpu_buffer_rsrc_t r, int byte_off)
 {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
 }
+// 16-byte write-through store (aux 16 = sc1): the bytes leave the XCD's L2 when they are stored, not at the kernel's end-of-kernel release.
+// An offset outside the descriptor's range drops the store without a trace: the caller checks its shape itself.
+__device__ __forceinline__ void buf_store_wt_f4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, float4 v)
+{
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, (int)byte_off, 0, 16);
+}
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }   // v_med3_i32
 // (the 64-bit form __builtin_amdgcn_raw_buffer_load_b64 is mis-lowered to a single dword load by hipcc 7.2:
 // twiddle tables are therefore read with ordinary float2 loads)
