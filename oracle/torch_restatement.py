@@ -13,6 +13,10 @@ tangent_fp64 / tangent_fp32 evaluate the forward-mode tangent d out / d lambd el
 derivative from torch.autograd.functional.jacobian, then a second stft with it), together with the cancellation-free magnitude of
 every tangent element: what tests/tangent_cases.py measures the oracle's and the kernels' tangents against.
 
+fbgrad_fp64 / fbgrad_fp32 evaluate the filterbank gradient grad_fb[f, m] = sum_{b,t} spec[b, f, t] gm[b, m, t] together with its
+cancellation-free magnitude sum spec |gm| (spec >= 0: the sum cancels only through the sign of the cotangent): what tests/fbgrad_cases.py
+measures the oracle's and the kernels' filterbank gradients against.
+
 Reference lines followed: time_frequency.py:21-30 (window), :39,:60-65 (n_fft), :48 (stft),
 :53 (power); models.py:38 (DC removal, abs), :42-53 (filterbank, contraction), :73 (log).
 """
@@ -132,3 +136,72 @@ def tangent_fp32(x, lambd, hop, n_mels, sample_rate, f_min=0.0, f_max=None, norm
     """tangent_fp64's construction in the reference's own arithmetic: fp32 window, fp32 stft, fp32 contraction (returned as fp64 arrays)"""
     return _tangent(torch.float32, x, lambd, hop, n_mels, sample_rate, f_min, f_max, normalize_window, log, eps, optimized, mean, fb,
                     spectrogram)
+
+
+def fbgrad_operands(dtype, x, lambd, hop, n_mels, sample_rate, grad_out, out=None, f_min=0.0, f_max=None, normalize_window=False,
+                    optimized=True, lengths=None, eps=None, mean=None, fb=None):
+    """the two operands of the filterbank gradient in ``dtype``, as fbgrad_fp64 describes them: spec (B, F, T), zero in the pad frames of a
+    clip shorter than the batch, and gm (B, M, T), zero there too"""
+    import numpy as np
+    x32 = np.ascontiguousarray(x, dtype=np.float32)
+    B, L = x32.shape
+    T = L // hop + 1
+    lam32 = np.float32(lambd)
+    lam = torch.tensor(float(lam32), dtype=dtype)
+    n_win = n_fft_of(torch.tensor(float(lam32))) if optimized else L
+    n = n_win if optimized else 2 * L
+    F = n // 2 + 1
+    w = _window_of(lam, n_win, normalize_window)
+    lens = [L] * B if lengths is None else [int(v) for v in np.asarray(lengths).reshape(B)]
+    if mean is not None:
+        mean = np.asarray(mean, dtype=np.float32).reshape(B)
+    p = torch.zeros((B, F, T), dtype=dtype)                                   # frames at or past lengths[b] // hop + 1 stay out of both sums
+    for b, Lb in enumerate(lens):
+        assert 1 <= Lb <= L, (b, Lb)
+        xb = x32[b, :Lb]
+        mb = np.float32(xb.astype(np.float64).mean()) if mean is None else mean[b]      # the correctly rounded fp32 mean (models.py:38)
+        xc = torch.tensor(xb).to(dtype) - torch.tensor(float(mb), dtype=dtype)
+        S = torch.stft(xc[None, :], n_fft=n, hop_length=hop, win_length=n_win, window=w, return_complex=True, pad_mode="constant")[0]
+        assert S.shape == (F, Lb // hop + 1), (S.shape, F, Lb, hop)
+        p[b, :, :Lb // hop + 1] = S.real * S.real + S.imag * S.imag
+    live = torch.tensor([[t < Lb // hop + 1 for t in range(T)] for Lb in lens])[:, None, :]          # (B, 1, T): pad frames are never read
+    zero = torch.zeros((), dtype=dtype)
+    g = torch.where(live, torch.tensor(np.ascontiguousarray(np.asarray(grad_out, dtype=np.float32).reshape(B, n_mels, T))).to(dtype), zero)
+    if out is not None:
+        g = g * torch.exp(-torch.where(live, torch.tensor(np.ascontiguousarray(np.asarray(out, dtype=np.float32).reshape(B, n_mels, T))).to(dtype), zero))
+    elif eps is not None:
+        if fb is None:
+            from oracle import dmel_oracle as O
+            fb = O.mel_fbanks(F, f_min, float(sample_rate // 2) if f_max is None else f_max, n_mels, sample_rate)
+        fbt = torch.tensor(np.asarray(fb, dtype=np.float32)).to(dtype)          # (F, M)
+        g = g / (torch.einsum("fm,bft->bmt", fbt, p) + eps)                      # d log(mel + eps) = d mel / (mel + eps) = d mel exp(-out)
+    return p, g
+
+
+def _fbgrad(dtype, *args):
+    p, g = fbgrad_operands(dtype, *args)
+    gfb = torch.einsum("bft,bmt->fm", p, g)
+    sc = torch.einsum("bft,bmt->fm", p, g.abs())
+    return gfb.to(torch.float64).numpy(), sc.to(torch.float64).numpy()
+
+
+def fbgrad_fp64(x, lambd, hop, n_mels, sample_rate, grad_out, out=None, f_min=0.0, f_max=None, normalize_window=False, optimized=True,
+                lengths=None, eps=None, mean=None, fb=None):
+    """(grad_fb, scale), each (n_fft/2+1, n_mels) fp64: the adjoint of models.py:53 and its cancellation-free magnitude.  Everything in
+    torch.float64 from the fp32 clip ``x`` (B, L), ``lambd`` rounded to fp32 and the fp32 cotangent ``grad_out`` (B, 1, n_mels, L//hop+1):
+      spec = |stft(x - mean, window(lambd))|^2 as tangent_fp64 forms it (``optimized``: n_fft points; else the whole-clip window in n_fft = 2L);
+      gm = grad_out for the linear output (``out`` None and ``eps`` None);  grad_out exp(-out) with the saved LOG output ``out`` -- what the
+      kernels are given;  with ``out`` None and ``eps`` set, the log output is computed here: grad_out / (mel + eps), mel through ``fb`` (F, M)
+      or the HTK bank;
+      grad_fb = sum_{b,t} spec gm,  scale = sum_{b,t} spec |gm|.
+    ``lengths``: clip b is x[b, :lengths[b]] with its own mean, and frames at or past lengths[b] // hop + 1 are left out of both sums.
+    |grad_fb| <= scale element by element; scale == 0 exactly where no frame of any clip has power in the bin or the cotangent is zero."""
+    return _fbgrad(torch.float64, x, lambd, hop, n_mels, sample_rate, grad_out, out, f_min, f_max, normalize_window, optimized, lengths,
+                   eps, mean, fb)
+
+
+def fbgrad_fp32(x, lambd, hop, n_mels, sample_rate, grad_out, out=None, f_min=0.0, f_max=None, normalize_window=False, optimized=True,
+                lengths=None, eps=None, mean=None, fb=None):
+    """fbgrad_fp64's construction in the reference's own arithmetic: fp32 window, stft, exp and contraction (returned as fp64 arrays)"""
+    return _fbgrad(torch.float32, x, lambd, hop, n_mels, sample_rate, grad_out, out, f_min, f_max, normalize_window, optimized, lengths,
+                   eps, mean, fb)

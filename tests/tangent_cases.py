@@ -133,16 +133,20 @@ def out_shape(case):
     return (case["B"], 1, rows, case["L"] // case["hop"] + 1)
 
 
+def synth_clips(B, L, seed, sr, tone=0.05, noise=0.1, gated=False):
+    """(B, L) fp32: noise + a 440 Hz tone (``gated``: in the middle half of the clip only), the clip mean removed (module docstring)"""
+    x = synth.normal((B, L), seed=seed, scale=noise, dtype=np.float64)
+    ph = 6.283 * synth.uniform01(B, seed=seed + 7)
+    gate = ((np.arange(L) >= L // 4) & (np.arange(L) < 3 * L // 4)) if gated else np.ones(L)
+    x += tone * gate[None, :] * np.sin(2.0 * np.pi * 440.0 * np.arange(L)[None, :] / float(max(sr, 8000)) + ph[:, None])
+    x -= x.mean(axis=1, keepdims=True)                       # zero offset (module docstring)
+    return x.astype(np.float32)
+
+
 @functools.lru_cache(maxsize=None)
 def _input(name):
     c = BY_NAME[name]
-    B, L = c["B"], c["L"]
-    x = synth.normal((B, L), seed=c["seed"], scale=c["noise"], dtype=np.float64)
-    ph = 6.283 * synth.uniform01(B, seed=c["seed"] + 7)
-    gate = ((np.arange(L) >= L // 4) & (np.arange(L) < 3 * L // 4)) if c["gated"] else np.ones(L)
-    x += c["tone"] * gate[None, :] * np.sin(2.0 * np.pi * 440.0 * np.arange(L)[None, :] / float(max(c["sr"], 8000)) + ph[:, None])
-    x -= x.mean(axis=1, keepdims=True)                       # zero offset (module docstring)
-    x = x.astype(np.float32)
+    x = synth_clips(c["B"], c["L"], c["seed"], c["sr"], c["tone"], c["noise"], c["gated"])
     x.setflags(write=False)
     return x
 

@@ -149,6 +149,11 @@ def test_every_clip_matches_the_oracle_on_that_clip_alone(lam, log):
     e_fb = _gfb_err(gfb.cpu().numpy(), ref_fb)
     print(f"mel_fb.grad err {e_fb:.3e}; lambd.grad {float(d):.6e} against {ref_d:.6e} (sum |.| {ref_abs:.3e})")
     assert e_fb <= TOL
+    # ... and element by element over each clip's own frames (tests/fbgrad_cases.py; the inputs: tests/test_fbgrad_restatement_cpu.py)
+    from test_hip_parity import _assert_gfb_elementwise
+    _assert_gfb_elementwise(f"fbgrad_lengths/{int(lam)}/{'log' if log else 'lin'}", gfb.cpu().numpy(),
+                            dict(lambd=lam, hop=HOP2, n_mels=M2, sr=SR, f_min=0.0, f_max=None, normalize_window=False), x_np, g_np,
+                            y_np if log else None, lengths=LENS2)
     assert abs(float(d) - ref_d) <= 1e-4 * ref_abs
 
 

@@ -676,6 +676,18 @@ def _gfb_err(got, exp):
     return float(np.abs(got.astype(np.float64) - exp).max() / (np.abs(exp).max() + 1e-30))
 
 
+def _assert_gfb_elementwise(tag, got, case, x_np, g_np, out, optimized=True, lengths=None):
+    """beside _gfb_err (one maximum over the largest element of the tensor: blind to up to 98 % of it, tests/fbgrad_cases.py): the gradient
+    against oracle/torch_restatement.py: fbgrad_fp64 given the saved log output `out` (None: linear), |got - ref| over the cancellation-free
+    magnitude of the element, TOL on every element.  tests/test_fbgrad_restatement_cpu.py holds the references to TOL / 4 on the inputs of
+    every site that calls this."""
+    from fbgrad_cases import assert_fbgrad
+    from oracle import torch_restatement as R
+    ref, sc = R.fbgrad_fp64(x_np, case["lambd"], case["hop"], case["n_mels"], case["sr"], g_np, out, case["f_min"], case["f_max"],
+                            case["normalize_window"], optimized=optimized, lengths=lengths)
+    return assert_fbgrad(tag, got, ref, sc, shape=ref.shape)
+
+
 @pytest.mark.parametrize("name", ["g1_c1", "g2_c2", "g5_n128", "g6_n256_ragged"])
 def test_fbgrad_matches_reference_golden(name):
     """dmel_backward_fb against torch autograd through the reference with mel_fb made a leaf (g8_fbgrad_*.npz)
@@ -702,6 +714,7 @@ def test_fbgrad_matches_reference_golden(name):
         assert _gfb_err(got, gold[key].astype(np.float64)) <= TOL
         ref = O.backward_fb(x_np, case["lambd"], case["hop"], g_np, y.cpu().numpy() if log else None, case["normalize_window"])
         assert _gfb_err(got, ref) <= TOL
+        _assert_gfb_elementwise(f"fbgrad_golden/{name}/{'log' if log else 'lin'}", got, case, x_np, g_np, y.cpu().numpy() if log else None)
         # deterministic: same bits on a second call
         gfb2 = torch.empty_like(gfb)
         plan.backward_fb(x.data_ptr(), case["B"], case["lambd"], g.data_ptr(), y.data_ptr() if log else None, gfb2.data_ptr(), log, st)
@@ -1159,6 +1172,7 @@ def test_filterbank_gradient_with_short_and_ragged_rows(hop, T):
         plan.backward_fb(x.data_ptr(), case["B"], case["lambd"], g.data_ptr(), y.data_ptr(), gfb.data_ptr(), log, st)
         torch.cuda.synchronize()
         assert _gfb_err(gfb.cpu().numpy(), O.backward_fb(x_np, case["lambd"], hop, g_np, y_np if log else None)) <= TOL
+        _assert_gfb_elementwise(f"fbgrad_ragged/T{T}/{'log' if log else 'lin'}", gfb.cpu().numpy(), case, x_np, g_np, y_np if log else None)
 
 
 def test_optional_gradients_at_tiny_n_fft():
@@ -1208,6 +1222,7 @@ def test_optional_gradients_on_edge_configurations(name):
                      torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert _gfb_err(gfb.cpu().numpy(), O.backward_fb(x_np, case["lambd"], case["hop"], g_np, y_np, case["normalize_window"])) <= TOL
+    _assert_gfb_elementwise(f"fbgrad_edge/{name}/log", gfb.cpu().numpy(), case, x_np, g_np, y_np)
 
 
 ODD_SHAPES = [
@@ -1386,6 +1401,8 @@ def test_learnable_filterbank_full_window_matches_reference_golden(name):
         (y * g).sum().backward()
         got = layer.mel_fb.grad.cpu().numpy()
         assert np.isfinite(got).all() and _gfb_err(got, gold[key].astype(np.float64)) <= TOL
+        _assert_gfb_elementwise(f"fbgrad_full_window/{name}/{'log' if log else 'lin'}", got, case, x.cpu().numpy(), g.cpu().numpy(),
+                                y.detach().cpu().numpy() if log else None, optimized=False)
         assert layer.lambd.grad is not None and np.isfinite(float(layer.lambd.grad))
         # the forward with the parameter as its filterbank equals the forward with the built-in table
         plain = _layer(case, log=log)
