@@ -11,8 +11,8 @@ from __future__ import annotations
 
 import importlib
 
-__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "capi", "synth", "dist",
-           "nets", "panns", "graph", "optim"]
+__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "PCEN", "capi", "synth", "dist",
+           "nets", "panns", "graph", "optim", "pcen"]
 
 _LAZY = {
     "MelSpectrogramLayer": ("layer", "MelSpectrogramLayer"),
@@ -24,6 +24,7 @@ _LAZY = {
     "SlotInput": ("layer", "SlotInput"),
     "GraphedStep": ("graph", "GraphedStep"),
     "LambdAdam": ("optim", "LambdAdam"),
+    "PCEN": ("pcen", "PCEN"),
 }
 
 
@@ -31,6 +32,6 @@ def __getattr__(name):
     if name in _LAZY:
         mod, attr = _LAZY[name]
         return getattr(importlib.import_module(f"dmel_amd.{mod}"), attr)
-    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim"):
+    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim", "pcen"):
         return importlib.import_module(f"dmel_amd.{name}")
     raise AttributeError(name)

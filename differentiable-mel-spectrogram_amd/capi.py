@@ -139,6 +139,9 @@ _SIGNATURES = {
     "dmel_plan_attach_mailbox": (status, [vp, vp]),
     "dmel_adam_step": (status, [vp, vp, vp, vp, vp, vp, i64, f64, f64, f64, f64, f64, i32, vp]),
     "dmel_plan_attach_adam": (status, [vp, vp, vp, vp, vp, f64, f64, f64, f64, f64, i32]),
+    "dmel_pcen_scratch_bytes": (C.c_size_t, [i64]),
+    "dmel_pcen_forward": (status, [vp, i64, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp]),
+    "dmel_pcen_backward": (status, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp]),
     "dmel_scratch_bytes_multi": (C.c_size_t, [vp, i32, i32]),
     "dmel_forward_multi": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_multi_dev": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
@@ -250,6 +253,25 @@ def adam_step(param_ptr: int, grad_ptr: int, exp_avg_ptr: int, exp_avg_sq_ptr: i
     _check(load().dmel_adam_step(param_ptr, grad_ptr, exp_avg_ptr, exp_avg_sq_ptr, step_ptr, ticket_ptr or None, int(n), C.c_double(float(lr)),
                                  C.c_double(float(beta1)), C.c_double(float(beta2)), C.c_double(float(eps)), C.c_double(float(weight_decay)),
                                  1 if maximize else 0, stream))
+
+
+def pcen_scratch_bytes(rows: int) -> int:
+    """dmel_pcen_scratch_bytes: what pcen_backward needs for the parameter gradients (a pure function, no device)"""
+    return int(load().dmel_pcen_scratch_bytes(int(rows)))
+
+
+def pcen_forward(e_ptr: int, rows: int, n_mels: int, n_time: int, alpha_ptr: int, delta_ptr: int, r_ptr: int, s_ptr: int, eps: float,
+                 y_ptr: int, m_ptr: int | None, stream: int) -> None:
+    """dmel_pcen_forward: y (and the smoother M, when ``m_ptr`` is given) of ``rows`` x ``n_time`` fp32 linear mel power, band = row % n_mels"""
+    _check(load().dmel_pcen_forward(e_ptr, int(rows), int(n_mels), int(n_time), alpha_ptr, delta_ptr, r_ptr, s_ptr, C.c_float(float(eps)),
+                                    y_ptr, m_ptr or None, stream))
+
+
+def pcen_backward(g_ptr: int, e_ptr: int, m_ptr: int, rows: int, n_mels: int, n_time: int, alpha_ptr: int, delta_ptr: int, r_ptr: int, s_ptr: int,
+                  eps: float, de_ptr: int | None, dparams_ptr: int | None, scratch_ptr: int | None, stream: int) -> None:
+    """dmel_pcen_backward: dE and / or the (4, n_mels) gradients of alpha, delta, r, s (``scratch_ptr``: pcen_scratch_bytes(rows) bytes)"""
+    _check(load().dmel_pcen_backward(g_ptr, e_ptr, m_ptr, int(rows), int(n_mels), int(n_time), alpha_ptr, delta_ptr, r_ptr, s_ptr,
+                                     C.c_float(float(eps)), de_ptr or None, dparams_ptr or None, scratch_ptr or None, stream))
 
 
 def device_count() -> int:

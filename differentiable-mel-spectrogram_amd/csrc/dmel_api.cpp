@@ -2952,6 +2952,73 @@ dmel_status dmel_adam_step(float* param, const float* grad, float* exp_avg, floa
     return DMEL_OK;
 }
 
+namespace {
+// what dmel_pcen_forward and dmel_pcen_backward check alike; DMEL_OK with *noop set: nothing to launch
+dmel_status pcen_check(const char* who, int64_t rows, int32_t n_mels, int32_t T, const float* alpha, const float* delta, const float* r,
+                       const float* s, float eps, bool* noop)
+{
+    const std::string w(who);
+    *noop = false;
+    if (!alpha || !delta || !r || !s) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": NULL parameter pointer");
+    if (n_mels < 1 || rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_mels / T out of range");
+    if (rows % n_mels != 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows must be a multiple of n_mels (band = row % n_mels)");
+    if (!std::isfinite(eps) || !(eps > 0.f)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": eps must be finite and > 0");
+    if (rows == 0 || T == 0) { *noop = true; return DMEL_OK; }
+    if (dmel::pcen_blocks(rows, T) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
+    return DMEL_OK;
+}
+
+dmel_status pcen_device(const char* who)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return fail(DMEL_ERR_NO_DEVICE, std::string(who) + ": no HIP device"); }
+    return DMEL_OK;
+}
+}  // namespace
+
+size_t dmel_pcen_scratch_bytes(int64_t rows)
+{
+    return rows > 0 ? (size_t)rows * 4 * sizeof(float) : 0;
+}
+
+dmel_status dmel_pcen_forward(const float* E, int64_t rows, int32_t n_mels, int32_t T, const float* alpha, const float* delta,
+                              const float* r, const float* s, float eps, float* y, float* M_or_null, void* stream)
+{
+    bool noop = false;
+    const dmel_status st = pcen_check("dmel_pcen_forward", rows, n_mels, T, alpha, delta, r, s, eps, &noop);
+    if (st != DMEL_OK) return st;
+    if (!E || !y) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_pcen_forward: NULL pointer (E / y)");
+    if (noop) return DMEL_OK;
+    const dmel_status sd = pcen_device("dmel_pcen_forward");
+    if (sd != DMEL_OK) return sd;
+    dmel::PcenParams p{};
+    p.E = E; p.y = y; p.M = M_or_null; p.alpha = alpha; p.delta = delta; p.r = r; p.s = s;
+    p.rows = rows; p.n_mels = n_mels; p.T = T; p.eps = eps;
+    DMEL_HIP(dmel::launch_pcen_fwd(p, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
+dmel_status dmel_pcen_backward(const float* g, const float* E, const float* M, int64_t rows, int32_t n_mels, int32_t T,
+                               const float* alpha, const float* delta, const float* r, const float* s, float eps,
+                               float* dE_or_null, float* dparams_or_null, float* scratch, void* stream)
+{
+    bool noop = false;
+    const dmel_status st = pcen_check("dmel_pcen_backward", rows, n_mels, T, alpha, delta, r, s, eps, &noop);
+    if (st != DMEL_OK) return st;
+    if (!g || !E || !M) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_pcen_backward: NULL pointer (g / E / M)");
+    if (dparams_or_null && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15)))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_pcen_backward: the parameter gradients need 16-byte aligned scratch of dmel_pcen_scratch_bytes(rows)");
+    if (noop || (!dE_or_null && !dparams_or_null)) return DMEL_OK;      // nothing is written (not dparams either)
+    const dmel_status sd = pcen_device("dmel_pcen_backward");
+    if (sd != DMEL_OK) return sd;
+    dmel::PcenParams p{};
+    p.g = g; p.E = E; p.Min = M; p.dE = dE_or_null; p.partials = dparams_or_null ? scratch : nullptr;
+    p.alpha = alpha; p.delta = delta; p.r = r; p.s = s;
+    p.rows = rows; p.n_mels = n_mels; p.T = T; p.eps = eps;
+    DMEL_HIP(dmel::launch_pcen_bwd(p, dparams_or_null, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
 dmel_status dmel_plan_set_profiling(dmel_plan* plan, int32_t enable)
 {
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");

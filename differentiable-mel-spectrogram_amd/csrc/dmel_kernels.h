@@ -706,6 +706,23 @@ struct AdamParams {
 int adam_grid(long long n);    // workgroups of one launch (more than one needs the ticket word)
 hipError_t launch_adam(const AdamParams& p, hipStream_t s);
 
+// PCEN behind the mel layers (dmel_pcen_forward / dmel_pcen_backward, csrc/dmel_pcen.hip): rows x T fp32, band = row % n_mels
+struct PcenParams {
+    const float* E;             // (rows, T) linear mel power
+    const float* g;             // backward: cotangent of y
+    const float* Min;           // backward: the smoother the forward wrote
+    float* y; float* M;         // forward: outputs (M may be nullptr)
+    float* dE;                  // backward: nullptr = not asked for
+    float* partials;            // backward: (rows, 4) per-row sums of d alpha, d delta, d r, d s; nullptr = not asked for
+    const float* alpha; const float* delta; const float* r; const float* s;   // (n_mels) each
+    long long rows; int n_mels, T;
+    float eps;
+    int W, logw;                // set by the launchers: lanes per row (next power of two >= T up to 32 frames, else 64)
+};
+long long pcen_blocks(long long rows, int T);      // workgroups of one launch
+hipError_t launch_pcen_fwd(PcenParams p, hipStream_t s);
+hipError_t launch_pcen_bwd(PcenParams p, float* dparams, hipStream_t s);      // dparams: (4, n_mels) or nullptr
+
 // Peer-to-peer all-reduce of the one scalar this path exchanges (d lambd), folded into the tail of the dot kernel: the workgroup
 // that draws the last ticket stores (step, local sum) as ONE 8-byte granule into slot `rank` of every rank's inbox -- peer memory
 // mapped over xGMI, system-scope stores -- then polls its own inbox until every rank's granule of this step has arrived and adds

@@ -27,8 +27,15 @@ class _MelFrontNet(nn.Module):
         self.size = (n_mels, n_points // hop_length + 1)
         self.energy_normalize = energy_normalize
 
+    def __setattr__(self, name, value):
+        if name == "compression" and value is not None and getattr(self, "energy_normalize", False):
+            raise ValueError("compression (dmel_amd.PCEN) takes linear mel power: build the net with energy_normalize=False")
+        super().__setattr__(name, value)
+
     def _features(self, x):
-        return self.spectrogram_layer(x)          # already log-compressed when energy_normalize
+        s = self.spectrogram_layer(x)             # already log-compressed when energy_normalize
+        compression = getattr(self, "compression", None)      # opt-in: net.compression = dmel_amd.PCEN(n_mels)
+        return s if compression is None else compression(s)
 
 
 class MelLinearNet(_MelFrontNet):

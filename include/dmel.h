@@ -497,6 +497,26 @@ dmel_status dmel_adam_step(float* param, const float* grad, float* exp_avg, floa
 dmel_status dmel_plan_attach_adam(dmel_plan* plan, float* param, float* exp_avg, float* exp_avg_sq, float* step,
                                   double lr, double beta1, double beta2, double eps, double weight_decay, int32_t maximize);
 
+/* ---- PCEN: per-channel energy normalisation behind the mel layers (dmel_amd.PCEN; plan-free, as dmel_adam_step) ---------------------
+ * The other standard compression of trainable audio front ends (Wang et al. 2017), next to the forward's fused log(s + eps).  Every
+ * row is one (clip[, channel], band) pair of T frames of LINEAR mel power E >= 0 (a forward without DMEL_FLAG_LOG); rows % n_mels == 0
+ * and the row's band is row % n_mels -- what a contiguous (..., n_mels, T) tensor gives.  alpha, delta, r, s: n_mels device floats each.
+ *   M[0] = E[0];  M[t] = (1 - s) M[t-1] + s E[t]  (t >= 1);   D = eps + M;  a = E D^(-alpha);  u = a + delta;  y = u^r - delta^r
+ * A frame with E == 0 gives y == +0.0 exactly (silent rows and the pad frames of the *_lengths forwards stay zero).  The kernels do not
+ * clamp the parameters: keep 0 <= alpha <= 1, delta > 0, 0 < r <= 1, 0 < s <= 1 (dmel_amd.PCEN.project_) and eps > 0.
+ * dmel_pcen_forward writes y and, when M_or_null is given, the smoother M that dmel_pcen_backward reads (rows * T floats each).
+ * dmel_pcen_backward takes g = dL/dy and writes dE = dL/dE (rows * T floats) and / or dparams = (4, n_mels): the gradients of alpha,
+ * delta, r, s summed over the frames and rows of each band; either may be NULL and is then neither computed nor written.  dparams needs
+ * `scratch`: dmel_pcen_scratch_bytes(rows) bytes (rows * 4 floats, 16-byte aligned) owned by the caller for the duration of the call's
+ * work on `stream`.  Two launches at most, no atomics: the same inputs give the same bits.  No host read, capturable.  rows == 0 or
+ * T == 0: DMEL_OK, nothing is launched or written. */
+size_t dmel_pcen_scratch_bytes(int64_t rows);
+dmel_status dmel_pcen_forward(const float* E, int64_t rows, int32_t n_mels, int32_t T, const float* alpha, const float* delta,
+                              const float* r, const float* s, float eps, float* y, float* M_or_null, void* stream);
+dmel_status dmel_pcen_backward(const float* g, const float* E, const float* M, int64_t rows, int32_t n_mels, int32_t T,
+                               const float* alpha, const float* delta, const float* r, const float* s, float eps,
+                               float* dE_or_null, float* dparams_or_null, float* scratch, void* stream);
+
 /* ---- the multi-window layer: K trainable window widths as K output channels (dmel_amd.MultiWindowMelSpectrogram) ------------------
  * Channel k of (batch, K, n_mels, n_time) is what dmel_forward* computes for lambd[k], bit for bit; 1 <= K <= 8, every channel's n_fft in
  * 32 ... 16384 (the fused kernel).  One launch per DISTINCT n_fft covers all the channels that need it.  out and tangent are (batch, K, M, T);
