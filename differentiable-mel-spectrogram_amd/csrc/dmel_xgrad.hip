@@ -19,6 +19,7 @@
 // Kernels 1 and 2 and the combine pass are written once, for these clips and for clips of per-clip lengths (dmel_xgrad_len.hip):
 // dmel_xgrad_body.h.  This file holds their fixed-length entry points, the wave-FFT kernels and the multi-window layer's combine pass.
 #include "dmel_xgrad_body.h"
+#include "dmel_xgrad_multi.h"
 
 namespace dmel {
 
@@ -63,85 +64,8 @@ __device__ __forceinline__ void xstamp(int wgid, int wave, int lane, int idx)
 #include "dmel_xgrad_wave_body.inc"
 #undef DMEL_XG_MULTI
 
-// grid (chunks, B): the multi-window layer's gradient w.r.t. the waveform, one launch per backward.  Every thread keeps 16 samples
-// (i = lo + tid + 256 r: consecutive lanes read consecutive words) and adds the channels' terms in ascending channel order, starting from
-// 0.f -- the sum autograd forms over K scalar layers.  A term is what the scalar path of that channel writes: segments in increasing
-// tile order minus the sequential fp64 tile-sum mean (dmel_xgrad_combine_kernel), or frame rows in increasing frame order minus the
-// mean of the 256-wide fp64 tree (dmel_xgrad_gather_kernel).  One write of grad_x; no atomics.
-__global__ void __launch_bounds__(256) dmel_xgrad_combine_multi_kernel(XgradCombineMultiParams p)
-{
-    __shared__ double red[256];
-    constexpr int PER = kXgChunk / 256;
-    const int tid = threadIdx.x, b = blockIdx.y, chunk = blockIdx.x;
-    const int lo = chunk * kXgChunk, hi = min(lo + kXgChunk, p.L);
-    float acc[PER];
-    static_for<0, PER>([&](auto rr) { acc[decltype(rr)::value] = 0.f; });
-    for (int c = 0; c < p.channels; ++c) {
-        int j = 0;
-        if (p.lam_dev) {                                              // the n_fft lambd[c] asks for: one of the launches issued for it?
-            const int n = lam_n_fft(__builtin_fabsf(p.lam_dev[c]));
-            j = -1;
-            for (int q = 0; q < p.ncand[c]; ++q) if (p.n[c][q] == n) j = q;
-        }
-        if (j < 0) {
-            static_for<0, PER>([&](auto rr) { constexpr int r = decltype(rr)::value; acc[r] = acc[r] + __builtin_nanf(""); });
-            continue;
-        }
-        const int N = p.n[c][j], tiles = p.tiles[c][j], half = N / 2;
-        if (tiles > 0) {
-            const int span = p.span[c][j], ts = p.tile_step[c][j];
-            const float* sg = p.frames[c] + (size_t)b * tiles * (size_t)span;
-            const int u_lo = lo + half, u_hi = hi - 1 + half;
-            const int qa = u_lo < span ? 0 : (u_lo - span) / ts + 1;
-            const int qb = min(tiles - 1, u_hi / ts);
-            double dacc = 0.0;
-            for (int q = 0; q < tiles; ++q) dacc += p.csum[c][(size_t)b * tiles + q];
-            const float mean = (float)(dacc / (double)p.L);
-            static_for<0, PER>([&](auto rr) {
-                constexpr int r = decltype(rr)::value;
-                const int i = lo + tid + 256 * r;
-                if (i < hi) {
-                    const int u = i + half;
-                    float s = 0.f;
-                    for (int q = qa; q <= qb; ++q) {
-                        const int off = u - q * ts;
-                        if (off >= 0 && off < span) s += sg[(size_t)q * span + off];
-                    }
-                    acc[r] = acc[r] + (s - mean);
-                }
-            });
-        } else {
-            const int T = p.T, hop = p.hop;
-            __syncthreads();                                          // (red of the previous channel has been read)
-            double dacc = 0.0;
-            for (int t = tid; t < T; t += 256) dacc += p.csum[c][(size_t)b * T + t];
-            red[tid] = dacc;
-            __syncthreads();
-            for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-            const float mean = (float)(red[0] / (double)p.L);
-            const float* fr = p.frames[c] + (size_t)b * T * N;
-            static_for<0, PER>([&](auto rr) {
-                constexpr int r = decltype(rr)::value;
-                const int i = lo + tid + 256 * r;
-                if (i < hi) {
-                    int t_lo = i + half - N + 1;
-                    t_lo = t_lo <= 0 ? 0 : (t_lo + hop - 1) / hop;
-                    int t_hi = (i + half) / hop;
-                    if (t_hi > T - 1) t_hi = T - 1;
-                    float s = 0.f;
-                    for (int t = t_lo; t <= t_hi; ++t) s += fr[(size_t)t * N + (i - t * hop + half)];
-                    acc[r] = acc[r] + (s - mean);
-                }
-            });
-        }
-    }
-    float* gx = p.grad_x + (size_t)b * p.L;
-    static_for<0, PER>([&](auto rr) {
-        constexpr int r = decltype(rr)::value;
-        const int i = lo + tid + 256 * r;
-        if (i < hi) gx[i] = acc[r];
-    });
-}
+// the multi-window layer's combine pass: grad_x = 0 + term_0 + term_1 + ... in ascending channel order (dmel_xgrad_multi.h)
+__global__ void __launch_bounds__(256) dmel_xgrad_combine_multi_kernel(XgradCombineMultiParams p) { xgrad_combine_multi_body(p); }
 
 // the wave-FFT path takes this shape (otherwise the LDS radix-2 kernels above run)
 bool xgrad_wave_shape(int n_fft, int n_mels, int win_n, int* frames_per_tile)
@@ -161,36 +85,20 @@ template <> struct XgKernels<XgradParams> {
     static constexpr auto gather = dmel_xgrad_gather_kernel, combine = dmel_xgrad_combine_kernel;
 };
 
+static constexpr auto kMultiWave = [](auto nn) { return dmel_xgrad_wave_multi_kernel<decltype(nn)::value>; };
+
 hipError_t xgrad_prepare_attributes()
 {
-    hipError_t e = xgrad_set_attributes<XgradParams>();
-    for (int n = 32; n <= 2048 && e == hipSuccess; n *= 2)
-        xgrad_with_plan(n, [&](auto nn) {
-            constexpr int N = decltype(nn)::value;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(dmel_xgrad_wave_multi_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, XgPlan<N>::LDS_MAX);
-        });
-    return e;
+    const hipError_t e = xgrad_set_attributes<XgradParams>();
+    return e != hipSuccess ? e : xgrad_set_wave_attributes(kMultiWave);
 }
 
 hipError_t launch_xgrad(const XgradParams& p, hipStream_t s) { return xgrad_launch(p, s); }
 hipError_t launch_xgrad_frames(const XgradParams& p, hipStream_t s) { return xgrad_launch_frames(p, s); }
 hipError_t launch_xgrad_gather(const XgradParams& p, hipStream_t s) { return xgrad_launch_second(dmel_xgrad_gather_kernel, p, s); }
 
-// the multi-window layer: one wave-FFT launch for the `count` channels of ch_list at p.p.N (ch_grid = B x tiles workgroups each)
-hipError_t launch_xgrad_wave_multi(const XgradMultiParams& p, hipStream_t s)
-{
-    const long long grid = (long long)p.count * p.ch_grid;
-    if (p.count < 1 || p.ch_grid < 1 || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipError_t e = hipErrorInvalidValue;
-    xgrad_with_plan(p.p.N, [&](auto nn) {
-        constexpr int N = decltype(nn)::value;
-        XgradMultiParams q = p;
-        q.p.tw2_off = (int)xgrad_wave_tw2_off<N>(p.p.M, p.p.win_n);
-        hipLaunchKernelGGL(dmel_xgrad_wave_multi_kernel<N>, dim3((unsigned)grid), dim3(XgPlan<N>::THREADS), xgrad_wave_lds<N>(p.p.M, p.p.win_n), s, q);
-        e = hipGetLastError();
-    });
-    return e;
-}
+// the multi-window layer's wave-FFT launch (xgrad_launch_wave_multi, dmel_xgrad_multi.h)
+hipError_t launch_xgrad_wave_multi(const XgradMultiParams& p, hipStream_t s) { return xgrad_launch_wave_multi(p, kMultiWave, s); }
 
 hipError_t launch_xgrad_combine_multi(const XgradCombineMultiParams& p, int batch, hipStream_t s)
 {

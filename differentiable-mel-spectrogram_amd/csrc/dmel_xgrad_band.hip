@@ -7,7 +7,7 @@
 // dmel_xgrad_band_stage_kernel writes that masked (B, M, T) cotangent out and the scalar frames kernel runs on it.  The combine pass is
 // dmel_xgrad_combine_multi_kernel (dmel_xgrad.hip).  A translation unit of its own: the kernels of dmel_xgrad.hip and dmel_xgrad_len.hip
 // keep their code.
-#include "dmel_xgrad_plan.h"
+#include "dmel_xgrad_multi.h"
 
 namespace dmel {
 
@@ -37,34 +37,12 @@ __global__ void __launch_bounds__(256) dmel_xgrad_band_stage_kernel(XgradBandSta
     }
 }
 
-hipError_t xgrad_band_prepare_attributes()
-{
-    hipError_t e = hipSuccess;
-    for (int n = 32; n <= 2048 && e == hipSuccess; n *= 2)
-        xgrad_with_plan(n, [&](auto nn) {
-            constexpr int N = decltype(nn)::value;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(dmel_xgrad_wave_band_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize, XgPlan<N>::LDS_MAX);
-        });
-    return e;
-}
+static constexpr auto kBandWave = [](auto nn) { return dmel_xgrad_wave_band_kernel<decltype(nn)::value>; };
 
-// one wave-FFT launch for the `count` channels of ch_list at p.p.N (ch_grid = B x tiles workgroups each), as launch_xgrad_wave_multi
-hipError_t launch_xgrad_wave_band(const XgradBandParams& p, hipStream_t s)
-{
-    const long long grid = (long long)p.count * p.ch_grid;
-    if (p.count < 1 || p.ch_grid < 1 || grid > 0x7fffffffLL || p.p.spec_mode) return hipErrorInvalidValue;
-    for (int c = 0; c < kMaxChannels; ++c)
-        if (p.band_edges[c] < 0 || p.band_edges[c] > p.band_edges[c + 1] || p.band_edges[c + 1] > p.p.M) return hipErrorInvalidValue;
-    hipError_t e = hipErrorInvalidValue;
-    xgrad_with_plan(p.p.N, [&](auto nn) {
-        constexpr int N = decltype(nn)::value;
-        XgradBandParams q = p;
-        q.p.tw2_off = (int)xgrad_wave_tw2_off<N>(p.p.M, p.p.win_n);
-        hipLaunchKernelGGL(dmel_xgrad_wave_band_kernel<N>, dim3((unsigned)grid), dim3(XgPlan<N>::THREADS), xgrad_wave_lds<N>(p.p.M, p.p.win_n), s, q);
-        e = hipGetLastError();
-    });
-    return e;
-}
+hipError_t xgrad_band_prepare_attributes() { return xgrad_set_wave_attributes(kBandWave); }
+
+// the band-split layer's wave-FFT launch (xgrad_launch_wave_multi, dmel_xgrad_multi.h: the band edges are checked there)
+hipError_t launch_xgrad_wave_band(const XgradBandParams& p, hipStream_t s) { return xgrad_launch_wave_multi(p, kBandWave, s); }
 
 hipError_t launch_xgrad_band_stage(const XgradBandStageParams& p, hipStream_t s)
 {

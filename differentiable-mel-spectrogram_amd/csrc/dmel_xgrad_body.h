@@ -137,27 +137,11 @@ __device__ __forceinline__ void xgrad_gather_body(const P& p)
         return;
     }
     float mean = 0.f;
-    if (p.remove_dc) {
-        double acc = 0.0;
-        for (int t = tid; t < Tc; t += 256) acc += p.csum[(size_t)b * T + t];
-        red[tid] = acc;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-        mean = (float)(red[0] / (double)Lc);
-    }
+    if (p.remove_dc) mean = xgrad_frame_mean(p.csum, (size_t)b * T, Tc, Lc, red, tid);
     const float* fr = p.frames + (size_t)b * T * N;
     for (int i = lo + tid; i < hi; i += 256) {
         float v = 0.f;
-        if (!LEN || i < Lc) {
-            // frames with 0 <= i - t hop + N/2 < N, in increasing t
-            int t_lo = i + half - N + 1;
-            t_lo = t_lo <= 0 ? 0 : (t_lo + hop - 1) / hop;
-            int t_hi = (i + half) / hop;
-            if (t_hi > Tc - 1) t_hi = Tc - 1;
-            float s = 0.f;
-            for (int t = t_lo; t <= t_hi; ++t) s += fr[(size_t)t * N + (i - t * hop + half)];
-            v = s - mean;
-        }
+        if (!LEN || i < Lc) v = xgrad_frame_sum(fr, i, N, half, hop, Tc) - mean;
         gx[i] = v;
     }
 }
@@ -188,15 +172,6 @@ __device__ __forceinline__ void xgrad_combine_body(const P& p)
     const int u_lo = lo + half, u_hi = hi - 1 + half;
     const int qa = u_lo < span ? 0 : (u_lo - span) / ts + 1;
     const int qb = min(ctiles - 1, u_hi / ts);
-    auto clip_mean = [&]() {
-        float mean = 0.f;
-        if (p.remove_dc) {
-            double acc = 0.0;
-            for (int q = 0; q < ctiles; ++q) acc += p.csum[(size_t)b * tiles + q];  // uniform: every thread adds the same values in the same order
-            mean = (float)(acc / (double)Lc);
-        }
-        return mean;
-    };
     // rows of four samples when every row involved starts on a 16-byte boundary (hop, n_fft / 2 and the row stride multiples of 4) and,
     // LEN, the clip ends between two rows (Lc a multiple of 4: a row is inside the clip or past it as a whole)
     const bool vec = ((p.hop | half | p.L | span | (LEN ? Lc : 0)) & 3) == 0 && ((reinterpret_cast<uintptr_t>(p.frames) | reinterpret_cast<uintptr_t>(p.grad_x)) & 15) == 0;
@@ -218,7 +193,7 @@ __device__ __forceinline__ void xgrad_combine_body(const P& p)
                 }
             }
         });
-        const float mean = clip_mean();                            // (its loads travel with the segment loads above)
+        const float mean = p.remove_dc ? xgrad_tile_mean(p.csum, b, tiles, ctiles, Lc) : 0.f;   // (its loads travel with the segment loads above)
         static_for<0, PER>([&](auto rr) {
             constexpr int r = decltype(rr)::value;
             const int i = lo + (tid + 256 * r) * 4;
@@ -228,17 +203,10 @@ __device__ __forceinline__ void xgrad_combine_body(const P& p)
         });
         return;
     }
-    const float mean = clip_mean();
+    const float mean = p.remove_dc ? xgrad_tile_mean(p.csum, b, tiles, ctiles, Lc) : 0.f;
     #pragma unroll 4
     for (int i = lo + tid; i < hi; i += 256) {
-        const int u = i + half;
-        float s = 0.f;
-        if (i < end)
-            for (int q = qa; q <= qb; ++q) {
-                const int off = u - q * ts;
-                if (off >= 0 && off < span) s += sg[(size_t)q * span + off];
-            }
-        gx[i] = i < end ? s - mean : 0.f;
+        gx[i] = i < end ? xgrad_segment_sum(sg, i + half, qa, qb, span, ts) - mean : 0.f;
     }
 }
 
@@ -295,9 +263,7 @@ template <class P> static hipError_t xgrad_set_attributes()
     auto set = [](auto kernel, int bytes) { return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
     hipError_t e = set(XgKernels<P>::template frames<false>, kMaxNfft * (int)sizeof(float2));
     if (e == hipSuccess) e = set(XgKernels<P>::template frames<true>, 8192 * 12);
-    for (int n = 32; n <= 2048 && e == hipSuccess; n *= 2)
-        xgrad_with_plan(n, [&](auto nn) { e = set(XgKernels<P>::template wave<decltype(nn)::value>, XgPlan<decltype(nn)::value>::LDS_MAX); });
-    return e;
+    return e != hipSuccess ? e : xgrad_set_wave_attributes([](auto nn) { return XgKernels<P>::template wave<decltype(nn)::value>; });
 }
 
 }  // namespace dmel

@@ -1,7 +1,12 @@
-// dmel_xgrad_plan.h -- what the two translation units of the gradient w.r.t. the waveform share: dmel_xgrad.hip (clips of n_points samples,
-// the scalar and the multi-window layer) and dmel_xgrad_len.hip (clips of per-clip lengths).  The geometry of the wave-FFT kernel
-// (csrc/dmel_xgrad_wave_body.inc), its LDS layout, the dispatch over n_fft and the clip-length load.  (The launch parameters, XgradParams and
-// XgradLenParams, are in dmel_kernels.h; the kernels both units instantiate and their launch logic in dmel_xgrad_body.h.)
+// dmel_xgrad_plan.h -- what the four translation units of the gradient w.r.t. the waveform share:
+//   dmel_xgrad.hip       clips of n_points samples: the scalar layer, the multi-window layer's wave kernel and combine pass
+//   dmel_xgrad_len.hip   the scalar layer over clips of per-clip lengths
+//   dmel_xgrad_band.hip  the band-split layer's wave kernel and its staging kernel
+//   dmel_xgrad_klen.hip  the K-window layers over clips of per-clip lengths
+// The geometry of the wave-FFT kernel (csrc/dmel_xgrad_wave_body.inc), its LDS layout, the dispatch over n_fft, the clip-length load and the
+// per-sample arithmetic of the second pass: every kernel that forms a sample of grad_x takes its sums and its mean from the four helpers at
+// the end of this file, which is what makes the K-window layers' x.grad the K scalar layers' sum bit for bit.  (The launch parameters are in
+// dmel_kernels.h; the scalar kernels' bodies and launch logic in dmel_xgrad_body.h, the K-window ones in dmel_xgrad_multi.h.)
 #pragma once
 #include <type_traits>
 #include "dmel_kernels.h"
@@ -74,6 +79,64 @@ template <class F> static bool xgrad_with_plan(int n, F&& f)
     case 2048: f(IC<2048>{}); return true;
     default: return false;
     }
+}
+
+// raises the dynamic-LDS limit of the wave-FFT kernels kernel_of(IC<N>) names, n_fft 32 ... 2048
+template <class K> static hipError_t xgrad_set_wave_attributes(K kernel_of)
+{
+    hipError_t e = hipSuccess;
+    for (int n = 32; n <= 2048 && e == hipSuccess; n *= 2)
+        xgrad_with_plan(n, [&](auto nn) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(nn)), hipFuncAttributeMaxDynamicSharedMemorySize, XgPlan<decltype(nn)::value>::LDS_MAX);
+        });
+    return e;
+}
+
+// ---- a sample of grad_x: s - mean ---------------------------------------------------------------------------------------------------------
+// The one copy of the second pass's arithmetic (gather, combine and the K-window combine).  The order of the additions is the contract.
+
+// wave path: the segments (span samples each, tile starts ts apart) that cover clip sample u - n_fft / 2, tiles qa ... qb in increasing order
+__device__ __forceinline__ float xgrad_segment_sum(const float* sg, int u, int qa, int qb, int span, int ts)
+{
+    float s = 0.f;
+    for (int q = qa; q <= qb; ++q) {
+        const int off = u - q * ts;
+        if (off >= 0 && off < span) s += sg[(size_t)q * span + off];
+    }
+    return s;
+}
+
+// LDS path: the rows of fr (Tc frames of N samples) with 0 <= i - t hop + half < N (half = N / 2), in increasing t
+__device__ __forceinline__ float xgrad_frame_sum(const float* fr, int i, int N, int half, int hop, int Tc)
+{
+    int t_lo = i + half - N + 1;
+    t_lo = t_lo <= 0 ? 0 : (t_lo + hop - 1) / hop;
+    int t_hi = (i + half) / hop;
+    if (t_hi > Tc - 1) t_hi = Tc - 1;
+    float s = 0.f;
+    for (int t = t_lo; t <= t_hi; ++t) s += fr[(size_t)t * N + (i - t * hop + half)];
+    return s;
+}
+
+// wave path: the first ctiles of clip b's fp64 tile sums (rows of `tiles`) added one after the other (uniform: every thread adds the same
+// values in the same order), over Lc
+__device__ __forceinline__ float xgrad_tile_mean(const double* csum, int b, int tiles, int ctiles, int Lc)
+{
+    double acc = 0.0;
+    for (int q = 0; q < ctiles; ++q) acc += csum[(size_t)b * tiles + q];
+    return (float)(acc / (double)Lc);
+}
+
+// LDS path: the clip's Tc fp64 frame sums csum[row ...] as 256 strided partial sums and a tree over them in red (256 doubles of LDS; every
+// thread of the workgroup calls, barriers inside, and nobody is still reading red), over Lc
+__device__ __forceinline__ float xgrad_frame_mean(const double* csum, size_t row, int Tc, int Lc, double* red, int tid)
+{
+    double acc = 0.0;
+    for (int t = tid; t < Tc; t += 256) acc += csum[row + t];
+    red[tid] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+    return (float)(red[0] / (double)Lc);
 }
 
 }  // namespace dmel

@@ -1,12 +1,16 @@
-// dmel_xgrad_wave_body.inc -- the wave-FFT kernel of the gradient w.r.t. the waveform, included twice by dmel_xgrad.hip: DMEL_XG_MULTI = 0
-// makes dmel_xgrad_wave_kernel (the scalar layer), 1 makes dmel_xgrad_wave_multi_kernel (the multi-window layer: the channel slot comes out of
-// the relabelled workgroup index, as in dmel_fwd_multi_kernel).  dmel_xgrad_len.hip includes it a third time with DMEL_XG_LEN = 1:
-// dmel_xgrad_wave_len_kernel, the scalar layer over clips of per-clip lengths (XgradLenParams).  The XG_* names below expand, for the two
-// kernels of dmel_xgrad.hip, to exactly the tokens they were written with, so that their code does not change.
-// dmel_xgrad_band.hip includes it a fourth time with DMEL_XG_MULTI = 1 and DMEL_XG_BAND = 1: dmel_xgrad_wave_band_kernel, the multi kernel's
-// channel slot with ONE image behind grad_out / out (XgradBandParams): a channel stages only its own rows of it, every other row of gm is +0.0.
-// dmel_xgrad_klen.hip includes it twice more with DMEL_XG_MULTI = 1 and DMEL_XG_LEN = 1, without and with DMEL_XG_BAND:
-// dmel_xgrad_wave_multi_len_kernel and dmel_xgrad_wave_band_len_kernel, the K-window layers over clips of per-clip lengths.
+// dmel_xgrad_wave_body.inc -- the wave-FFT kernel of the gradient w.r.t. the waveform.  Six builds, chosen by the macros set at the #include:
+//
+//   DMEL_XG_MULTI  DMEL_XG_BAND  DMEL_XG_LEN   kernel                              parameters            file
+//   0              -             -             dmel_xgrad_wave_kernel              XgradParams           dmel_xgrad.hip
+//   1              -             -             dmel_xgrad_wave_multi_kernel        XgradMultiParams      dmel_xgrad.hip
+//   0              -             1             dmel_xgrad_wave_len_kernel          XgradLenParams        dmel_xgrad_len.hip
+//   1              1             -             dmel_xgrad_wave_band_kernel         XgradBandParams       dmel_xgrad_band.hip
+//   1              -             1             dmel_xgrad_wave_multi_len_kernel    XgradMultiLenParams   dmel_xgrad_klen.hip
+//   1              1             1             dmel_xgrad_wave_band_len_kernel     XgradBandLenParams    dmel_xgrad_klen.hip
+//
+// MULTI: the channel slot comes out of the relabelled workgroup index, as in dmel_fwd_multi_kernel.  BAND: the multi kernel's channel slot with
+// ONE image behind grad_out / out; a channel stages only its own rows of it, every other row of gm is +0.0.  LEN: clips of per-clip lengths.
+// The XG_* names below expand, for the two kernels of dmel_xgrad.hip, to exactly the tokens they were written with.
 #if DMEL_XG_BAND && DMEL_XG_LEN
 #define XG_KERNEL dmel_xgrad_wave_band_len_kernel
 #define XG_PARAMS XgradBandLenParams mp
