@@ -11,8 +11,8 @@ from __future__ import annotations
 
 import importlib
 
-__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "PCEN", "capi", "synth", "dist",
-           "nets", "panns", "graph", "optim", "pcen"]
+__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "PCEN", "BandNorm", "capi", "synth", "dist",
+           "nets", "panns", "graph", "optim", "pcen", "bandnorm"]
 
 _LAZY = {
     "MelSpectrogramLayer": ("layer", "MelSpectrogramLayer"),
@@ -25,6 +25,7 @@ _LAZY = {
     "GraphedStep": ("graph", "GraphedStep"),
     "LambdAdam": ("optim", "LambdAdam"),
     "PCEN": ("pcen", "PCEN"),
+    "BandNorm": ("bandnorm", "BandNorm"),
 }
 
 
@@ -32,6 +33,6 @@ def __getattr__(name):
     if name in _LAZY:
         mod, attr = _LAZY[name]
         return getattr(importlib.import_module(f"dmel_amd.{mod}"), attr)
-    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim", "pcen"):
+    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim", "pcen", "bandnorm"):
         return importlib.import_module(f"dmel_amd.{name}")
     raise AttributeError(name)

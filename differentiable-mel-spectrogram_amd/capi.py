@@ -142,6 +142,9 @@ _SIGNATURES = {
     "dmel_pcen_scratch_bytes": (C.c_size_t, [i64]),
     "dmel_pcen_forward": (status, [vp, i64, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp]),
     "dmel_pcen_backward": (status, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp]),
+    "dmel_bandnorm_scratch_bytes": (C.c_size_t, [i64, i32]),
+    "dmel_bandnorm_forward": (status, [vp, i64, i32, i64, i32, vp, vp, vp, i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, vp]),
+    "dmel_bandnorm_backward": (status, [vp, vp, vp, i64, i32, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "dmel_scratch_bytes_multi": (C.c_size_t, [vp, i32, i32]),
     "dmel_forward_multi": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_multi_dev": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
@@ -272,6 +275,32 @@ def pcen_backward(g_ptr: int, e_ptr: int, m_ptr: int, rows: int, n_mels: int, n_
     """dmel_pcen_backward: dE and / or the (4, n_mels) gradients of alpha, delta, r, s (``scratch_ptr``: pcen_scratch_bytes(rows) bytes)"""
     _check(load().dmel_pcen_backward(g_ptr, e_ptr, m_ptr, int(rows), int(n_mels), int(n_time), alpha_ptr, delta_ptr, r_ptr, s_ptr,
                                      C.c_float(float(eps)), de_ptr or None, dparams_ptr or None, scratch_ptr or None, stream))
+
+
+def bandnorm_scratch_bytes(rows: int, n_mels: int) -> int:
+    """dmel_bandnorm_scratch_bytes: what bandnorm_backward (and the training forward of the batch statistics) needs (a pure function, no device)"""
+    return int(load().dmel_bandnorm_scratch_bytes(int(rows), int(n_mels)))
+
+
+def bandnorm_forward(s_ptr: int, rows: int, n_mels: int, rows_per_clip: int, n_time: int, lengths_ptr: int | None, weight_ptr: int | None,
+                     bias_ptr: int | None, batch_stats: bool, training: bool, eps: float, momentum: float, running_mean_ptr: int | None,
+                     running_var_ptr: int | None, num_batches_tracked_ptr: int | None, y_ptr: int, stats_ptr: int, scratch_ptr: int | None,
+                     stream: int) -> None:
+    """dmel_bandnorm_forward: y and the fp64 (mu, rstd) pairs of ``rows`` x ``n_time`` fp32 frames, band = row % n_mels,
+    clip = row // rows_per_clip, valid frames t < lengths[clip] (int32 on the device; None: all)"""
+    _check(load().dmel_bandnorm_forward(s_ptr, int(rows), int(n_mels), int(rows_per_clip), int(n_time), lengths_ptr or None, weight_ptr or None,
+                                        bias_ptr or None, int(bool(batch_stats)), int(bool(training)), C.c_double(float(eps)),
+                                        C.c_double(float(momentum)), running_mean_ptr or None, running_var_ptr or None,
+                                        num_batches_tracked_ptr or None, y_ptr, stats_ptr, scratch_ptr or None, stream))
+
+
+def bandnorm_backward(g_ptr: int, s_ptr: int, stats_ptr: int, rows: int, n_mels: int, rows_per_clip: int, n_time: int, lengths_ptr: int | None,
+                      weight_ptr: int | None, batch_stats: bool, training: bool, ds_ptr: int | None, dweight_ptr: int | None,
+                      dbias_ptr: int | None, scratch_ptr: int, stream: int) -> None:
+    """dmel_bandnorm_backward: ds and / or the (n_mels,) gradients of weight and bias (``scratch_ptr``: bandnorm_scratch_bytes(rows, n_mels) bytes)"""
+    _check(load().dmel_bandnorm_backward(g_ptr, s_ptr, stats_ptr, int(rows), int(n_mels), int(rows_per_clip), int(n_time), lengths_ptr or None,
+                                         weight_ptr or None, int(bool(batch_stats)), int(bool(training)), ds_ptr or None, dweight_ptr or None,
+                                         dbias_ptr or None, scratch_ptr, stream))
 
 
 def device_count() -> int:

@@ -3019,6 +3019,86 @@ dmel_status dmel_pcen_backward(const float* g, const float* E, const float* M, i
     return DMEL_OK;
 }
 
+namespace {
+// what dmel_bandnorm_forward and dmel_bandnorm_backward check alike; DMEL_OK with *noop set: nothing to launch
+dmel_status bandnorm_check(const char* who, int64_t rows, int32_t n_mels, int64_t rows_per_clip, int32_t T, int32_t batch_stats, int32_t training,
+                           const void* stats, bool* noop)
+{
+    const std::string w(who);
+    *noop = false;
+    if (n_mels < 1 || rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_mels / T out of range");
+    if (rows_per_clip < 1 || rows_per_clip % n_mels != 0)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows_per_clip must be a positive multiple of n_mels (band = row % n_mels)");
+    if (rows % rows_per_clip != 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows must be a multiple of rows_per_clip (clip = row / rows_per_clip)");
+    if ((batch_stats != 0 && batch_stats != 1) || (training != 0 && training != 1))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": batch_stats and training are 0 or 1");
+    if (!stats || (reinterpret_cast<uintptr_t>(stats) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats must be a 16-byte aligned buffer");
+    if (rows == 0 || T == 0) { *noop = true; return DMEL_OK; }
+    if (dmel::bandnorm_blocks(rows, T) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
+    return DMEL_OK;
+}
+}  // namespace
+
+size_t dmel_bandnorm_scratch_bytes(int64_t rows, int32_t n_mels)
+{
+    return (rows > 0 ? (size_t)rows * 2 * sizeof(double) : 0) + (n_mels > 0 ? (size_t)n_mels * 2 * sizeof(double) : 0);
+}
+
+dmel_status dmel_bandnorm_forward(const float* s, int64_t rows, int32_t n_mels, int64_t rows_per_clip, int32_t T, const int32_t* frame_lengths_or_null,
+                                  const float* weight_or_null, const float* bias_or_null, int32_t batch_stats, int32_t training, double eps,
+                                  double momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked_or_null, float* y,
+                                  double* stats, void* scratch, void* stream)
+{
+    bool noop = false;
+    const dmel_status st = bandnorm_check("dmel_bandnorm_forward", rows, n_mels, rows_per_clip, T, batch_stats, training, stats, &noop);
+    if (st != DMEL_OK) return st;
+    if (!s || !y) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: NULL pointer (s / y)");
+    if (!std::isfinite(eps) || !(eps > 0.0)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: eps must be finite and > 0");
+    if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: momentum must lie in 0 ... 1");
+    if (batch_stats && !training && (!running_mean || !running_var))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: eval mode of the batch statistics reads running_mean and running_var");
+    if (!batch_stats && (running_mean || running_var || num_batches_tracked_or_null))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: clip statistics keep no running_mean / running_var / num_batches_tracked");
+    if ((running_mean == nullptr) != (running_var == nullptr))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: running_mean and running_var come together");
+    if (batch_stats && training && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15)))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: the batch statistics need 16-byte aligned scratch of dmel_bandnorm_scratch_bytes(rows, n_mels)");
+    if (noop) return DMEL_OK;
+    const dmel_status sd = pcen_device("dmel_bandnorm_forward");
+    if (sd != DMEL_OK) return sd;
+    dmel::BandNormParams p{};
+    p.s = s; p.y = y; p.lengths = frame_lengths_or_null; p.gamma = weight_or_null; p.beta = bias_or_null;
+    p.stats = stats; p.partials = static_cast<double*>(scratch);
+    p.running_mean = running_mean; p.running_var = running_var; p.num_batches_tracked = reinterpret_cast<long long*>(num_batches_tracked_or_null);
+    p.rows = rows; p.rows_per_clip = rows_per_clip; p.n_mels = n_mels; p.T = T;
+    p.batch_stats = batch_stats; p.eval = (batch_stats && !training) ? 1 : 0; p.eps = eps; p.momentum = momentum;
+    DMEL_HIP(dmel::launch_bandnorm_fwd(p, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
+dmel_status dmel_bandnorm_backward(const float* g, const float* s, const double* stats, int64_t rows, int32_t n_mels, int64_t rows_per_clip, int32_t T,
+                                   const int32_t* frame_lengths_or_null, const float* weight_or_null, int32_t batch_stats, int32_t training,
+                                   float* ds_or_null, float* dweight_or_null, float* dbias_or_null, void* scratch, void* stream)
+{
+    bool noop = false;
+    const dmel_status st = bandnorm_check("dmel_bandnorm_backward", rows, n_mels, rows_per_clip, T, batch_stats, training, stats, &noop);
+    if (st != DMEL_OK) return st;
+    if (!g || !s) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_backward: NULL pointer (g / s)");
+    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_backward: needs 16-byte aligned scratch of dmel_bandnorm_scratch_bytes(rows, n_mels)");
+    if (noop || (!ds_or_null && !dweight_or_null && !dbias_or_null)) return DMEL_OK;      // nothing is written
+    const dmel_status sd = pcen_device("dmel_bandnorm_backward");
+    if (sd != DMEL_OK) return sd;
+    dmel::BandNormParams p{};
+    p.g = g; p.s = s; p.ds = ds_or_null; p.lengths = frame_lengths_or_null; p.gamma = weight_or_null;
+    p.stats = const_cast<double*>(stats); p.partials = static_cast<double*>(scratch); p.band_means = p.partials + 2 * rows;
+    p.dweight = dweight_or_null; p.dbias = dbias_or_null;
+    p.rows = rows; p.rows_per_clip = rows_per_clip; p.n_mels = n_mels; p.T = T;
+    p.batch_stats = batch_stats; p.eval = (batch_stats && !training) ? 1 : 0;
+    DMEL_HIP(dmel::launch_bandnorm_bwd(p, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
 dmel_status dmel_plan_set_profiling(dmel_plan* plan, int32_t enable)
 {
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");

@@ -723,6 +723,30 @@ long long pcen_blocks(long long rows, int T);      // workgroups of one launch
 hipError_t launch_pcen_fwd(PcenParams p, hipStream_t s);
 hipError_t launch_pcen_bwd(PcenParams p, float* dparams, hipStream_t s);      // dparams: (4, n_mels) or nullptr
 
+// BandNorm behind the mel layers (dmel_bandnorm_forward / dmel_bandnorm_backward, csrc/dmel_bandnorm.hip): rows x T fp32, band = row % n_mels,
+// clip = row / rows_per_clip, the valid frames of a row are t < lengths[clip]
+struct BandNormParams {
+    const float* s;             // (rows, T) input
+    const float* g;             // backward: cotangent of y
+    float* y;                   // forward: output
+    float* ds;                  // backward: nullptr = not asked for
+    const int* lengths;         // (rows / rows_per_clip) valid frames per clip; nullptr: T for every clip
+    const float* gamma; const float* beta;      // (n_mels) each; nullptr: 1 and 0
+    double* stats;              // (mu, rstd) pairs: per row (clip statistics) or per band (batch statistics); forward writes, backward reads
+    double* partials;           // (rows, 2) scratch: forward (mean, sum of squared deviations) of a row; backward (sum g, sum g yh)
+    double* band_means;         // backward, batch statistics: (n_mels, 2) scratch, (mean g, mean g yh) of a band
+    float* running_mean; float* running_var; long long* num_batches_tracked;      // batch statistics: (n_mels), (n_mels), one word; nullptr: none
+    float* dweight; float* dbias;               // backward: (n_mels) each; nullptr = not asked for
+    long long rows, rows_per_clip; int n_mels, T;
+    int batch_stats;            // 0: statistics of each row; 1: of each band over the batch
+    int eval;                   // batch statistics only: 1 = the running buffers are the statistics
+    double eps, momentum;
+    int W, logw;                // set by the launchers: lanes per row (next power of two >= T up to 32 frames, else 64)
+};
+long long bandnorm_blocks(long long rows, int T);  // workgroups of a launch over the rows
+hipError_t launch_bandnorm_fwd(BandNormParams p, hipStream_t s);
+hipError_t launch_bandnorm_bwd(BandNormParams p, hipStream_t s);
+
 // Peer-to-peer all-reduce of the one scalar this path exchanges (d lambd), folded into the tail of the dot kernel: the workgroup
 // that draws the last ticket stores (step, local sum) as ONE 8-byte granule into slot `rank` of every rank's inbox -- peer memory
 // mapped over xGMI, system-scope stores -- then polls its own inbox until every rank's granule of this step has arrived and adds

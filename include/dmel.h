@@ -517,6 +517,40 @@ dmel_status dmel_pcen_backward(const float* g, const float* E, const float* M, i
                                const float* alpha, const float* delta, const float* r, const float* s, float eps,
                                float* dE_or_null, float* dparams_or_null, float* scratch, void* stream);
 
+/* ---- BandNorm: length-aware per-band standardisation behind the mel layers (dmel_amd.BandNorm; plan-free, as PCEN) ------------------
+ * What a consumer applies first to a mel image -- batch normalisation over the mel bins (panns.py:169-172) or per-clip mean / variance
+ * normalisation -- with the statistics taken over the VALID frames only.  Every row is one (clip[, channel], band) triple of T fp32 frames:
+ * band = row % n_mels, clip = row / rows_per_clip (rows_per_clip = channels * n_mels; rows a multiple of it) -- what a contiguous
+ * (B[, C], n_mels, T) tensor gives.  frame_lengths: rows / rows_per_clip device int32 values Tc, read by the kernels only (what
+ * layer.frame_lengths(lengths) returns); NULL: every clip has T valid frames.  The valid frames of a clip are t < Tc.
+ *   y = (s - mu) rstd weight[band] + bias[band]  on valid frames,  rstd = 1 / sqrt(var + eps), var the biased variance;  +0.0 on pad frames
+ * weight / bias: n_mels device floats each, or NULL (1 and 0).  batch_stats = 0: mu and var of each row over its own valid frames
+ * (utterance-level CMVN; no buffers, training is ignored).  batch_stats = 1, training = 1: mu and var of band m over every valid frame of
+ * every row of that band; running_mean / running_var (n_mels floats each, both or neither) move by nn.BatchNorm2d's rule
+ * r = (1 - momentum) r + momentum v with the unbiased variance n / (n - 1) -- running_var left alone when the band has fewer than two valid
+ * frames, both when it has none -- and *num_batches_tracked (one int64, may be NULL) advances by one, all on the device.  batch_stats = 1,
+ * training = 0: the running buffers are the statistics and nothing is updated.
+ * `stats` receives the (mu, rstd) pairs in fp64 that dmel_bandnorm_backward reads: 2 * rows doubles with batch_stats = 0, 2 * n_mels with
+ * batch_stats = 1; 16-byte aligned.  `scratch`: dmel_bandnorm_scratch_bytes(rows, n_mels) bytes (16-byte aligned) owned by the caller for
+ * the duration of the call's work on `stream`; the forward needs it with batch_stats = 1 and training = 1 only, the backward always.
+ * dmel_bandnorm_backward takes g = dL/dy and, with yh = (s - mu) rstd, writes  ds = weight rstd (g - mean(g) - yh mean(g yh))  -- the means
+ * over the statistic's own population; with batch_stats = 1 and training = 0  ds = weight rstd g  --, dweight[band] = sum g yh and
+ * dbias[band] = sum g over the valid frames; each may be NULL and is then neither computed nor written.  ds is +0.0 on pad frames.
+ * s and g are never read at a pad frame.  A frame_lengths[b] outside 1 ... T makes every frame of that clip's rows NaN in y and ds; the clip
+ * contributes nothing to batch statistics, running buffers or parameter gradients.  Sums are accumulated in fp64 and combined in a fixed
+ * order: no atomics, the same inputs give the same bits.  No host read, capturable.  Three launches at most per call.  rows == 0 or
+ * T == 0: DMEL_OK, nothing is launched or written. */
+size_t dmel_bandnorm_scratch_bytes(int64_t rows, int32_t n_mels);
+dmel_status dmel_bandnorm_forward(const float* s, int64_t rows, int32_t n_mels, int64_t rows_per_clip, int32_t T,
+                                  const int32_t* frame_lengths_or_null, const float* weight_or_null, const float* bias_or_null,
+                                  int32_t batch_stats, int32_t training, double eps, double momentum, float* running_mean,
+                                  float* running_var, int64_t* num_batches_tracked_or_null, float* y, double* stats, void* scratch,
+                                  void* stream);
+dmel_status dmel_bandnorm_backward(const float* g, const float* s, const double* stats, int64_t rows, int32_t n_mels, int64_t rows_per_clip,
+                                   int32_t T, const int32_t* frame_lengths_or_null, const float* weight_or_null, int32_t batch_stats,
+                                   int32_t training, float* ds_or_null, float* dweight_or_null, float* dbias_or_null, void* scratch,
+                                   void* stream);
+
 /* ---- the multi-window layer: K trainable window widths as K output channels (dmel_amd.MultiWindowMelSpectrogram) ------------------
  * Channel k of (batch, K, n_mels, n_time) is what dmel_forward* computes for lambd[k], bit for bit; 1 <= K <= 8, every channel's n_fft in
  * 32 ... 16384 (the fused kernel).  One launch per DISTINCT n_fft covers all the channels that need it.  out and tangent are (batch, K, M, T);
