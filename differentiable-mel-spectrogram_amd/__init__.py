@@ -11,8 +11,8 @@ from __future__ import annotations
 
 import importlib
 
-__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "PCEN", "BandNorm", "capi", "synth", "dist",
-           "nets", "panns", "graph", "optim", "pcen", "bandnorm"]
+__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "PCEN", "BandNorm", "SpecMask", "capi", "synth", "dist",
+           "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask"]
 
 _LAZY = {
     "MelSpectrogramLayer": ("layer", "MelSpectrogramLayer"),
@@ -26,6 +26,7 @@ _LAZY = {
     "LambdAdam": ("optim", "LambdAdam"),
     "PCEN": ("pcen", "PCEN"),
     "BandNorm": ("bandnorm", "BandNorm"),
+    "SpecMask": ("specmask", "SpecMask"),
 }
 
 
@@ -33,6 +34,6 @@ def __getattr__(name):
     if name in _LAZY:
         mod, attr = _LAZY[name]
         return getattr(importlib.import_module(f"dmel_amd.{mod}"), attr)
-    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim", "pcen", "bandnorm"):
+    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask"):
         return importlib.import_module(f"dmel_amd.{name}")
     raise AttributeError(name)

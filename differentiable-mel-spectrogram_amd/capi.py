@@ -145,6 +145,8 @@ _SIGNATURES = {
     "dmel_bandnorm_scratch_bytes": (C.c_size_t, [i64, i32]),
     "dmel_bandnorm_forward": (status, [vp, i64, i32, i64, i32, vp, vp, vp, i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, vp]),
     "dmel_bandnorm_backward": (status, [vp, vp, vp, i64, i32, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "dmel_specmask_draw": (status, [i64, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
+    "dmel_specmask_apply": (status, [vp, i64, i32, i64, i32, vp, vp, i32, i32, i32, f32, vp, vp]),
     "dmel_scratch_bytes_multi": (C.c_size_t, [vp, i32, i32]),
     "dmel_forward_multi": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_multi_dev": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
@@ -301,6 +303,24 @@ def bandnorm_backward(g_ptr: int, s_ptr: int, stats_ptr: int, rows: int, n_mels:
     _check(load().dmel_bandnorm_backward(g_ptr, s_ptr, stats_ptr, int(rows), int(n_mels), int(rows_per_clip), int(n_time), lengths_ptr or None,
                                          weight_ptr or None, int(bool(batch_stats)), int(bool(training)), ds_ptr or None, dweight_ptr or None,
                                          dbias_ptr or None, scratch_ptr, stream))
+
+
+def specmask_draw(images: int, channels: int, n_mels: int, n_time_frames: int, lengths_ptr: int | None, time_param: int, time_permille: int,
+                  n_time: int, freq_param: int, n_freq: int, rng_state_ptr: int, advance: bool, stripes_ptr: int | None, stream: int) -> None:
+    """dmel_specmask_draw: the (images, n_time + n_freq, 2) int32 table of [lo, hi) stripe pairs from the device words
+    ``rng_state`` = (seed, calls); ``advance`` stores calls + 1 behind the draw"""
+    _check(load().dmel_specmask_draw(int(images), int(channels), int(n_mels), int(n_time_frames), lengths_ptr or None, int(time_param),
+                                     int(time_permille), int(n_time), int(freq_param), int(n_freq), rng_state_ptr or None, int(bool(advance)),
+                                     stripes_ptr or None, stream))
+
+
+def specmask_apply(s_ptr: int, rows: int, n_mels: int, rows_per_clip: int, n_time_frames: int, lengths_ptr: int | None, stripes_ptr: int | None,
+                   n_time: int, n_freq: int, elem_bf16: bool, fill: float, y_ptr: int, stream: int) -> None:
+    """dmel_specmask_apply: y = fill under the table's stripes on valid frames, s's bits elsewhere (``rows`` x ``n_time_frames`` fp32 or bf16
+    elements); the backward is the same call on the cotangent with fill 0"""
+    _check(load().dmel_specmask_apply(s_ptr or None, int(rows), int(n_mels), int(rows_per_clip), int(n_time_frames), lengths_ptr or None,
+                                      stripes_ptr or None, int(n_time), int(n_freq), int(bool(elem_bf16)), C.c_float(float(fill)), y_ptr or None,
+                                      stream))
 
 
 def device_count() -> int:

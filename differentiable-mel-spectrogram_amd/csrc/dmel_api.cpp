@@ -3099,6 +3099,75 @@ dmel_status dmel_bandnorm_backward(const float* g, const float* s, const double*
     return DMEL_OK;
 }
 
+namespace {
+// the element's bits of `fill`: fp32 as it is, bf16 rounded to nearest even (a NaN stays one)
+unsigned specmask_fill_bits(float fill, bool bf16)
+{
+    unsigned u;
+    std::memcpy(&u, &fill, sizeof(u));
+    if (!bf16) return u;
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0u;
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+}  // namespace
+
+dmel_status dmel_specmask_draw(int64_t images, int32_t channels, int32_t n_mels, int32_t T, const int32_t* frame_lengths_or_null,
+                               int32_t time_param, int32_t time_permille, int32_t n_time, int32_t freq_param, int32_t n_freq,
+                               int64_t* rng_state, int32_t advance, int32_t* stripes, void* stream)
+{
+    const std::string w("dmel_specmask_draw");
+    if (images < 0 || images > 0xFFFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": images out of range (the Philox counter holds 32 bits of it)");
+    if (channels < 1 || images % channels != 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": channels must be positive and divide images (clip = image / channels)");
+    if (n_mels < 1 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": n_mels / T out of range");
+    if (n_time < 0 || n_freq < 0 || n_time + n_freq > 8) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": n_time and n_freq must be >= 0 and n_time + n_freq <= 8");
+    if (time_param < 0 || freq_param < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": time_param and freq_param must be >= 0");
+    if (time_permille < 0 || time_permille > 1000) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": time_permille must lie in 0 ... 1000");
+    if (advance != 0 && advance != 1) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": advance is 0 or 1");
+    if (!rng_state || (reinterpret_cast<uintptr_t>(rng_state) & 7)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rng_state must be two 8-byte aligned int64 values (seed, calls)");
+    if (n_time + n_freq > 0 && (!stripes || (reinterpret_cast<uintptr_t>(stripes) & 3)))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stripes must be a buffer of images * (n_time + n_freq) * 2 int32 values");
+    if (images == 0 || T == 0 || n_time + n_freq == 0) return DMEL_OK;                 // nothing to draw: `calls` stays
+    const dmel_status sd = pcen_device("dmel_specmask_draw");
+    if (sd != DMEL_OK) return sd;
+    dmel::SpecMaskDrawParams p{};
+    p.lengths = frame_lengths_or_null; p.rng_state = reinterpret_cast<unsigned long long*>(rng_state); p.stripes = stripes;
+    p.images = images; p.channels = channels; p.n_mels = n_mels; p.T = T;
+    p.time_param = time_param; p.time_permille = time_permille; p.n_time = n_time; p.freq_param = freq_param; p.n_freq = n_freq;
+    p.advance = advance;
+    DMEL_HIP(dmel::launch_specmask_draw(p, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
+dmel_status dmel_specmask_apply(const void* s, int64_t rows, int32_t n_mels, int64_t rows_per_clip, int32_t T,
+                                const int32_t* frame_lengths_or_null, const int32_t* stripes, int32_t n_time, int32_t n_freq,
+                                int32_t elem_bf16, float fill, void* y, void* stream)
+{
+    const std::string w("dmel_specmask_apply");
+    if (n_mels < 1 || rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_mels / T out of range");
+    if (rows_per_clip < 1 || rows_per_clip % n_mels != 0)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows_per_clip must be a positive multiple of n_mels (an image is n_mels rows)");
+    if (rows % rows_per_clip != 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows must be a multiple of rows_per_clip (clip = row / rows_per_clip)");
+    if (n_time < 0 || n_freq < 0 || n_time + n_freq > 8) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": n_time and n_freq must be >= 0 and n_time + n_freq <= 8");
+    if (elem_bf16 != 0 && elem_bf16 != 1) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": elem_bf16 is 0 (fp32) or 1 (bf16)");
+    const int elem_bytes = elem_bf16 ? 2 : 4;
+    if (!s || (reinterpret_cast<uintptr_t>(s) & (uintptr_t)(elem_bytes - 1))) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer aligned to its element");
+    if (!y || (reinterpret_cast<uintptr_t>(y) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": y must be a 16-byte aligned buffer");
+    if (n_time + n_freq > 0 && (!stripes || (reinterpret_cast<uintptr_t>(stripes) & 3)))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stripes must be the table dmel_specmask_draw wrote");
+    if (rows == 0 || T == 0) return DMEL_OK;
+    const int64_t images = rows / n_mels;
+    if ((int64_t)n_mels * T > (1LL << 30)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": n_mels * T is too large (an image has at most 2^30 elements)");
+    if (images * dmel::specmask_waves_per_image(n_mels, T, elem_bytes) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
+    const dmel_status sd = pcen_device("dmel_specmask_apply");
+    if (sd != DMEL_OK) return sd;
+    dmel::SpecMaskParams p{};
+    p.s = s; p.y = y; p.lengths = frame_lengths_or_null; p.stripes = stripes;
+    p.images = images; p.channels = (int)(rows_per_clip / n_mels); p.n_mels = n_mels; p.T = T; p.n_time = n_time; p.n_freq = n_freq;
+    p.fill_bits = specmask_fill_bits(fill, elem_bf16 != 0);
+    DMEL_HIP(dmel::launch_specmask_apply(p, elem_bytes, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
 dmel_status dmel_plan_set_profiling(dmel_plan* plan, int32_t enable)
 {
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");

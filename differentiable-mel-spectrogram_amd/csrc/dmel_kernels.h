@@ -747,6 +747,28 @@ long long bandnorm_blocks(long long rows, int T);  // workgroups of a launch ove
 hipError_t launch_bandnorm_fwd(BandNormParams p, hipStream_t s);
 hipError_t launch_bandnorm_bwd(BandNormParams p, hipStream_t s);
 
+// SpecMask behind the mel layers (dmel_specmask_draw / dmel_specmask_apply, csrc/dmel_specmask.hip): an image is one (clip, channel) pair,
+// n_mels * T consecutive elements; clip = image / channels, the valid frames of a clip are t < lengths[clip]
+struct SpecMaskDrawParams {
+    const int* lengths;         // (images / channels) valid frames per clip; nullptr: T for every clip
+    unsigned long long* rng_state;      // (seed, calls)
+    int* stripes;               // (images, n_time + n_freq, 2): [lo, hi) pairs, the time stripes first
+    long long images; int channels, n_mels, T;
+    int time_param, time_permille, n_time, freq_param, n_freq;
+    int advance;                // 1: calls + 1 is stored behind the last draw
+};
+struct SpecMaskParams {
+    const void* s; void* y;     // (images, n_mels, T) elements of 4 bytes (fp32) or 2 (bf16): moved, never converted
+    const int* lengths; const int* stripes;
+    long long images; int channels, n_mels, T, n_time, n_freq;
+    unsigned fill_bits;         // the fill value as the element's bits
+    long long waves_per_image;  // set by the launcher
+    unsigned t_magic; int t_shift;      // set by the launcher: floor(e / T) = (e * t_magic) >> t_shift for e < 2^30
+};
+long long specmask_waves_per_image(int n_mels, int T, int elem_bytes);
+hipError_t launch_specmask_draw(const SpecMaskDrawParams& p, hipStream_t s);
+hipError_t launch_specmask_apply(SpecMaskParams p, int elem_bytes, hipStream_t s);
+
 // Peer-to-peer all-reduce of the one scalar this path exchanges (d lambd), folded into the tail of the dot kernel: the workgroup
 // that draws the last ticket stores (step, local sum) as ONE 8-byte granule into slot `rank` of every rank's inbox -- peer memory
 // mapped over xGMI, system-scope stores -- then polls its own inbox until every rank's granule of this step has arrived and adds

@@ -17,6 +17,10 @@ from .layer import MelSpectrogramLayer
 
 
 class _MelFrontNet(nn.Module):
+    """The front end the three nets share.  Two opt-in attributes, both ``None`` by default (nothing changes then): ``compression``
+    (``dmel_amd.PCEN``) and, behind it and only while ``self.training``, ``augmentation`` (``dmel_amd.SpecMask``).  ``panns.Cnn6`` keeps its
+    ``_IidAxisMask``: its tensor is transposed there and the reference masks the swapped axes."""
+
     def __init__(self, init_lambd, device, n_mels, sample_rate, n_points, hop_length, optimized, energy_normalize,
                  normalize_window):
         super().__init__()
@@ -35,7 +39,9 @@ class _MelFrontNet(nn.Module):
     def _features(self, x):
         s = self.spectrogram_layer(x)             # already log-compressed when energy_normalize
         compression = getattr(self, "compression", None)      # opt-in: net.compression = dmel_amd.PCEN(n_mels)
-        return s if compression is None else compression(s)
+        s = s if compression is None else compression(s)
+        augmentation = getattr(self, "augmentation", None)    # opt-in: net.augmentation = dmel_amd.SpecMask(...); training only
+        return s if augmentation is None or not self.training else augmentation(s)
 
 
 class MelLinearNet(_MelFrontNet):

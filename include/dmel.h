@@ -551,6 +551,36 @@ dmel_status dmel_bandnorm_backward(const float* g, const float* s, const double*
                                    int32_t training, float* ds_or_null, float* dweight_or_null, float* dbias_or_null, void* scratch,
                                    void* stream);
 
+/* ---- SpecMask: length-aware SpecAugment stripes behind the mel layers (dmel_amd.SpecMask; plan-free, as PCEN and BandNorm) ------------
+ * What a training loop applies behind the normalisation (panns.py:141-142, 174-176: time and frequency masking with iid_masks=True), drawn
+ * over the VALID frames of a zero-padded batch and pinned to the bit.  An image is one (clip, channel) pair of a contiguous
+ * (B[, C], n_mels, T) tensor: image i = clip * channels + channel, n_mels rows of T elements.  Every image draws n_time time stripes, then
+ * n_freq frequency stripes, independently of every other image; n_time + n_freq <= 8, either may be 0.  All of it is integer arithmetic.
+ *   random words   Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key (seed & 0xffffffff,
+ *                  seed >> 32), counter (calls & 0xffffffff, calls >> 32, i, j); stripe k of the image (time stripes first) takes block
+ *                  j = k / 2 and the word pair (w[2 (k % 2)], w[2 (k % 2) + 1]) = (w_a, w_b).  rng_state = (seed, calls): two int64 on the device.
+ *   a stripe       on an axis of `size` positions with cap = min(param, size): width = mulhi32(w_a, cap), lo = mulhi32(w_b, size - width),
+ *                  hi = lo + width -- 0 <= lo <= hi <= size - 1, width <= cap - 1 (0 when cap == 0): torchaudio's mask_along_axis_iid support.
+ *   time stripes   size = Tc = frame_lengths[clip] (NULL: T), param = min(time_param, Tc * time_permille / 1000) in integer division
+ *   freq stripes   size = n_mels, param = freq_param
+ * dmel_specmask_draw writes `stripes`: images * (n_time + n_freq) * 2 int32 values, the [lo, hi) pairs; with advance = 1 it then stores
+ * calls + 1 (after every draw of the call has read calls; one workgroup, a barrier, a plain store: no atomics, no host read, so a captured
+ * call draws fresh stripes on every replay); advance = 0 draws at calls and leaves it.  A frame_lengths[b] outside 1 ... T leaves that clip's
+ * table rows zero.  images == 0, T == 0 or n_time + n_freq == 0: DMEL_OK, nothing is launched and calls stays.
+ * dmel_specmask_apply moves rows x T elements of 4 bytes (elem_bf16 = 0) or 2 (elem_bf16 = 1) from s to y, never converting them:
+ *   y = fill  on a valid frame t < Tc that lies in one of the image's time stripes or whose band lies in one of its frequency stripes
+ *       (fill rounded to bf16, to nearest even, for 2-byte elements);  y = s bit for bit elsewhere -- every pad frame t >= Tc included.
+ * clip = row / rows_per_clip, rows_per_clip = channels * n_mels, rows a multiple of it.  A frame_lengths[b] outside 1 ... T makes every
+ * element of that clip's rows NaN.  The gradient is the same call on the cotangent with fill = +0.0 and the table the forward wrote.
+ * s needs its element's alignment only (16-byte accesses are used where s and y sit alike inside a 16-byte granule, chosen per image from
+ * the addresses); y must be 16-byte aligned.  One launch; rows == 0 or T == 0: DMEL_OK, nothing is launched.  s and y must not overlap. */
+dmel_status dmel_specmask_draw(int64_t images, int32_t channels, int32_t n_mels, int32_t T, const int32_t* frame_lengths_or_null,
+                               int32_t time_param, int32_t time_permille, int32_t n_time, int32_t freq_param, int32_t n_freq,
+                               int64_t* rng_state, int32_t advance, int32_t* stripes, void* stream);
+dmel_status dmel_specmask_apply(const void* s, int64_t rows, int32_t n_mels, int64_t rows_per_clip, int32_t T,
+                                const int32_t* frame_lengths_or_null, const int32_t* stripes, int32_t n_time, int32_t n_freq,
+                                int32_t elem_bf16, float fill, void* y, void* stream);
+
 /* ---- the multi-window layer: K trainable window widths as K output channels (dmel_amd.MultiWindowMelSpectrogram) ------------------
  * Channel k of (batch, K, n_mels, n_time) is what dmel_forward* computes for lambd[k], bit for bit; 1 <= K <= 8, every channel's n_fft in
  * 32 ... 16384 (the fused kernel).  One launch per DISTINCT n_fft covers all the channels that need it.  out and tangent are (batch, K, M, T);
