@@ -11,8 +11,8 @@ from __future__ import annotations
 
 import importlib
 
-__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "PCEN", "BandNorm", "SpecMask", "capi", "synth", "dist",
-           "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask"]
+__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "PCEN", "BandNorm", "SpecMask", "Deltas", "capi", "synth", "dist",
+           "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask", "deltas"]
 
 _LAZY = {
     "MelSpectrogramLayer": ("layer", "MelSpectrogramLayer"),
@@ -27,6 +27,7 @@ _LAZY = {
     "PCEN": ("pcen", "PCEN"),
     "BandNorm": ("bandnorm", "BandNorm"),
     "SpecMask": ("specmask", "SpecMask"),
+    "Deltas": ("deltas", "Deltas"),
 }
 
 
@@ -34,6 +35,6 @@ def __getattr__(name):
     if name in _LAZY:
         mod, attr = _LAZY[name]
         return getattr(importlib.import_module(f"dmel_amd.{mod}"), attr)
-    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask"):
+    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask", "deltas"):
         return importlib.import_module(f"dmel_amd.{name}")
     raise AttributeError(name)

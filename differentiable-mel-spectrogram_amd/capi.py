@@ -147,6 +147,8 @@ _SIGNATURES = {
     "dmel_bandnorm_backward": (status, [vp, vp, vp, i64, i32, i64, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     "dmel_specmask_draw": (status, [i64, i32, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "dmel_specmask_apply": (status, [vp, i64, i32, i64, i32, vp, vp, i32, i32, i32, f32, vp, vp]),
+    "dmel_deltas_forward": (status, [vp, i64, i64, i32, vp, i32, i32, i32, vp, vp]),
+    "dmel_deltas_backward": (status, [vp, i64, i64, i32, vp, i32, i32, i32, vp, vp]),
     "dmel_scratch_bytes_multi": (C.c_size_t, [vp, i32, i32]),
     "dmel_forward_multi": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_multi_dev": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
@@ -321,6 +323,21 @@ def specmask_apply(s_ptr: int, rows: int, n_mels: int, rows_per_clip: int, n_tim
     _check(load().dmel_specmask_apply(s_ptr or None, int(rows), int(n_mels), int(rows_per_clip), int(n_time_frames), lengths_ptr or None,
                                       stripes_ptr or None, int(n_time), int(n_freq), int(bool(elem_bf16)), C.c_float(float(fill)), y_ptr or None,
                                       stream))
+
+
+def deltas_forward(s_ptr: int, rows: int, rows_per_clip: int, n_time_frames: int, lengths_ptr: int | None, win_length: int, order: int,
+                   include_static: bool, y_ptr: int, stream: int) -> None:
+    """dmel_deltas_forward: y = the groups [s,] d[, dd] of ``rows`` x ``n_time_frames`` fp32 values, the stencil's edge at each clip's own
+    last valid frame"""
+    _check(load().dmel_deltas_forward(s_ptr or None, int(rows), int(rows_per_clip), int(n_time_frames), lengths_ptr or None, int(win_length),
+                                      int(order), int(bool(include_static)), y_ptr or None, stream))
+
+
+def deltas_backward(g_ptr: int, rows: int, rows_per_clip: int, n_time_frames: int, lengths_ptr: int | None, win_length: int, order: int,
+                    include_static: bool, ds_ptr: int, stream: int) -> None:
+    """dmel_deltas_backward: ds = g_static + D^T (g_d + D^T g_dd) from the cotangent of dmel_deltas_forward's y"""
+    _check(load().dmel_deltas_backward(g_ptr or None, int(rows), int(rows_per_clip), int(n_time_frames), lengths_ptr or None, int(win_length),
+                                       int(order), int(bool(include_static)), ds_ptr or None, stream))
 
 
 def device_count() -> int:

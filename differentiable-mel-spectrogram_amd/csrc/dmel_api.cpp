@@ -3168,6 +3168,51 @@ dmel_status dmel_specmask_apply(const void* s, int64_t rows, int32_t n_mels, int
     return DMEL_OK;
 }
 
+namespace {
+// both directions of Deltas: `in` / `out` are (s, y) forward and (g, ds) backward
+dmel_status deltas_call(const char* what, const char* in_name, const char* out_name, const float* in, int64_t rows, int64_t rows_per_clip,
+                        int32_t T, const int32_t* lengths, int32_t win_length, int32_t order, int32_t include_static, float* out, bool backward,
+                        void* stream)
+{
+    const std::string w(what);
+    if (rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_time out of range");
+    if (rows_per_clip < 1 || rows % rows_per_clip != 0)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows_per_clip must be positive and divide rows (clip = row / rows_per_clip)");
+    if (win_length != 3 && win_length != 5 && win_length != 7 && win_length != 9)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": win_length must be 3, 5, 7 or 9");
+    if (order != 1 && order != 2) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": order must be 1 or 2");
+    if (include_static != 0 && include_static != 1) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": include_static is 0 or 1");
+    if (!in || (reinterpret_cast<uintptr_t>(in) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": " + in_name + " must be a buffer of fp32 values");
+    if (!out || (reinterpret_cast<uintptr_t>(out) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": " + out_name + " must be a 16-byte aligned buffer");
+    if (lengths && (reinterpret_cast<uintptr_t>(lengths) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": frame_lengths must be int32 values");
+    if (rows == 0 || T == 0) return DMEL_OK;
+    const int n = (win_length - 1) / 2;
+    if (rows > 0x7FFFFFFFLL || dmel::deltas_waves(rows, T, n) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
+    const dmel_status sd = pcen_device(what);
+    if (sd != DMEL_OK) return sd;
+    dmel::DeltasParams p{};
+    p.in = in; p.out = out; p.lengths = lengths; p.rows = rows; p.rows_per_clip = rows_per_clip;
+    p.T = T; p.n = n; p.order = order; p.include_static = include_static; p.groups = include_static + order;
+    p.inv_denom = 3.0 / (double)(n * (n + 1) * (2 * n + 1));
+    DMEL_HIP(dmel::launch_deltas(p, backward, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+}  // namespace
+
+dmel_status dmel_deltas_forward(const float* s, int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null,
+                                int32_t win_length, int32_t order, int32_t include_static, float* y, void* stream)
+{
+    return deltas_call("dmel_deltas_forward", "s", "y", s, rows, rows_per_clip, n_time, frame_lengths_or_null, win_length, order, include_static, y,
+                       false, stream);
+}
+
+dmel_status dmel_deltas_backward(const float* g, int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null,
+                                 int32_t win_length, int32_t order, int32_t include_static, float* ds, void* stream)
+{
+    return deltas_call("dmel_deltas_backward", "g", "ds", g, rows, rows_per_clip, n_time, frame_lengths_or_null, win_length, order, include_static,
+                       ds, true, stream);
+}
+
 dmel_status dmel_plan_set_profiling(dmel_plan* plan, int32_t enable)
 {
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");

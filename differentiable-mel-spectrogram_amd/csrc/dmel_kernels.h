@@ -769,6 +769,19 @@ long long specmask_waves_per_image(int n_mels, int T, int elem_bytes);
 hipError_t launch_specmask_draw(const SpecMaskDrawParams& p, hipStream_t s);
 hipError_t launch_specmask_apply(SpecMaskParams p, int elem_bytes, hipStream_t s);
 
+// Deltas behind the mel layers (dmel_deltas_forward / dmel_deltas_backward, csrc/dmel_deltas.hip): rows x T fp32 on the input side of the
+// forward (s; the backward's ds), groups * rows x T on the other (y; the backward's g), clip = row / rows_per_clip
+struct DeltasParams {
+    const float* in; float* out;        // forward: s -> y; backward: g -> ds
+    const int* lengths;         // (rows / rows_per_clip) valid frames per clip; nullptr: T for every clip
+    long long rows, rows_per_clip;
+    int T, n, order, include_static, groups;    // n = (win_length - 1) / 2, groups = include_static + order
+    double inv_denom;           // 3 / (n (n + 1) (2 n + 1))
+    int logw, W, halo, step, chunks;    // set by the launcher
+};
+long long deltas_waves(long long rows, int T, int n);      // waves of a launch over `rows` rows of T frames
+hipError_t launch_deltas(DeltasParams p, bool backward, hipStream_t s);
+
 // Peer-to-peer all-reduce of the one scalar this path exchanges (d lambd), folded into the tail of the dot kernel: the workgroup
 // that draws the last ticket stores (step, local sum) as ONE 8-byte granule into slot `rank` of every rank's inbox -- peer memory
 // mapped over xGMI, system-scope stores -- then polls its own inbox until every rank's granule of this step has arrived and adds

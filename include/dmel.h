@@ -581,6 +581,36 @@ dmel_status dmel_specmask_apply(const void* s, int64_t rows, int32_t n_mels, int
                                 const int32_t* frame_lengths_or_null, const int32_t* stripes, int32_t n_time, int32_t n_freq,
                                 int32_t elem_bf16, float fill, void* y, void* stream);
 
+/* ---- Deltas: length-aware delta and delta-delta channels behind the mel layers (dmel_amd.Deltas; plan-free, as PCEN, BandNorm, SpecMask) --
+ * The "velocity" and "acceleration" channels of the mel image, with the stencil's replicate edge at each clip's OWN last valid frame (a
+ * stencil over a zero-padded batch reads log(1e-10) = -23.03 behind a short clip's last frame instead).  s is rows x n_time fp32, a row is
+ * one (clip, channel, band) triple of a contiguous (B, C, M, T) tensor: rows = B C M, rows_per_clip = C M, clip = row / rows_per_clip,
+ * Tc = frame_lengths[clip] (NULL: n_time).  win_length is 3, 5, 7 or 9, n = (win_length - 1) / 2, denom = n (n + 1) (2 n + 1) / 3
+ * (2, 10, 28, 60); order is 1 or 2.
+ *   for t <  Tc:   d[t]  = ( sum_{j = 1 .. n}  j * ( x[min(t + j, Tc - 1)] - x[max(t - j, 0)] ) ) / denom
+ *                  dd[t] = the same formula applied to the STORED fp32 row d[0 .. Tc - 1]
+ *   for t >= Tc:   d[t] = dd[t] = +0.0
+ * With Tc = n_time this is torchaudio.functional.compute_deltas(win_length, mode="replicate"), applied once and twice.  The antisymmetric
+ * form -- a difference first, j times it second -- is part of the specification: a constant row, Tc = 1 and a row of silent frames give
+ * +0.0 bit for bit in both channels.  Sums are fp32 or wider in a fixed order (here: fp64, scaled by 1 / denom, rounded to fp32 once); dd is
+ * formed from d as rounded to fp32, so dd is the call applied to its own d bit for bit.
+ * y has G = include_static + order groups per clip, in torch.cat([s, d, dd], dim=1) order: the output row of input row r in group o is
+ * (r / rows_per_clip) * G * rows_per_clip + o * rows_per_clip + r % rows_per_clip.  Group 0 is s moved as words when include_static = 1:
+ * every frame, pad frames, NaN payloads and -0.0 included; then d; then dd (order = 2).  s is never loaded at a pad frame for d and dd.
+ * A frame_lengths[b] outside 1 ... n_time makes every output row of clip b NaN, the static group included; other clips are untouched.
+ * dmel_deltas_backward: g is the cotangent of y (G rows x n_time per input row, the same layout), ds is rows x n_time.  With D the Tc x Tc
+ * matrix of the clamped stencil (out-of-range taps fold onto frames 0 and Tc - 1):  ds = g_static + D^T (g_d + D^T g_dd)  on t < Tc
+ * (g_static = 0 without include_static, g_dd = 0 with order = 1); on pad frames ds = g_static bit for bit, +0.0 without the static group;
+ * g_d and g_dd are never loaded at a pad frame; an invalid length gives a NaN clip.  Every ds[t] is gathered by its own lane: no atomics, two
+ * runs give the same bits.  The stage is linear: the backward needs frame_lengths only.
+ * s and g need their element's alignment only; y and ds must be 16-byte aligned.  One launch each, no host read, capturable; rows == 0 or
+ * n_time == 0: DMEL_OK, nothing is launched.  Refused with DMEL_ERR_INVALID_ARGUMENT before any device is touched: a NULL s, g, y or ds,
+ * rows_per_clip that does not divide rows, another win_length or order, a misaligned output.  Input and output must not overlap. */
+dmel_status dmel_deltas_forward(const float* s, int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null,
+                                int32_t win_length, int32_t order, int32_t include_static, float* y, void* stream);
+dmel_status dmel_deltas_backward(const float* g, int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null,
+                                 int32_t win_length, int32_t order, int32_t include_static, float* ds, void* stream);
+
 /* ---- the multi-window layer: K trainable window widths as K output channels (dmel_amd.MultiWindowMelSpectrogram) ------------------
  * Channel k of (batch, K, n_mels, n_time) is what dmel_forward* computes for lambd[k], bit for bit; 1 <= K <= 8, every channel's n_fft in
  * 32 ... 16384 (the fused kernel).  One launch per DISTINCT n_fft covers all the channels that need it.  out and tangent are (batch, K, M, T);
