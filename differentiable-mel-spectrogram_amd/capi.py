@@ -149,6 +149,8 @@ _SIGNATURES = {
     "dmel_specmask_apply": (status, [vp, i64, i32, i64, i32, vp, vp, i32, i32, i32, f32, vp, vp]),
     "dmel_deltas_forward": (status, [vp, i64, i64, i32, vp, i32, i32, i32, vp, vp]),
     "dmel_deltas_backward": (status, [vp, i64, i64, i32, vp, i32, i32, i32, vp, vp]),
+    "dmel_statspool_forward": (status, [vp, i64, i64, i32, vp, i32, f64, vp, vp, vp, vp]),
+    "dmel_statspool_backward": (status, [vp, vp, vp, vp, i64, i64, i32, vp, i32, vp, vp]),
     "dmel_scratch_bytes_multi": (C.c_size_t, [vp, i32, i32]),
     "dmel_forward_multi": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_multi_dev": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
@@ -338,6 +340,24 @@ def deltas_backward(g_ptr: int, rows: int, rows_per_clip: int, n_time_frames: in
     """dmel_deltas_backward: ds = g_static + D^T (g_d + D^T g_dd) from the cotangent of dmel_deltas_forward's y"""
     _check(load().dmel_deltas_backward(g_ptr or None, int(rows), int(rows_per_clip), int(n_time_frames), lengths_ptr or None, int(win_length),
                                        int(order), int(bool(include_static)), ds_ptr or None, stream))
+
+
+STATSPOOL_MEAN, STATSPOOL_STD, STATSPOOL_MAX = 1, 2, 4
+
+
+def statspool_forward(s_ptr: int, rows: int, rows_per_clip: int, n_time_frames: int, lengths_ptr: int | None, which: int, eps: float,
+                      y_ptr: int, stats_ptr: int | None, argmax_ptr: int | None, stream: int) -> None:
+    """dmel_statspool_forward: y = the groups [mean][, std][, max] (``which``: bits 1, 2, 4) of ``rows`` x ``n_time_frames`` fp32 values over
+    each clip's own valid frames; ``stats_ptr`` (2 * rows doubles) and ``argmax_ptr`` (rows int32) are what the backward reads"""
+    _check(load().dmel_statspool_forward(s_ptr or None, int(rows), int(rows_per_clip), int(n_time_frames), lengths_ptr or None, int(which),
+                                         C.c_double(float(eps)), y_ptr or None, stats_ptr or None, argmax_ptr or None, stream))
+
+
+def statspool_backward(g_ptr: int, s_ptr: int | None, stats_ptr: int | None, argmax_ptr: int | None, rows: int, rows_per_clip: int,
+                       n_time_frames: int, lengths_ptr: int | None, which: int, ds_ptr: int, stream: int) -> None:
+    """dmel_statspool_backward: ds = g_mean / Tc + g_std (s - mu) / (Tc sd) + [t == am] g_max from the cotangent of dmel_statspool_forward's y"""
+    _check(load().dmel_statspool_backward(g_ptr or None, s_ptr or None, stats_ptr or None, argmax_ptr or None, int(rows), int(rows_per_clip),
+                                          int(n_time_frames), lengths_ptr or None, int(which), ds_ptr or None, stream))
 
 
 def device_count() -> int:

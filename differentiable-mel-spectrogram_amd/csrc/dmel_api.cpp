@@ -3213,6 +3213,70 @@ dmel_status dmel_deltas_backward(const float* g, int64_t rows, int64_t rows_per_
                        ds, true, stream);
 }
 
+namespace {
+// what both directions of StatsPool check alike; *noop: nothing to do
+dmel_status statspool_check(const std::string& w, int64_t rows, int64_t rows_per_clip, int32_t T, const int32_t* lengths, int32_t which,
+                            const double* stats, const int32_t* argmax, bool* noop)
+{
+    if (rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_time out of range");
+    if (rows_per_clip < 1 || rows % rows_per_clip != 0)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows_per_clip must be positive and divide rows (clip = row / rows_per_clip)");
+    if (which < 1 || which > 7) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": which must lie in 1 ... 7 (bit 0 mean, bit 1 std, bit 2 max)");
+    if (lengths && (reinterpret_cast<uintptr_t>(lengths) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": frame_lengths must be int32 values");
+    if (stats && (reinterpret_cast<uintptr_t>(stats) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats must be a 16-byte aligned buffer of 2 * rows doubles");
+    if (argmax && (reinterpret_cast<uintptr_t>(argmax) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": argmax must be int32 values");
+    *noop = rows == 0 || T == 0;
+    if (!*noop && rows > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
+    return DMEL_OK;
+}
+}  // namespace
+
+dmel_status dmel_statspool_forward(const float* s, int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null,
+                                   int32_t which, double eps, float* y, double* stats_or_null, int32_t* argmax_or_null, void* stream)
+{
+    const std::string w("dmel_statspool_forward");
+    bool noop = false;
+    const dmel_status st = statspool_check(w, rows, rows_per_clip, n_time, frame_lengths_or_null, which, stats_or_null, argmax_or_null, &noop);
+    if (st != DMEL_OK) return st;
+    if (!s || (reinterpret_cast<uintptr_t>(s) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer of fp32 values");
+    if (!y || (reinterpret_cast<uintptr_t>(y) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": y must be a buffer of fp32 values");
+    if ((which & 2) && (!std::isfinite(eps) || !(eps > 0.0))) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": eps must be finite and > 0 when std is selected");
+    if (noop) return DMEL_OK;
+    const dmel_status sd = pcen_device("dmel_statspool_forward");
+    if (sd != DMEL_OK) return sd;
+    dmel::StatsPoolParams p{};
+    p.s = s; p.y = y; p.lengths = frame_lengths_or_null; p.stats = stats_or_null; p.argmax = argmax_or_null;
+    p.rows = rows; p.rows_per_clip = rows_per_clip; p.T = n_time; p.which = which; p.S = __builtin_popcount((unsigned)which);
+    p.eps = (std::isfinite(eps) && eps > 0.0) ? eps : 0.0;        // (without std an eps that was not checked can still reach `stats`: it must not be a NaN there)
+    DMEL_HIP(dmel::launch_statspool(p, false, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
+dmel_status dmel_statspool_backward(const float* g, const float* s_or_null, const double* stats_or_null, const int32_t* argmax_or_null,
+                                    int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null, int32_t which,
+                                    float* ds, void* stream)
+{
+    const std::string w("dmel_statspool_backward");
+    bool noop = false;
+    const dmel_status st = statspool_check(w, rows, rows_per_clip, n_time, frame_lengths_or_null, which, stats_or_null, argmax_or_null, &noop);
+    if (st != DMEL_OK) return st;
+    if (!g || (reinterpret_cast<uintptr_t>(g) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": g must be a buffer of fp32 values");
+    if (!ds || (reinterpret_cast<uintptr_t>(ds) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": ds must be a buffer of fp32 values");
+    if (s_or_null && (reinterpret_cast<uintptr_t>(s_or_null) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer of fp32 values");
+    if ((which & 2) && (!s_or_null || !stats_or_null))
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": std is selected: s and the stats the forward wrote are needed");
+    if ((which & 4) && !argmax_or_null) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": max is selected: the argmax the forward wrote is needed");
+    if (noop) return DMEL_OK;
+    const dmel_status sd = pcen_device("dmel_statspool_backward");
+    if (sd != DMEL_OK) return sd;
+    dmel::StatsPoolParams p{};
+    p.g = g; p.s = s_or_null; p.ds = ds; p.lengths = frame_lengths_or_null;
+    p.stats = const_cast<double*>(stats_or_null); p.argmax = const_cast<int32_t*>(argmax_or_null);
+    p.rows = rows; p.rows_per_clip = rows_per_clip; p.T = n_time; p.which = which; p.S = __builtin_popcount((unsigned)which);
+    DMEL_HIP(dmel::launch_statspool(p, true, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
 dmel_status dmel_plan_set_profiling(dmel_plan* plan, int32_t enable)
 {
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");

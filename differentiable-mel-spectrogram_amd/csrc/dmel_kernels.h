@@ -782,6 +782,24 @@ struct DeltasParams {
 long long deltas_waves(long long rows, int T, int n);      // waves of a launch over `rows` rows of T frames
 hipError_t launch_deltas(DeltasParams p, bool backward, hipStream_t s);
 
+// StatsPool behind the mel layers (dmel_statspool_forward / dmel_statspool_backward, csrc/dmel_statspool.hip): rows x T fp32 on the input
+// side (s; the backward's ds), S = popcount(which) groups of rows_per_clip values per clip on the other (y; the backward's g)
+struct StatsPoolParams {
+    const float* s;             // forward: input; backward: read only when std is selected
+    const float* g;             // backward: cotangent of y
+    float* y;                   // forward: (rows / rows_per_clip, S, rows_per_clip)
+    float* ds;                  // backward: (rows, T)
+    const int* lengths;         // (rows / rows_per_clip) valid frames per clip; nullptr: T for every clip
+    double* stats;              // (rows, 2) unrounded (mu, sd) pairs: forward writes (nullptr: not kept), backward reads
+    int* argmax;                // (rows) frame of the maximum, -1 for a clip with an invalid length: forward writes (nullptr: not kept), backward reads
+    long long rows, rows_per_clip;
+    int T, which, S;            // which: bit 0 mean, bit 1 std, bit 2 max
+    double eps;
+    int W, logw;                // set by the launcher: lanes per row (next power of two >= T up to 32 frames, else 64)
+};
+long long statspool_blocks(long long rows, int T);         // workgroups of a launch over the rows
+hipError_t launch_statspool(StatsPoolParams p, bool backward, hipStream_t s);
+
 // Peer-to-peer all-reduce of the one scalar this path exchanges (d lambd), folded into the tail of the dot kernel: the workgroup
 // that draws the last ticket stores (step, local sum) as ONE 8-byte granule into slot `rank` of every rank's inbox -- peer memory
 // mapped over xGMI, system-scope stores -- then polls its own inbox until every rank's granule of this step has arrived and adds

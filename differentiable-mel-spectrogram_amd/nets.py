@@ -93,6 +93,41 @@ class MelConvNet(_MelFrontNet):
         return self.fc2(F.relu(self.fc1(h))), s
 
 
+class MelPoolNet(nn.Module):
+    """The first net that takes a zero-padded batch: the mel layer over clips of per-clip lengths, ``dmel_amd.StatsPool`` over each clip's
+    own valid frames, one linear layer on the ``S * n_mels`` pooled values -- no frame of the padding reaches the head, so a clip's logits
+    do not depend on what it was batched with.  ``forward(x, lengths=None)`` returns ``(logits, s)``, ``s`` the image in front of the pool;
+    ``lengths=None`` means every clip is full.  Two opt-in attributes, both ``None`` by default and both called as ``(s, fl)`` with
+    ``fl = spectrogram_layer.frame_lengths(lengths)`` (``None`` for full clips): ``normalization`` (``dmel_amd.BandNorm``) and, behind it
+    and only while ``self.training``, ``augmentation`` (``dmel_amd.SpecMask``).  The layer is the scalar ``MelSpectrogramLayer`` with
+    ``optimized=True``, which takes ``lengths`` as it is; its parameter name ``spectrogram_layer.lambd`` keeps ``make_optimizer`` working."""
+
+    def __init__(self, n_classes, init_lambd, device, n_mels, sample_rate, n_points, hop_length=1, energy_normalize=True,
+                 normalize_window=False, stats=("mean", "std", "max")):
+        super().__init__()
+        from .statspool import StatsPool
+        self.spectrogram_layer = MelSpectrogramLayer(
+            init_lambd, n_mels=n_mels, n_points=n_points, sample_rate=sample_rate, hop_length=hop_length,
+            device=device, optimized=True, normalize_window=normalize_window, log=bool(energy_normalize))
+        self.pool = StatsPool(stats)
+        self.fc = nn.Linear(self.pool.groups * n_mels, n_classes)
+        self.device = device
+        self.size = (n_mels, n_points // hop_length + 1)
+        self.energy_normalize = energy_normalize
+        self.normalization = None
+        self.augmentation = None
+
+    def forward(self, x, lengths=None):
+        layer = self.spectrogram_layer
+        fl = None if lengths is None else layer.frame_lengths(lengths)
+        s = layer(x) if lengths is None else layer(x, lengths)
+        if self.normalization is not None:
+            s = self.normalization(s, fl)
+        if self.augmentation is not None and self.training:
+            s = self.augmentation(s, fl)
+        return self.fc(self.pool(s, fl).flatten(1)), s
+
+
 def make_optimizer(net: nn.Module, lr_model: float, lr_tf: float, name: str = "adam"):
     """The two learning-rate groups of main.py:36-53: ``lr_tf`` for ``spectrogram_layer.lambd``, ``lr_model`` for the rest."""
     groups = [{"params": [p], "lr": (lr_tf if n == "spectrogram_layer.lambd" else lr_model)} for n, p in net.named_parameters()]

@@ -611,6 +611,40 @@ dmel_status dmel_deltas_forward(const float* s, int64_t rows, int64_t rows_per_c
 dmel_status dmel_deltas_backward(const float* g, int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null,
                                  int32_t win_length, int32_t order, int32_t include_static, float* ds, void* stream);
 
+/* ---- StatsPool: length-aware mean / std / max pooling over time behind the mel layers (dmel_amd.StatsPool; plan-free, as Deltas) ----------
+ * The stage that ends the length-aware chain: (B, C, M, T) plus frame lengths become a fixed-size (B, S C, M) -- the "statistics pooling"
+ * of x-vector style heads -- from each row's own VALID frames only.  s is rows x n_time fp32, a row is one (clip, channel, band) triple of
+ * a contiguous (B, C, M, T) tensor: rows = B C M, rows_per_clip = C M, clip = row / rows_per_clip, Tc = frame_lengths[clip] (NULL: n_time).
+ * `which` selects the statistics: bit 0 mean, bit 1 std, bit 2 max; 1 ... 7; S = popcount(which).  For 1 <= Tc <= n_time:
+ *   mean   mu = (sum_{t < Tc} s[t]) / Tc, the sum and the quotient in fp64, rounded to fp32 once for y
+ *   std    sd = sqrt(m2 / Tc + eps),  m2 = sum_{t < Tc} (s[t] - mu)^2: the mean first, the squared deviations from the UNROUNDED fp64 mu
+ *          second (never E[x^2] - mu^2); the biased variance, as in BandNorm; all in fp64, rounded once.  eps > 0 keeps the gradient finite
+ *          on a constant row.  A constant row and Tc = 1 give exactly (float)sqrt((double)eps): the fp64 sum of Tc equal fp32 values and
+ *          its quotient by Tc are exact
+ *   max    s[am] moved as a word, am chosen by an order that is associative and commutative (the reduction tree cannot change it): a NaN
+ *          beats a non-NaN; then the larger value wins; then the lower t wins -- -0.0 and +0.0 tie, so the lower t's bits are stored
+ * y has S groups per clip in the fixed order mean, std, max -- torch.cat([mean, std, max], dim=1) of three (B, C, M) tensors: the element of
+ * input row r in group o is (r / rows_per_clip) * S * rows_per_clip + o * rows_per_clip + r % rows_per_clip (Deltas' group layout).
+ * stats_or_null: 2 * rows doubles, the unrounded pairs (mu, sd), 16-byte aligned; argmax_or_null: rows int32 values am (-1 for a clip with
+ * an invalid length); each is written when it is not NULL, whatever `which` selects (without std, sd is formed with eps where eps > 0, else 0).
+ * s is never loaded at a pad frame, and a 64-frame chunk without a valid frame is not visited.  A frame_lengths[b] outside 1 ... n_time makes
+ * every output element of clip b NaN; other clips are untouched.  Sums run in a fixed order, no atomics: the same inputs give the same bits,
+ * and a row's result depends on its own Tc values and (n_time, Tc) only, not on where the row sits in the launch.
+ * dmel_statspool_backward: g has y's layout, ds is rows x n_time.  On t < Tc
+ *   ds[t] = g_mean / Tc + g_std (s[t] - mu) / (Tc sd) + [t == am] g_max
+ * in fp64 from the stored (mu, sd) and am, rounded once; a group that is not selected contributes nothing; ds = +0.0 on pad frames; an
+ * invalid length gives a NaN clip.  s is read only when std is selected and never at a pad frame.  With std alone a constant row gives
+ * ds == 0 everywhere.  Element-wise: no reduction.
+ * s, g, y and ds need their element's alignment only.  One launch each, no host read, capturable; rows == 0 or n_time == 0: DMEL_OK,
+ * nothing is launched.  Refused with DMEL_ERR_INVALID_ARGUMENT before any device is touched: a NULL s, g, y or ds, rows_per_clip that does
+ * not divide rows, `which` outside 1 ... 7, eps <= 0 or NaN when std is selected, a misaligned stats, a backward that selects std without
+ * s and stats or max without argmax. */
+dmel_status dmel_statspool_forward(const float* s, int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null,
+                                   int32_t which, double eps, float* y, double* stats_or_null, int32_t* argmax_or_null, void* stream);
+dmel_status dmel_statspool_backward(const float* g, const float* s_or_null, const double* stats_or_null, const int32_t* argmax_or_null,
+                                    int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null, int32_t which,
+                                    float* ds, void* stream);
+
 /* ---- the multi-window layer: K trainable window widths as K output channels (dmel_amd.MultiWindowMelSpectrogram) ------------------
  * Channel k of (batch, K, n_mels, n_time) is what dmel_forward* computes for lambd[k], bit for bit; 1 <= K <= 8, every channel's n_fft in
  * 32 ... 16384 (the fused kernel).  One launch per DISTINCT n_fft covers all the channels that need it.  out and tangent are (batch, K, M, T);
