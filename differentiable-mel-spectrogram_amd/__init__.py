@@ -11,8 +11,8 @@ from __future__ import annotations
 
 import importlib
 
-__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "PCEN", "BandNorm", "SpecMask", "Deltas", "StatsPool", "capi", "synth", "dist",
-           "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask", "deltas", "statspool"]
+__all__ = ["MelSpectrogramLayer", "MultiWindowMelSpectrogram", "BandSplitMelSpectrogram", "DifferentiableMelSpectrogram", "SpectrogramLayer", "SlotInput", "dmel_log_mel", "GraphedStep", "LambdAdam", "PCEN", "BandNorm", "SpecMask", "Deltas", "StatsPool", "AttentivePool", "capi", "synth", "dist",
+           "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask", "deltas", "statspool", "attnpool"]
 
 _LAZY = {
     "MelSpectrogramLayer": ("layer", "MelSpectrogramLayer"),
@@ -29,6 +29,7 @@ _LAZY = {
     "SpecMask": ("specmask", "SpecMask"),
     "Deltas": ("deltas", "Deltas"),
     "StatsPool": ("statspool", "StatsPool"),
+    "AttentivePool": ("attnpool", "AttentivePool"),
 }
 
 
@@ -36,6 +37,6 @@ def __getattr__(name):
     if name in _LAZY:
         mod, attr = _LAZY[name]
         return getattr(importlib.import_module(f"dmel_amd.{mod}"), attr)
-    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask", "deltas", "statspool"):
+    if name in ("capi", "synth", "layer", "dist", "nets", "panns", "graph", "optim", "pcen", "bandnorm", "specmask", "deltas", "statspool", "attnpool"):
         return importlib.import_module(f"dmel_amd.{name}")
     raise AttributeError(name)

@@ -151,6 +151,8 @@ _SIGNATURES = {
     "dmel_deltas_backward": (status, [vp, i64, i64, i32, vp, i32, i32, i32, vp, vp]),
     "dmel_statspool_forward": (status, [vp, i64, i64, i32, vp, i32, f64, vp, vp, vp, vp]),
     "dmel_statspool_backward": (status, [vp, vp, vp, vp, i64, i64, i32, vp, i32, vp, vp]),
+    "dmel_attnpool_forward": (status, [vp, vp, i64, i64, i64, i32, vp, i32, f64, vp, vp, vp, vp]),
+    "dmel_attnpool_backward": (status, [vp, vp, vp, vp, vp, i64, i64, i64, i32, vp, i32, f64, vp, vp, vp]),
     "dmel_scratch_bytes_multi": (C.c_size_t, [vp, i32, i32]),
     "dmel_forward_multi": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
     "dmel_forward_multi_dev": (status, [vp, vp, i32, vp, i32, u32, f64, vp, vp, vp, vp]),
@@ -358,6 +360,29 @@ def statspool_backward(g_ptr: int, s_ptr: int | None, stats_ptr: int | None, arg
     """dmel_statspool_backward: ds = g_mean / Tc + g_std (s - mu) / (Tc sd) + [t == am] g_max from the cotangent of dmel_statspool_forward's y"""
     _check(load().dmel_statspool_backward(g_ptr or None, s_ptr or None, stats_ptr or None, argmax_ptr or None, int(rows), int(rows_per_clip),
                                           int(n_time_frames), lengths_ptr or None, int(which), ds_ptr or None, stream))
+
+
+ATTNPOOL_MEAN, ATTNPOOL_STD = 1, 2
+
+
+def attnpool_forward(s_ptr: int, a_ptr: int, rows: int, rows_per_clip: int, logit_rows_per_clip: int, n_time_frames: int,
+                     lengths_ptr: int | None, which: int, eps: float, y_ptr: int, stats_ptr: int | None, norm_ptr: int | None, stream: int) -> None:
+    """dmel_attnpool_forward: y = the groups [mean][, std] (``which``: bits 1, 2) of ``rows`` x ``n_time_frames`` fp32 values under the softmax
+    of each clip's ``logit_rows_per_clip`` logit rows over its own valid frames; ``stats_ptr`` (2 * rows doubles: mu, var) and ``norm_ptr``
+    (2 doubles per logit row: m, Z) are what the backward reads"""
+    _check(load().dmel_attnpool_forward(s_ptr or None, a_ptr or None, int(rows), int(rows_per_clip), int(logit_rows_per_clip), int(n_time_frames),
+                                        lengths_ptr or None, int(which), C.c_double(float(eps)), y_ptr or None, stats_ptr or None,
+                                        norm_ptr or None, stream))
+
+
+def attnpool_backward(g_ptr: int, s_ptr: int, a_ptr: int, stats_ptr: int, norm_ptr: int, rows: int, rows_per_clip: int,
+                      logit_rows_per_clip: int, n_time_frames: int, lengths_ptr: int | None, which: int, eps: float, ds_ptr: int, da_ptr: int,
+                      stream: int) -> None:
+    """dmel_attnpool_backward: ds = w (g_mean + g_std d / sd) and da = w sum_r (g_mean d + g_std (d^2 - var) / (2 sd)), d = s - mu, from the
+    cotangent of dmel_attnpool_forward's y and the pairs it stored (``eps``: the forward's)"""
+    _check(load().dmel_attnpool_backward(g_ptr or None, s_ptr or None, a_ptr or None, stats_ptr or None, norm_ptr or None, int(rows),
+                                         int(rows_per_clip), int(logit_rows_per_clip), int(n_time_frames), lengths_ptr or None, int(which),
+                                         C.c_double(float(eps)), ds_ptr or None, da_ptr or None, stream))
 
 
 def device_count() -> int:

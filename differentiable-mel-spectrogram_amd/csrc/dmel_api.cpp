@@ -3277,6 +3277,85 @@ dmel_status dmel_statspool_backward(const float* g, const float* s_or_null, cons
     return DMEL_OK;
 }
 
+namespace {
+// what both directions of AttentivePool check alike; *noop: nothing to do
+dmel_status attnpool_check(const std::string& w, const float* s, const float* a, int64_t rows, int64_t rows_per_clip, int64_t logit_rows,
+                           int32_t T, const int32_t* lengths, int32_t which, double eps, const double* stats, const double* norm, bool* noop)
+{
+    if (rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_time out of range");
+    if (rows_per_clip < 1 || rows % rows_per_clip != 0)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows_per_clip must be positive and divide rows (clip = row / rows_per_clip)");
+    if (logit_rows < 1 || rows_per_clip % logit_rows != 0)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": logit_rows_per_clip must be positive and divide rows_per_clip (row r reads logit row r / (rows_per_clip / logit_rows_per_clip))");
+    if (which < 1 || which > 3) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": which must lie in 1 ... 3 (bit 0 mean, bit 1 std)");
+    if ((which & 2) && (!std::isfinite(eps) || !(eps > 0.0))) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": eps must be finite and > 0 when std is selected");
+    if (lengths && (reinterpret_cast<uintptr_t>(lengths) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": frame_lengths must be int32 values");
+    if (!s || (reinterpret_cast<uintptr_t>(s) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer of fp32 values");
+    if (!a || (reinterpret_cast<uintptr_t>(a) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": a must be a buffer of fp32 logits");
+    if (stats && (reinterpret_cast<uintptr_t>(stats) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats must be a 16-byte aligned buffer of 2 * rows doubles");
+    if (norm && (reinterpret_cast<uintptr_t>(norm) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": norm must be a 16-byte aligned buffer of 2 doubles per logit row");
+    if (!stats != !norm) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats and norm must both be given or both be NULL");
+    *noop = rows == 0 || T == 0;
+    if (!*noop && rows > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
+    return DMEL_OK;
+}
+
+dmel::AttnPoolParams attnpool_params(const float* s, const float* a, int64_t rows, int64_t rows_per_clip, int64_t logit_rows, int32_t T,
+                                     const int32_t* lengths, int32_t which, double eps, const double* stats, const double* norm)
+{
+    dmel::AttnPoolParams p{};
+    p.s = s; p.a = a; p.lengths = lengths; p.stats = const_cast<double*>(stats); p.norm = const_cast<double*>(norm);
+    p.rows = rows; p.rows_per_clip = rows_per_clip; p.logit_rows = logit_rows; p.T = T; p.which = which;
+    p.S = __builtin_popcount((unsigned)which);
+    p.eps = (std::isfinite(eps) && eps > 0.0) ? eps : 0.0;        // (without std an eps that was not checked must not be a NaN in the kernels)
+    return p;
+}
+}  // namespace
+
+dmel_status dmel_attnpool_forward(const float* s, const float* a, int64_t rows, int64_t rows_per_clip, int64_t logit_rows_per_clip,
+                                  int32_t n_time, const int32_t* frame_lengths_or_null, int32_t which, double eps, float* y,
+                                  double* stats_or_null, double* norm_or_null, void* stream)
+{
+    const std::string w("dmel_attnpool_forward");
+    bool noop = false;
+    const dmel_status st = attnpool_check(w, s, a, rows, rows_per_clip, logit_rows_per_clip, n_time, frame_lengths_or_null, which, eps,
+                                          stats_or_null, norm_or_null, &noop);
+    if (st != DMEL_OK) return st;
+    if (!y || (reinterpret_cast<uintptr_t>(y) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": y must be a buffer of fp32 values");
+    if (noop) return DMEL_OK;
+    const dmel_status sd = pcen_device("dmel_attnpool_forward");
+    if (sd != DMEL_OK) return sd;
+    dmel::AttnPoolParams p = attnpool_params(s, a, rows, rows_per_clip, logit_rows_per_clip, n_time, frame_lengths_or_null, which, eps,
+                                             stats_or_null, norm_or_null);
+    p.y = y;
+    DMEL_HIP(dmel::launch_attnpool(p, false, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
+dmel_status dmel_attnpool_backward(const float* g, const float* s, const float* a, const double* stats, const double* norm, int64_t rows,
+                                   int64_t rows_per_clip, int64_t logit_rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null,
+                                   int32_t which, double eps, float* ds, float* da, void* stream)
+{
+    const std::string w("dmel_attnpool_backward");
+    bool noop = false;
+    const dmel_status st = attnpool_check(w, s, a, rows, rows_per_clip, logit_rows_per_clip, n_time, frame_lengths_or_null, which, eps,
+                                          stats, norm, &noop);
+    if (st != DMEL_OK) return st;
+    if (!g || (reinterpret_cast<uintptr_t>(g) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": g must be a buffer of fp32 values");
+    if (!ds || (reinterpret_cast<uintptr_t>(ds) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": ds must be a buffer of fp32 values");
+    if (!da || (reinterpret_cast<uintptr_t>(da) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": da must be a buffer of fp32 values");
+    if (!stats || !norm) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": the stats and norm the forward wrote are needed");
+    if (noop) return DMEL_OK;
+    if (dmel::attnpool_blocks(rows, rows_per_clip, logit_rows_per_clip, n_time, true) > 0x7FFFFFFFLL)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
+    const dmel_status sd = pcen_device("dmel_attnpool_backward");
+    if (sd != DMEL_OK) return sd;
+    dmel::AttnPoolParams p = attnpool_params(s, a, rows, rows_per_clip, logit_rows_per_clip, n_time, frame_lengths_or_null, which, eps, stats, norm);
+    p.g = g; p.ds = ds; p.da = da;
+    DMEL_HIP(dmel::launch_attnpool(p, true, reinterpret_cast<hipStream_t>(stream)));
+    return DMEL_OK;
+}
+
 dmel_status dmel_plan_set_profiling(dmel_plan* plan, int32_t enable)
 {
     if (!plan) return fail(DMEL_ERR_INVALID_ARGUMENT, "plan is NULL");

@@ -800,6 +800,29 @@ struct StatsPoolParams {
 long long statspool_blocks(long long rows, int T);         // workgroups of a launch over the rows
 hipError_t launch_statspool(StatsPoolParams p, bool backward, hipStream_t s);
 
+// AttentivePool behind the mel layers (dmel_attnpool_forward / dmel_attnpool_backward, csrc/dmel_attnpool.hip): rows x T fp32 (s; the
+// backward's ds), A = logit_rows_per_clip rows of T logits per clip (a; the backward's da), S = popcount(which) groups of rows_per_clip
+// values per clip on the pooled side (y; the backward's g).  Row r of a clip reads logit row r / group, group = rows_per_clip / A
+struct AttnPoolParams {
+    const float* s;             // (rows, T)
+    const float* a;             // (rows / rows_per_clip * A, T) logits
+    const float* g;             // backward: cotangent of y
+    float* y;                   // forward: (rows / rows_per_clip, S, rows_per_clip)
+    float* ds;                  // backward: (rows, T)
+    float* da;                  // backward: (rows / rows_per_clip * A, T)
+    const int* lengths;         // (rows / rows_per_clip) valid frames per clip; nullptr: T for every clip
+    double* stats;              // (rows, 2) unrounded (mu, var) pairs: forward writes (nullptr: not kept), backward reads
+    double* norm;               // (rows / rows_per_clip * A, 2) (m, Z) of every logit row: forward writes (nullptr: not kept), backward reads
+    long long rows, rows_per_clip, logit_rows, group;    // logit_rows = A; group = rows_per_clip / A
+    int T, which, S;            // which: bit 0 mean, bit 1 std
+    double eps;
+    int W, logw;                // forward, set by the launcher: lanes per row (next power of two >= T up to 32 frames, else 64)
+    int chunks, logsplit;       // backward, set by the launcher: 64-frame chunks of a row; log2 of the waves that share an owner's rows (0 ... 4)
+    long long owners;           // backward, set by the launcher: (clip, logit row, chunk) triples
+};
+long long attnpool_blocks(long long rows, long long rows_per_clip, long long logit_rows, int T, bool backward);      // workgroups of a launch
+hipError_t launch_attnpool(AttnPoolParams p, bool backward, hipStream_t s);
+
 // Peer-to-peer all-reduce of the one scalar this path exchanges (d lambd), folded into the tail of the dot kernel: the workgroup
 // that draws the last ticket stores (step, local sum) as ONE 8-byte granule into slot `rank` of every rank's inbox -- peer memory
 // mapped over xGMI, system-scope stores -- then polls its own inbox until every rank's granule of this step has arrived and adds

@@ -128,6 +128,47 @@ class MelPoolNet(nn.Module):
         return self.fc(self.pool(s, fl).flatten(1)), s
 
 
+class MelAttnPoolNet(nn.Module):
+    """``MelPoolNet`` with ``dmel_amd.AttentivePool`` in the pool's place and a per-frame scorer of stock torch modules in front of it:
+    ``attention_fc1 = Conv1d(n_mels, attention_hidden, 1)``, tanh, ``attention_fc2 = Conv1d(attention_hidden, A, 1)`` on ``s[:, 0]`` (behind
+    ``normalization`` and ``augmentation``); ``attention="shared"`` is one attention for the clip (``A = 1``), ``"band"`` one per mel band
+    (``A = n_mels``).  The scorer's kernel size is 1 on purpose: a frame's logit depends on that frame alone, so pad frames reach the scorer
+    and stop at the pool -- they cannot leak into valid frames through a context window.  ``forward(x, lengths=None)`` returns
+    ``(logits, s)``; ``normalization`` and ``augmentation`` are opt-in exactly as on ``MelPoolNet``; the parameter name
+    ``spectrogram_layer.lambd`` keeps ``make_optimizer`` working."""
+
+    def __init__(self, n_classes, init_lambd, device, n_mels, sample_rate, n_points, hop_length=1, energy_normalize=True,
+                 normalize_window=False, stats=("mean", "std"), attention="shared", attention_hidden=32):
+        super().__init__()
+        from .attnpool import AttentivePool
+        if attention not in ("shared", "band"):
+            raise ValueError(f"MelAttnPoolNet: attention must be 'shared' or 'band', got {attention!r}")
+        self.spectrogram_layer = MelSpectrogramLayer(
+            init_lambd, n_mels=n_mels, n_points=n_points, sample_rate=sample_rate, hop_length=hop_length,
+            device=device, optimized=True, normalize_window=normalize_window, log=bool(energy_normalize))
+        self.attention = attention
+        self.attention_fc1 = nn.Conv1d(n_mels, attention_hidden, 1)
+        self.attention_fc2 = nn.Conv1d(attention_hidden, 1 if attention == "shared" else n_mels, 1)
+        self.pool = AttentivePool(stats)
+        self.fc = nn.Linear(self.pool.groups * n_mels, n_classes)
+        self.device = device
+        self.size = (n_mels, n_points // hop_length + 1)
+        self.energy_normalize = energy_normalize
+        self.normalization = None
+        self.augmentation = None
+
+    def forward(self, x, lengths=None):
+        layer = self.spectrogram_layer
+        fl = None if lengths is None else layer.frame_lengths(lengths)
+        s = layer(x) if lengths is None else layer(x, lengths)
+        if self.normalization is not None:
+            s = self.normalization(s, fl)
+        if self.augmentation is not None and self.training:
+            s = self.augmentation(s, fl)
+        a = self.attention_fc2(torch.tanh(self.attention_fc1(s[:, 0])))
+        return self.fc(self.pool(s, a, fl).flatten(1)), s
+
+
 def make_optimizer(net: nn.Module, lr_model: float, lr_tf: float, name: str = "adam"):
     """The two learning-rate groups of main.py:36-53: ``lr_tf`` for ``spectrogram_layer.lambd``, ``lr_model`` for the rest."""
     groups = [{"params": [p], "lr": (lr_tf if n == "spectrogram_layer.lambd" else lr_model)} for n, p in net.named_parameters()]

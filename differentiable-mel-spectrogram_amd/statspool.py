@@ -22,7 +22,7 @@ int32 ``argmax`` when max is selected, and the lengths; under ``torch.no_grad()`
 ``1 ... T`` makes that clip NaN, as in the stages in front.  No parameters, no buffers; the same in ``train()`` and ``eval()``; no host read,
 capturable.
 
-Out of scope here: bf16; per-frame weights (attentive pooling); the unbiased variance; pooling over bands; double backward; fusing the
+Out of scope here: bf16; per-frame weights (``dmel_amd.AttentivePool`` is that stage); the unbiased variance; pooling over bands; double backward; fusing the
 stage into BandNorm or Deltas; a CPU fallback.
 """
 from __future__ import annotations

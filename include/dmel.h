@@ -645,6 +645,51 @@ dmel_status dmel_statspool_backward(const float* g, const float* s_or_null, cons
                                     int64_t rows, int64_t rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null, int32_t which,
                                     float* ds, void* stream);
 
+/* ---- AttentivePool: length-aware attentive statistics pooling over time behind the mel layers (dmel_amd.AttentivePool; plan-free) ---------
+ * The x-vector / ECAPA "attentive statistics pooling" with a softmax that knows the lengths: a scorer of the caller's gives every frame a
+ * logit, a softmax over the clip's VALID frames turns logits into weights, and the clip vector is the weighted mean and the weighted standard
+ * deviation.  (torch.softmax(a, -1) over a zero-padded batch hands every pad frame a share of the weight.)
+ * Inputs   s: contiguous (B, C, M, T) fp32 seen as rows = B C M rows of n_time frames, R = rows_per_clip = C M rows per clip;
+ *          a: contiguous (B, A, T) fp32 logits, A = logit_rows_per_clip >= 1 divides R, and row r of a clip reads logit row r / (R / A):
+ *             A = 1 one attention for the whole clip, A = C one per channel, A = R one per band (ECAPA's channel-dependent form);
+ *          Tc = frame_lengths[clip] (NULL: n_time), clip = row / R;
+ *          which: bit 0 mean, bit 1 std; 1 ... 3; S = popcount(which);  eps finite and > 0, asked for only when std is selected.
+ * Per (clip, logit row), over t < Tc only:
+ *          m = max a[t];  p[t] = exp((double)a[t] - (double)m);  Z = sum p[t];  w[t] = p[t] / Z
+ * Per row: mu  = (sum p[t] s[t]) / Z            evaluated around the row's first frame, s[0] + (sum p[t] (s[t] - s[0])) / Z: the same
+ *                                              number, and a constant row has mu == c and var == 0 exactly in fp64 as well
+ *          var = (sum p[t] (s[t] - mu)^2) / Z      the mean first, the deviations from the UNROUNDED fp64 mu second
+ *          sd  = sqrt(var + eps)
+ * Sums are in fp64; each of mean and std is rounded to fp32 once.
+ * Output   y is (B, S C, M) in torch.cat([mean, std], dim=1) order: the element of input row r in group o is
+ *          (r / R) * S * R + o * R + r % R (StatsPool's group layout).
+ * Optional outputs, needed only when a backward will run, both given or both NULL, both 16-byte aligned:
+ *          stats: (rows, 2) fp64, the pairs (mu, var) -- var, not sd: the backward needs var, and sd^2 - eps cancels;
+ *          norm:  (B A, 2) fp64, the pairs (m, Z).
+ * dmel_attnpool_backward, from g (y's layout), s, a, stats and norm; with d = s[t] - mu, on t < Tc:
+ *          ds[r, t] = w[t] (g_mean[r] + g_std[r] d / sd[r])
+ *          da[t]    = w[t] sum_{r in the logit row's group} (g_mean[r] d + g_std[r] (d^2 - var[r]) / (2 sd[r]))
+ * da is the softmax Jacobian with its mean term sum_u w[u] q[u] taken in closed form from the stored pairs (sum_u w[u] d[u] = 0 and
+ * sum_u w[u] d[u]^2 = var): no second reduction over frames.  Both in fp64, rounded once; w[t] is recomputed as exp(a[t] - m) / Z;
+ * sd = sqrt(var + eps) from the stored var and the eps of the forward, which the backward therefore takes as well; the g of a statistic
+ * that is not selected is not read.
+ * Rules shared with the stages in front: s, a and g are never loaded at a pad frame; ds and da are +0.0 on every pad frame; a 64-frame chunk
+ * without a valid frame is not visited; a frame_lengths[b] outside 1 ... n_time makes every element of clip b NaN in y, ds, da, stats and
+ * norm, and other clips keep their bits; lengths are read on the device only; no host read, no atomics; two runs give the same bits; a
+ * clip's bits do not depend on what it is batched with; rows are limited to 2^31 - 1 per launch.  A row that is a constant c over its
+ * valid frames gives mean == c and std == (float)sqrt((double)eps) bit for bit.  A valid frame whose logit is -inf, next to finite logits,
+ * has weight exactly 0 and ds, da of exactly zero there; other non-finite logits follow IEEE through the formulas and are not specified.
+ * s, a, g, y, ds and da need their element's alignment only.  One launch each, capturable; rows == 0 or n_time == 0: DMEL_OK, nothing is
+ * launched.  Refused with DMEL_ERR_INVALID_ARGUMENT before any device is touched: a NULL or misaligned s, a, g, y, ds or da,
+ * rows_per_clip that does not divide rows, logit_rows_per_clip that does not divide rows_per_clip, `which` outside 1 ... 3, eps <= 0 or
+ * NaN when std is selected, a misaligned stats or norm, one of the two without the other, a backward without them. */
+dmel_status dmel_attnpool_forward(const float* s, const float* a, int64_t rows, int64_t rows_per_clip, int64_t logit_rows_per_clip,
+                                  int32_t n_time, const int32_t* frame_lengths_or_null, int32_t which, double eps, float* y,
+                                  double* stats_or_null, double* norm_or_null, void* stream);
+dmel_status dmel_attnpool_backward(const float* g, const float* s, const float* a, const double* stats, const double* norm, int64_t rows,
+                                   int64_t rows_per_clip, int64_t logit_rows_per_clip, int32_t n_time, const int32_t* frame_lengths_or_null,
+                                   int32_t which, double eps, float* ds, float* da, void* stream);
+
 /* ---- the multi-window layer: K trainable window widths as K output channels (dmel_amd.MultiWindowMelSpectrogram) ------------------
  * Channel k of (batch, K, n_mels, n_time) is what dmel_forward* computes for lambd[k], bit for bit; 1 <= K <= 8, every channel's n_fft in
  * 32 ... 16384 (the fused kernel).  One launch per DISTINCT n_fft covers all the channels that need it.  out and tangent are (batch, K, M, T);
