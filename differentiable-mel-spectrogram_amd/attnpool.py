@@ -28,12 +28,11 @@ BandNorm into the stage; a CPU fallback.
 """
 from __future__ import annotations
 
-import math
-
 import torch
 import torch.nn as nn
 
-from . import capi
+from . import _stage, capi
+from ._stage import ptr
 
 STATS = ("mean", "std")                # the canonical order: the order of the output's groups; bit i of ``which`` selects STATS[i]
 
@@ -48,10 +47,8 @@ class _AttentivePoolFunction(torch.autograd.Function):
         y = torch.empty((B, S * C, M), dtype=s.dtype, device=s.device)
         stats = torch.empty((rows, 2), dtype=torch.float64, device=s.device) if keep else None
         norm = torch.empty((B * A, 2), dtype=torch.float64, device=s.device) if keep else None
-        with torch.cuda.device(s.device):
-            capi.attnpool_forward(s.data_ptr(), a.data_ptr(), rows, C * M, A, T, None if lengths is None else lengths.data_ptr(), which, eps,
-                                  y.data_ptr(), None if stats is None else stats.data_ptr(), None if norm is None else norm.data_ptr(),
-                                  torch.cuda.current_stream(s.device).cuda_stream)
+        _stage.launch(capi.attnpool_forward, s, s.data_ptr(), a.data_ptr(), rows, C * M, A, T, ptr(lengths), which, eps, y.data_ptr(), ptr(stats),
+                      ptr(norm))
         if keep:
             ctx.save_for_backward(s, a, stats, norm, lengths)
         ctx.which, ctx.eps = which, eps
@@ -62,15 +59,11 @@ class _AttentivePoolFunction(torch.autograd.Function):
         if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             return (None,) * 6
         s, a, stats, norm, lengths = ctx.saved_tensors
-        if g.dtype != torch.float32:
-            raise RuntimeError(f"AttentivePool: the gradient of the output must be fp32, got {g.dtype}")
-        g = g.contiguous()
+        g = _stage.cotangent("AttentivePool", g)
         B, C, M, T = s.shape
         ds, da = torch.empty_like(s), torch.empty_like(a)
-        with torch.cuda.device(g.device):
-            capi.attnpool_backward(g.data_ptr(), s.data_ptr(), a.data_ptr(), stats.data_ptr(), norm.data_ptr(), B * C * M, C * M, a.shape[1], T,
-                                   None if lengths is None else lengths.data_ptr(), ctx.which, ctx.eps, ds.data_ptr(), da.data_ptr(),
-                                   torch.cuda.current_stream(g.device).cuda_stream)
+        _stage.launch(capi.attnpool_backward, g, g.data_ptr(), s.data_ptr(), a.data_ptr(), stats.data_ptr(), norm.data_ptr(), B * C * M, C * M,
+                      a.shape[1], T, ptr(lengths), ctx.which, ctx.eps, ds.data_ptr(), da.data_ptr())
         return (ds if ctx.needs_input_grad[0] else None, da if ctx.needs_input_grad[1] else None) + (None,) * 4
 
 
@@ -83,20 +76,7 @@ class AttentivePool(nn.Module):
 
     def __init__(self, stats=("mean", "std"), eps: float = 1e-5):
         super().__init__()
-        if isinstance(stats, str):
-            stats = (stats,)
-        try:
-            given = list(stats)
-        except TypeError:
-            raise ValueError(f"AttentivePool: stats must be a non-empty subset of {STATS}, got {stats!r}") from None
-        if not given or any(not isinstance(k, str) or k not in STATS for k in given):
-            raise ValueError(f"AttentivePool: stats must be a non-empty subset of {STATS}, got {stats!r}")
-        if len(set(given)) != len(given):
-            raise ValueError(f"AttentivePool: stats names a statistic twice: {stats!r}")
-        if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not math.isfinite(eps) or not eps > 0:
-            raise ValueError(f"AttentivePool: eps must be a finite number > 0, got {eps!r}")
-        self.stats = tuple(k for k in STATS if k in given)
-        self.eps = float(eps)
+        self.stats, self.eps = _stage.pool_stats("AttentivePool", STATS, stats, eps)
 
     @property
     def which(self) -> int:
@@ -110,22 +90,6 @@ class AttentivePool(nn.Module):
 
     def extra_repr(self) -> str:
         return f"stats={self.stats}, eps={self.eps}"
-
-    def _lengths(self, s, frame_lengths):
-        """shape, dtype and device of ``frame_lengths``; returns them as the kernels read them (int32, contiguous).  Their values never
-        leave the device."""
-        if not torch.is_tensor(frame_lengths):
-            raise TypeError(f"AttentivePool: frame_lengths must be a 1-D integer tensor, got {type(frame_lengths).__name__}")
-        if frame_lengths.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"AttentivePool: frame_lengths must hold int32 or int64 values, got {frame_lengths.dtype}")
-        if frame_lengths.dim() != 1 or frame_lengths.shape[0] != s.shape[0]:
-            raise ValueError(f"AttentivePool: frame_lengths must have shape ({s.shape[0]},), got {tuple(frame_lengths.shape)}")
-        if frame_lengths.device != s.device:
-            raise RuntimeError(f"AttentivePool: frame_lengths is on {frame_lengths.device} but the input is on {s.device}")
-        if frame_lengths.dtype != torch.int32:
-            # int64 values clamped on the device before the narrowing: 2**32 + 5 must stay invalid (NaN), not wrap to 5
-            frame_lengths = frame_lengths.clamp(0, s.shape[-1] + 1).to(torch.int32)
-        return frame_lengths.contiguous()
 
     @staticmethod
     def _logits(s, logits):
@@ -150,20 +114,14 @@ class AttentivePool(nn.Module):
         return a
 
     def forward(self, s: torch.Tensor, logits: torch.Tensor, frame_lengths: torch.Tensor | None = None) -> torch.Tensor:
-        if not torch.is_tensor(s) or s.dim() not in (3, 4):
-            raise ValueError(f"AttentivePool: expected a (B, n_mels, T) or (B, C, n_mels, T) tensor, got {tuple(s.shape) if torch.is_tensor(s) else type(s).__name__}")
-        if s.dtype != torch.float32:
-            raise RuntimeError(f"AttentivePool takes an fp32 mel image, got {s.dtype}")
-        lengths = None if frame_lengths is None else self._lengths(s, frame_lengths)
-        if s.dim() == 3:
-            s = s.unsqueeze(1)
+        s = _stage.mel_image("AttentivePool", s)
+        lengths = _stage.frame_lengths_for_kernels("AttentivePool", s, frame_lengths)
         a = self._logits(s, logits)
         B, C, M, T = s.shape
         if B * C * M == 0:
             return s.new_empty((B, self.groups * C, M))
         if T == 0:
             raise ValueError("AttentivePool: the input has no frames (T = 0): there is nothing to pool")
-        if not s.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: AttentivePool's input must be a CUDA/HIP tensor (no CPU fallback)")
+        _stage.require_gpu("AttentivePool", s)
         keep = torch.is_grad_enabled() and (s.requires_grad or a.requires_grad)      # (asked here: inside an autograd function the grad mode is always off)
         return _AttentivePoolFunction.apply(s.contiguous(), a.contiguous(), lengths, self.which, self.eps, keep)

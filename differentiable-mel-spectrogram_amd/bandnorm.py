@@ -33,7 +33,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import capi
+from . import _stage, capi
+from ._stage import ptr
 
 
 class _BandNormFunction(torch.autograd.Function):
@@ -48,11 +49,9 @@ class _BandNormFunction(torch.autograd.Function):
         scratch = None
         if batch_stats and training:
             scratch = torch.empty(max(capi.bandnorm_scratch_bytes(rows, n_mels) // 8, 2), dtype=torch.float64, device=s.device)
-        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        with torch.cuda.device(s.device):
-            capi.bandnorm_forward(s.data_ptr(), rows, n_mels, rows_per_clip, T, ptr(lengths), ptr(weight), ptr(bias), batch_stats, training, eps,
-                                  momentum, ptr(running_mean), ptr(running_var), ptr(num_batches_tracked) if training else None, y.data_ptr(),
-                                  stats.data_ptr(), ptr(scratch), torch.cuda.current_stream(s.device).cuda_stream)
+        _stage.launch(capi.bandnorm_forward, s, s.data_ptr(), rows, n_mels, rows_per_clip, T, ptr(lengths), ptr(weight), ptr(bias), batch_stats,
+                      training, eps, momentum, ptr(running_mean), ptr(running_var), ptr(num_batches_tracked) if training else None, y.data_ptr(),
+                      stats.data_ptr(), ptr(scratch))
         ctx.save_for_backward(s, stats, weight, lengths)
         ctx.batch_stats, ctx.training, ctx.has_bias = batch_stats, training, bias is not None
         return y
@@ -63,9 +62,7 @@ class _BandNormFunction(torch.autograd.Function):
         n_mels, T = s.shape[-2], s.shape[-1]
         rows = s.numel() // T if T else 0
         rows_per_clip = (s.shape[1] if s.dim() == 4 else 1) * n_mels
-        g = g.contiguous()
-        if g.dtype != torch.float32:
-            raise RuntimeError(f"BandNorm: the gradient of the output must be fp32, got {g.dtype}")
+        g = _stage.cotangent("BandNorm", g)
         want_s, want_w, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
         ds = torch.empty_like(s) if want_s else None
         # (an empty tensor launches nothing: its parameter gradients are empty sums)
@@ -73,11 +70,8 @@ class _BandNormFunction(torch.autograd.Function):
         dw = mk(n_mels, dtype=torch.float32, device=s.device) if want_w else None
         db = mk(n_mels, dtype=torch.float32, device=s.device) if want_b else None
         scratch = torch.empty(max(capi.bandnorm_scratch_bytes(rows, n_mels) // 8, 2), dtype=torch.float64, device=s.device)
-        ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        with torch.cuda.device(s.device):
-            capi.bandnorm_backward(g.data_ptr(), s.data_ptr(), stats.data_ptr(), rows, n_mels, rows_per_clip, T, ptr(lengths), ptr(weight),
-                                   ctx.batch_stats, ctx.training, ptr(ds), ptr(dw), ptr(db), scratch.data_ptr(),
-                                   torch.cuda.current_stream(s.device).cuda_stream)
+        _stage.launch(capi.bandnorm_backward, s, g.data_ptr(), s.data_ptr(), stats.data_ptr(), rows, n_mels, rows_per_clip, T, ptr(lengths),
+                      ptr(weight), ctx.batch_stats, ctx.training, ptr(ds), ptr(dw), ptr(db), scratch.data_ptr())
         return (ds, dw, db) + (None,) * 8
 
 
@@ -128,30 +122,12 @@ class BandNorm(nn.Module):
     def extra_repr(self) -> str:
         return f"n_mels={self.n_mels}, stats={self.stats!r}, affine={self.affine}, eps={self.eps}, momentum={self.momentum}"
 
-    def _lengths(self, s, frame_lengths):
-        """shape, dtype and device of ``frame_lengths``; returns them as the kernels read them (int32, contiguous).  Their values never
-        leave the device."""
-        if not torch.is_tensor(frame_lengths):
-            raise TypeError(f"BandNorm: frame_lengths must be a 1-D integer tensor, got {type(frame_lengths).__name__}")
-        if frame_lengths.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"BandNorm: frame_lengths must hold int32 or int64 values, got {frame_lengths.dtype}")
-        if frame_lengths.dim() != 1 or frame_lengths.shape[0] != s.shape[0]:
-            raise ValueError(f"BandNorm: frame_lengths must have shape ({s.shape[0]},), got {tuple(frame_lengths.shape)}")
-        if frame_lengths.device != s.device:
-            raise RuntimeError(f"BandNorm: frame_lengths is on {frame_lengths.device} but the input is on {s.device}")
-        if frame_lengths.dtype != torch.int32:
-            # int64 values clamped on the device before the narrowing: 2**32 + 5 must stay invalid (NaN), not wrap to 5
-            frame_lengths = frame_lengths.clamp(0, s.shape[-1] + 1).to(torch.int32)
-        return frame_lengths.contiguous()
-
     def forward(self, s: torch.Tensor, frame_lengths: torch.Tensor | None = None) -> torch.Tensor:
-        if not torch.is_tensor(s) or s.dim() not in (3, 4):
-            raise ValueError(f"BandNorm: expected a (B, n_mels, T) or (B, C, n_mels, T) tensor, got {tuple(s.shape) if torch.is_tensor(s) else type(s).__name__}")
-        if s.dtype != torch.float32:
-            raise RuntimeError(f"BandNorm takes an fp32 mel image (a layer with out_dtype=torch.float32), got {s.dtype}")
+        # (the checks only: this stage works on the tensor as it is given, 3-D or 4-D, and returns that shape)
+        _stage.mel_image("BandNorm", s, "an fp32 mel image (a layer with out_dtype=torch.float32)")
         if s.shape[-2] != self.n_mels:
             raise RuntimeError(f"BandNorm was built for n_mels={self.n_mels} but dim -2 of the input has {s.shape[-2]} bands")
-        lengths = None if frame_lengths is None else self._lengths(s, frame_lengths)
+        lengths = _stage.frame_lengths_for_kernels("BandNorm", s, frame_lengths)
         for name in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked"):
             p = getattr(self, name)
             if p is None:
@@ -161,8 +137,7 @@ class BandNorm(nn.Module):
             want = torch.int64 if name == "num_batches_tracked" else torch.float32
             if p.dtype != want:
                 raise RuntimeError(f"BandNorm.{name} must stay {want}, got {p.dtype}")
-        if not s.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: BandNorm's input must be a CUDA/HIP tensor (no CPU fallback)")
+        _stage.require_gpu("BandNorm", s)
         batch = self.stats == "batch"
         return _BandNormFunction.apply(s.contiguous(), self.weight, self.bias, lengths, batch, bool(self.training) if batch else True, self.eps,
                                        self.momentum, self.running_mean, self.running_var, self.num_batches_tracked)

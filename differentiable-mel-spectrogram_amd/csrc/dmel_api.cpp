@@ -7,6 +7,7 @@
 #include "../../include/dmel.h"
 #include "dmel_kernels.h"
 #include "dmel_lamtrack.h"
+#include "dmel_stage.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2953,6 +2954,38 @@ dmel_status dmel_adam_step(float* param, const float* grad, float* exp_avg, floa
 }
 
 namespace {
+// the stages behind the mel layers (PCEN, BandNorm, SpecMask, Deltas, StatsPool, AttentivePool): what their entry points check alike
+
+// p is not a multiple of `bytes` (a power of two); false for NULL
+bool misaligned(const void* p, int bytes)
+{
+    return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) != 0;
+}
+
+// a stage launches on the calling thread's current device: there must be one
+dmel_status hip_device(const char* who)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return fail(DMEL_ERR_NO_DEVICE, std::string(who) + ": no HIP device"); }
+    return DMEL_OK;
+}
+
+// rows of T frames, rows_per_clip of them per clip (Deltas, StatsPool, AttentivePool: one text)
+dmel_status stage_rows_check(const std::string& w, int64_t rows, int64_t rows_per_clip, int32_t T)
+{
+    if (rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_time out of range");
+    if (rows_per_clip < 1 || rows % rows_per_clip != 0)
+        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows_per_clip must be positive and divide rows (clip = row / rows_per_clip)");
+    return DMEL_OK;
+}
+
+// (after the stage's own arguments, where each entry point has always looked at it)
+dmel_status stage_lengths_check(const std::string& w, const int32_t* lengths)
+{
+    if (misaligned(lengths, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": frame_lengths must be int32 values");
+    return DMEL_OK;
+}
+
 // what dmel_pcen_forward and dmel_pcen_backward check alike; DMEL_OK with *noop set: nothing to launch
 dmel_status pcen_check(const char* who, int64_t rows, int32_t n_mels, int32_t T, const float* alpha, const float* delta, const float* r,
                        const float* s, float eps, bool* noop)
@@ -2964,14 +2997,7 @@ dmel_status pcen_check(const char* who, int64_t rows, int32_t n_mels, int32_t T,
     if (rows % n_mels != 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows must be a multiple of n_mels (band = row % n_mels)");
     if (!std::isfinite(eps) || !(eps > 0.f)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": eps must be finite and > 0");
     if (rows == 0 || T == 0) { *noop = true; return DMEL_OK; }
-    if (dmel::pcen_blocks(rows, T) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
-    return DMEL_OK;
-}
-
-dmel_status pcen_device(const char* who)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return fail(DMEL_ERR_NO_DEVICE, std::string(who) + ": no HIP device"); }
+    if (dmel::stage_row_blocks(rows, T) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
     return DMEL_OK;
 }
 }  // namespace
@@ -2989,7 +3015,7 @@ dmel_status dmel_pcen_forward(const float* E, int64_t rows, int32_t n_mels, int3
     if (st != DMEL_OK) return st;
     if (!E || !y) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_pcen_forward: NULL pointer (E / y)");
     if (noop) return DMEL_OK;
-    const dmel_status sd = pcen_device("dmel_pcen_forward");
+    const dmel_status sd = hip_device("dmel_pcen_forward");
     if (sd != DMEL_OK) return sd;
     dmel::PcenParams p{};
     p.E = E; p.y = y; p.M = M_or_null; p.alpha = alpha; p.delta = delta; p.r = r; p.s = s;
@@ -3006,10 +3032,10 @@ dmel_status dmel_pcen_backward(const float* g, const float* E, const float* M, i
     const dmel_status st = pcen_check("dmel_pcen_backward", rows, n_mels, T, alpha, delta, r, s, eps, &noop);
     if (st != DMEL_OK) return st;
     if (!g || !E || !M) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_pcen_backward: NULL pointer (g / E / M)");
-    if (dparams_or_null && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15)))
+    if (dparams_or_null && (!scratch || misaligned(scratch, 16)))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_pcen_backward: the parameter gradients need 16-byte aligned scratch of dmel_pcen_scratch_bytes(rows)");
     if (noop || (!dE_or_null && !dparams_or_null)) return DMEL_OK;      // nothing is written (not dparams either)
-    const dmel_status sd = pcen_device("dmel_pcen_backward");
+    const dmel_status sd = hip_device("dmel_pcen_backward");
     if (sd != DMEL_OK) return sd;
     dmel::PcenParams p{};
     p.g = g; p.E = E; p.Min = M; p.dE = dE_or_null; p.partials = dparams_or_null ? scratch : nullptr;
@@ -3032,9 +3058,9 @@ dmel_status bandnorm_check(const char* who, int64_t rows, int32_t n_mels, int64_
     if (rows % rows_per_clip != 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows must be a multiple of rows_per_clip (clip = row / rows_per_clip)");
     if ((batch_stats != 0 && batch_stats != 1) || (training != 0 && training != 1))
         return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": batch_stats and training are 0 or 1");
-    if (!stats || (reinterpret_cast<uintptr_t>(stats) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats must be a 16-byte aligned buffer");
+    if (!stats || misaligned(stats, 16)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats must be a 16-byte aligned buffer");
     if (rows == 0 || T == 0) { *noop = true; return DMEL_OK; }
-    if (dmel::bandnorm_blocks(rows, T) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
+    if (dmel::stage_row_blocks(rows, T) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
     return DMEL_OK;
 }
 }  // namespace
@@ -3061,10 +3087,10 @@ dmel_status dmel_bandnorm_forward(const float* s, int64_t rows, int32_t n_mels, 
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: clip statistics keep no running_mean / running_var / num_batches_tracked");
     if ((running_mean == nullptr) != (running_var == nullptr))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: running_mean and running_var come together");
-    if (batch_stats && training && (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15)))
+    if (batch_stats && training && (!scratch || misaligned(scratch, 16)))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_forward: the batch statistics need 16-byte aligned scratch of dmel_bandnorm_scratch_bytes(rows, n_mels)");
     if (noop) return DMEL_OK;
-    const dmel_status sd = pcen_device("dmel_bandnorm_forward");
+    const dmel_status sd = hip_device("dmel_bandnorm_forward");
     if (sd != DMEL_OK) return sd;
     dmel::BandNormParams p{};
     p.s = s; p.y = y; p.lengths = frame_lengths_or_null; p.gamma = weight_or_null; p.beta = bias_or_null;
@@ -3084,10 +3110,10 @@ dmel_status dmel_bandnorm_backward(const float* g, const float* s, const double*
     const dmel_status st = bandnorm_check("dmel_bandnorm_backward", rows, n_mels, rows_per_clip, T, batch_stats, training, stats, &noop);
     if (st != DMEL_OK) return st;
     if (!g || !s) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_backward: NULL pointer (g / s)");
-    if (!scratch || (reinterpret_cast<uintptr_t>(scratch) & 15))
+    if (!scratch || misaligned(scratch, 16))
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_bandnorm_backward: needs 16-byte aligned scratch of dmel_bandnorm_scratch_bytes(rows, n_mels)");
     if (noop || (!ds_or_null && !dweight_or_null && !dbias_or_null)) return DMEL_OK;      // nothing is written
-    const dmel_status sd = pcen_device("dmel_bandnorm_backward");
+    const dmel_status sd = hip_device("dmel_bandnorm_backward");
     if (sd != DMEL_OK) return sd;
     dmel::BandNormParams p{};
     p.g = g; p.s = s; p.ds = ds_or_null; p.lengths = frame_lengths_or_null; p.gamma = weight_or_null;
@@ -3123,11 +3149,11 @@ dmel_status dmel_specmask_draw(int64_t images, int32_t channels, int32_t n_mels,
     if (time_param < 0 || freq_param < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": time_param and freq_param must be >= 0");
     if (time_permille < 0 || time_permille > 1000) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": time_permille must lie in 0 ... 1000");
     if (advance != 0 && advance != 1) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": advance is 0 or 1");
-    if (!rng_state || (reinterpret_cast<uintptr_t>(rng_state) & 7)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rng_state must be two 8-byte aligned int64 values (seed, calls)");
-    if (n_time + n_freq > 0 && (!stripes || (reinterpret_cast<uintptr_t>(stripes) & 3)))
+    if (!rng_state || misaligned(rng_state, 8)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rng_state must be two 8-byte aligned int64 values (seed, calls)");
+    if (n_time + n_freq > 0 && (!stripes || misaligned(stripes, 4)))
         return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stripes must be a buffer of images * (n_time + n_freq) * 2 int32 values");
     if (images == 0 || T == 0 || n_time + n_freq == 0) return DMEL_OK;                 // nothing to draw: `calls` stays
-    const dmel_status sd = pcen_device("dmel_specmask_draw");
+    const dmel_status sd = hip_device("dmel_specmask_draw");
     if (sd != DMEL_OK) return sd;
     dmel::SpecMaskDrawParams p{};
     p.lengths = frame_lengths_or_null; p.rng_state = reinterpret_cast<unsigned long long*>(rng_state); p.stripes = stripes;
@@ -3150,15 +3176,15 @@ dmel_status dmel_specmask_apply(const void* s, int64_t rows, int32_t n_mels, int
     if (n_time < 0 || n_freq < 0 || n_time + n_freq > 8) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": n_time and n_freq must be >= 0 and n_time + n_freq <= 8");
     if (elem_bf16 != 0 && elem_bf16 != 1) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": elem_bf16 is 0 (fp32) or 1 (bf16)");
     const int elem_bytes = elem_bf16 ? 2 : 4;
-    if (!s || (reinterpret_cast<uintptr_t>(s) & (uintptr_t)(elem_bytes - 1))) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer aligned to its element");
-    if (!y || (reinterpret_cast<uintptr_t>(y) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": y must be a 16-byte aligned buffer");
-    if (n_time + n_freq > 0 && (!stripes || (reinterpret_cast<uintptr_t>(stripes) & 3)))
+    if (!s || misaligned(s, elem_bytes)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer aligned to its element");
+    if (!y || misaligned(y, 16)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": y must be a 16-byte aligned buffer");
+    if (n_time + n_freq > 0 && (!stripes || misaligned(stripes, 4)))
         return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stripes must be the table dmel_specmask_draw wrote");
     if (rows == 0 || T == 0) return DMEL_OK;
     const int64_t images = rows / n_mels;
     if ((int64_t)n_mels * T > (1LL << 30)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": n_mels * T is too large (an image has at most 2^30 elements)");
     if (images * dmel::specmask_waves_per_image(n_mels, T, elem_bytes) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
-    const dmel_status sd = pcen_device("dmel_specmask_apply");
+    const dmel_status sd = hip_device("dmel_specmask_apply");
     if (sd != DMEL_OK) return sd;
     dmel::SpecMaskParams p{};
     p.s = s; p.y = y; p.lengths = frame_lengths_or_null; p.stripes = stripes;
@@ -3175,20 +3201,18 @@ dmel_status deltas_call(const char* what, const char* in_name, const char* out_n
                         void* stream)
 {
     const std::string w(what);
-    if (rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_time out of range");
-    if (rows_per_clip < 1 || rows % rows_per_clip != 0)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows_per_clip must be positive and divide rows (clip = row / rows_per_clip)");
+    if (const dmel_status st = stage_rows_check(w, rows, rows_per_clip, T); st != DMEL_OK) return st;
     if (win_length != 3 && win_length != 5 && win_length != 7 && win_length != 9)
         return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": win_length must be 3, 5, 7 or 9");
     if (order != 1 && order != 2) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": order must be 1 or 2");
     if (include_static != 0 && include_static != 1) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": include_static is 0 or 1");
-    if (!in || (reinterpret_cast<uintptr_t>(in) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": " + in_name + " must be a buffer of fp32 values");
-    if (!out || (reinterpret_cast<uintptr_t>(out) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": " + out_name + " must be a 16-byte aligned buffer");
-    if (lengths && (reinterpret_cast<uintptr_t>(lengths) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": frame_lengths must be int32 values");
+    if (!in || misaligned(in, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": " + in_name + " must be a buffer of fp32 values");
+    if (!out || misaligned(out, 16)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": " + out_name + " must be a 16-byte aligned buffer");
+    if (const dmel_status st = stage_lengths_check(w, lengths); st != DMEL_OK) return st;
     if (rows == 0 || T == 0) return DMEL_OK;
     const int n = (win_length - 1) / 2;
     if (rows > 0x7FFFFFFFLL || dmel::deltas_waves(rows, T, n) > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
-    const dmel_status sd = pcen_device(what);
+    const dmel_status sd = hip_device(what);
     if (sd != DMEL_OK) return sd;
     dmel::DeltasParams p{};
     p.in = in; p.out = out; p.lengths = lengths; p.rows = rows; p.rows_per_clip = rows_per_clip;
@@ -3218,13 +3242,11 @@ namespace {
 dmel_status statspool_check(const std::string& w, int64_t rows, int64_t rows_per_clip, int32_t T, const int32_t* lengths, int32_t which,
                             const double* stats, const int32_t* argmax, bool* noop)
 {
-    if (rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_time out of range");
-    if (rows_per_clip < 1 || rows % rows_per_clip != 0)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows_per_clip must be positive and divide rows (clip = row / rows_per_clip)");
+    if (const dmel_status st = stage_rows_check(w, rows, rows_per_clip, T); st != DMEL_OK) return st;
     if (which < 1 || which > 7) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": which must lie in 1 ... 7 (bit 0 mean, bit 1 std, bit 2 max)");
-    if (lengths && (reinterpret_cast<uintptr_t>(lengths) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": frame_lengths must be int32 values");
-    if (stats && (reinterpret_cast<uintptr_t>(stats) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats must be a 16-byte aligned buffer of 2 * rows doubles");
-    if (argmax && (reinterpret_cast<uintptr_t>(argmax) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": argmax must be int32 values");
+    if (const dmel_status st = stage_lengths_check(w, lengths); st != DMEL_OK) return st;
+    if (misaligned(stats, 16)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats must be a 16-byte aligned buffer of 2 * rows doubles");
+    if (misaligned(argmax, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": argmax must be int32 values");
     *noop = rows == 0 || T == 0;
     if (!*noop && rows > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
     return DMEL_OK;
@@ -3238,11 +3260,11 @@ dmel_status dmel_statspool_forward(const float* s, int64_t rows, int64_t rows_pe
     bool noop = false;
     const dmel_status st = statspool_check(w, rows, rows_per_clip, n_time, frame_lengths_or_null, which, stats_or_null, argmax_or_null, &noop);
     if (st != DMEL_OK) return st;
-    if (!s || (reinterpret_cast<uintptr_t>(s) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer of fp32 values");
-    if (!y || (reinterpret_cast<uintptr_t>(y) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": y must be a buffer of fp32 values");
+    if (!s || misaligned(s, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer of fp32 values");
+    if (!y || misaligned(y, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": y must be a buffer of fp32 values");
     if ((which & 2) && (!std::isfinite(eps) || !(eps > 0.0))) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": eps must be finite and > 0 when std is selected");
     if (noop) return DMEL_OK;
-    const dmel_status sd = pcen_device("dmel_statspool_forward");
+    const dmel_status sd = hip_device("dmel_statspool_forward");
     if (sd != DMEL_OK) return sd;
     dmel::StatsPoolParams p{};
     p.s = s; p.y = y; p.lengths = frame_lengths_or_null; p.stats = stats_or_null; p.argmax = argmax_or_null;
@@ -3260,14 +3282,14 @@ dmel_status dmel_statspool_backward(const float* g, const float* s_or_null, cons
     bool noop = false;
     const dmel_status st = statspool_check(w, rows, rows_per_clip, n_time, frame_lengths_or_null, which, stats_or_null, argmax_or_null, &noop);
     if (st != DMEL_OK) return st;
-    if (!g || (reinterpret_cast<uintptr_t>(g) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": g must be a buffer of fp32 values");
-    if (!ds || (reinterpret_cast<uintptr_t>(ds) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": ds must be a buffer of fp32 values");
-    if (s_or_null && (reinterpret_cast<uintptr_t>(s_or_null) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer of fp32 values");
+    if (!g || misaligned(g, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": g must be a buffer of fp32 values");
+    if (!ds || misaligned(ds, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": ds must be a buffer of fp32 values");
+    if (misaligned(s_or_null, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer of fp32 values");
     if ((which & 2) && (!s_or_null || !stats_or_null))
         return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": std is selected: s and the stats the forward wrote are needed");
     if ((which & 4) && !argmax_or_null) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": max is selected: the argmax the forward wrote is needed");
     if (noop) return DMEL_OK;
-    const dmel_status sd = pcen_device("dmel_statspool_backward");
+    const dmel_status sd = hip_device("dmel_statspool_backward");
     if (sd != DMEL_OK) return sd;
     dmel::StatsPoolParams p{};
     p.g = g; p.s = s_or_null; p.ds = ds; p.lengths = frame_lengths_or_null;
@@ -3282,18 +3304,16 @@ namespace {
 dmel_status attnpool_check(const std::string& w, const float* s, const float* a, int64_t rows, int64_t rows_per_clip, int64_t logit_rows,
                            int32_t T, const int32_t* lengths, int32_t which, double eps, const double* stats, const double* norm, bool* noop)
 {
-    if (rows < 0 || T < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows / n_time out of range");
-    if (rows_per_clip < 1 || rows % rows_per_clip != 0)
-        return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": rows_per_clip must be positive and divide rows (clip = row / rows_per_clip)");
+    if (const dmel_status st = stage_rows_check(w, rows, rows_per_clip, T); st != DMEL_OK) return st;
     if (logit_rows < 1 || rows_per_clip % logit_rows != 0)
         return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": logit_rows_per_clip must be positive and divide rows_per_clip (row r reads logit row r / (rows_per_clip / logit_rows_per_clip))");
     if (which < 1 || which > 3) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": which must lie in 1 ... 3 (bit 0 mean, bit 1 std)");
     if ((which & 2) && (!std::isfinite(eps) || !(eps > 0.0))) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": eps must be finite and > 0 when std is selected");
-    if (lengths && (reinterpret_cast<uintptr_t>(lengths) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": frame_lengths must be int32 values");
-    if (!s || (reinterpret_cast<uintptr_t>(s) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer of fp32 values");
-    if (!a || (reinterpret_cast<uintptr_t>(a) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": a must be a buffer of fp32 logits");
-    if (stats && (reinterpret_cast<uintptr_t>(stats) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats must be a 16-byte aligned buffer of 2 * rows doubles");
-    if (norm && (reinterpret_cast<uintptr_t>(norm) & 15)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": norm must be a 16-byte aligned buffer of 2 doubles per logit row");
+    if (const dmel_status st = stage_lengths_check(w, lengths); st != DMEL_OK) return st;
+    if (!s || misaligned(s, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": s must be a buffer of fp32 values");
+    if (!a || misaligned(a, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": a must be a buffer of fp32 logits");
+    if (misaligned(stats, 16)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats must be a 16-byte aligned buffer of 2 * rows doubles");
+    if (misaligned(norm, 16)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": norm must be a 16-byte aligned buffer of 2 doubles per logit row");
     if (!stats != !norm) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": stats and norm must both be given or both be NULL");
     *noop = rows == 0 || T == 0;
     if (!*noop && rows > 0x7FFFFFFFLL) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
@@ -3321,9 +3341,9 @@ dmel_status dmel_attnpool_forward(const float* s, const float* a, int64_t rows, 
     const dmel_status st = attnpool_check(w, s, a, rows, rows_per_clip, logit_rows_per_clip, n_time, frame_lengths_or_null, which, eps,
                                           stats_or_null, norm_or_null, &noop);
     if (st != DMEL_OK) return st;
-    if (!y || (reinterpret_cast<uintptr_t>(y) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": y must be a buffer of fp32 values");
+    if (!y || misaligned(y, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": y must be a buffer of fp32 values");
     if (noop) return DMEL_OK;
-    const dmel_status sd = pcen_device("dmel_attnpool_forward");
+    const dmel_status sd = hip_device("dmel_attnpool_forward");
     if (sd != DMEL_OK) return sd;
     dmel::AttnPoolParams p = attnpool_params(s, a, rows, rows_per_clip, logit_rows_per_clip, n_time, frame_lengths_or_null, which, eps,
                                              stats_or_null, norm_or_null);
@@ -3341,14 +3361,14 @@ dmel_status dmel_attnpool_backward(const float* g, const float* s, const float* 
     const dmel_status st = attnpool_check(w, s, a, rows, rows_per_clip, logit_rows_per_clip, n_time, frame_lengths_or_null, which, eps,
                                           stats, norm, &noop);
     if (st != DMEL_OK) return st;
-    if (!g || (reinterpret_cast<uintptr_t>(g) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": g must be a buffer of fp32 values");
-    if (!ds || (reinterpret_cast<uintptr_t>(ds) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": ds must be a buffer of fp32 values");
-    if (!da || (reinterpret_cast<uintptr_t>(da) & 3)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": da must be a buffer of fp32 values");
+    if (!g || misaligned(g, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": g must be a buffer of fp32 values");
+    if (!ds || misaligned(ds, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": ds must be a buffer of fp32 values");
+    if (!da || misaligned(da, 4)) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": da must be a buffer of fp32 values");
     if (!stats || !norm) return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": the stats and norm the forward wrote are needed");
     if (noop) return DMEL_OK;
     if (dmel::attnpool_blocks(rows, rows_per_clip, logit_rows_per_clip, n_time, true) > 0x7FFFFFFFLL)
         return fail(DMEL_ERR_INVALID_ARGUMENT, w + ": too many rows for one launch");
-    const dmel_status sd = pcen_device("dmel_attnpool_backward");
+    const dmel_status sd = hip_device("dmel_attnpool_backward");
     if (sd != DMEL_OK) return sd;
     dmel::AttnPoolParams p = attnpool_params(s, a, rows, rows_per_clip, logit_rows_per_clip, n_time, frame_lengths_or_null, which, eps, stats, norm);
     p.g = g; p.ds = ds; p.da = da;

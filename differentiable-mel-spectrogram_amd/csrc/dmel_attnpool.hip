@@ -8,7 +8,7 @@
 // The output has S = popcount(which) groups of R values per clip in torch.cat([mean, std], dim=1) order, StatsPool's group layout
 // (include/dmel.h is the specification).
 //
-// Forward, one launch on the row geometry of dmel_statspool.hip (copied, not shared: that object keeps its bits): frames one per lane, rows
+// Forward, one launch on the row geometry of dmel_statspool.hip (ap_row is sp_row with the logit-row fields; both are built from dmel_stage.h): frames one per lane, rows
 // of up to 32 frames packed 64 / W to a wave (W = the next power of two >= T lanes each), longer rows a wave each, lane j taking frames j,
 // j + 64, ... of the chunks that hold valid frames: a pad chunk is skipped, not masked, and neither s nor a is loaded at a pad frame.  Every
 // row's lanes recompute m and Z from the row's logit row (T exponentials per row more than a weights pass would need, and one launch less);
@@ -29,12 +29,9 @@
 // before the first of their stores.  Where every row has a logit row of its own (R / A == 1) nothing is shared: dmel_attnpool_bwd_row_kernel
 // is the same arithmetic straight through, a wave per row's chunk.  +0.0 on pad frames, a chunk without a valid frame stores its zeros without loading, NaN for a clip with an invalid length.
 #include "dmel_kernels.h"
+#include "dmel_stage.h"
 
 namespace dmel {
-
-typedef const int __attribute__((address_space(4))) * ap_const_ints;
-typedef const double __attribute__((address_space(4))) * ap_const_doubles;
-typedef const float __attribute__((address_space(4))) * ap_const_floats;
 
 struct ApRow {
     long long row, off, aoff, lrow, out;  // off = row * T; lrow: the logit row, aoff = lrow * T; out: the row's element of group 0 of y
@@ -49,7 +46,7 @@ __device__ __forceinline__ ApRow ap_row(const AttnPoolParams& p)
     ApRow q;
     const int lane = threadIdx.x & 63;
     // (the launcher keeps rows below 2^31: 32-bit quotients)
-    const unsigned wid = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned wid = stage_wave();
     q.j = lane & (p.W - 1);
     unsigned row, clip;
     int tc;
@@ -57,14 +54,14 @@ __device__ __forceinline__ ApRow ap_row(const AttnPoolParams& p)
         row = wid;
         q.rowok = row < (unsigned)p.rows;
         clip = (q.rowok ? row : 0u) / (unsigned)p.rows_per_clip;
-        tc = p.lengths ? ((ap_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
+        tc = p.lengths ? ((stage_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
     } else {
         row = wid * (unsigned)(64 >> p.logw) + (unsigned)(lane >> p.logw);
         q.rowok = row < (unsigned)p.rows;
         clip = (q.rowok ? row : 0u) / (unsigned)p.rows_per_clip;
         tc = p.lengths ? p.lengths[clip] : p.T;
     }
-    q.bad = tc < 1 || tc > p.T;
+    q.bad = stage_bad(tc, p.T);
     q.n = q.bad ? 0 : tc;
     q.row = row;
     q.off = (long long)row * p.T;
@@ -76,13 +73,6 @@ __device__ __forceinline__ ApRow ap_row(const AttnPoolParams& p)
     q.out = (long long)clip * p.S * p.rows_per_clip + in_clip;
     if (!q.rowok) { q.n = 0; q.bad = false; }                      // rows past the end load nothing and store nothing
     return q;
-}
-
-// sum over the W lanes of a segment in fp64, the same order every run; every lane of the segment ends with the sum
-__device__ __forceinline__ double ap_seg_sum(double v, int W)
-{
-    for (int d = W >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 __global__ void __launch_bounds__(256) dmel_attnpool_fwd_kernel(AttnPoolParams p)
@@ -115,8 +105,8 @@ __global__ void __launch_bounds__(256) dmel_attnpool_fwd_kernel(AttnPoolParams p
             ps = __builtin_fma(pe, (double)sv - ref, ps);
         }
     }
-    const double Z = ap_seg_sum(z, W);
-    const double mean = ref + ap_seg_sum(ps, W) / Z;
+    const double Z = stage_seg_sum(z, W);
+    const double mean = ref + stage_seg_sum(ps, W) / Z;
     double var = 0.0;
     if ((p.which & 2) || p.stats) {
         double v = 0.0;
@@ -128,7 +118,7 @@ __global__ void __launch_bounds__(256) dmel_attnpool_fwd_kernel(AttnPoolParams p
                 v = __builtin_fma(pe * d, d, v);
             }
         }
-        var = ap_seg_sum(v, W) / Z;
+        var = stage_seg_sum(v, W) / Z;
     }
     if (q.rowok && q.j == 0) {
         const unsigned nan = 0x7FC00000u;
@@ -157,20 +147,19 @@ __global__ void __launch_bounds__(1024) dmel_attnpool_bwd_kernel(AttnPoolParams 
     const int chunk = (int)(ow - lrow * p.chunks);
     const long long clip = lrow / p.logit_rows;
     const long long arow = lrow - clip * p.logit_rows;
-    const int tc = p.lengths ? ((ap_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
-    const bool bad = tc < 1 || tc > p.T;
-    const int n = bad ? 0 : tc;
+    bool bad;
+    const int n = stage_valid(p.lengths ? ((stage_const_ints)(unsigned long long)p.lengths)[clip] : p.T, p.T, bad);
     const int t = chunk * 64 + lane;
     const bool in_row = t < p.T, valid = t < n;
     const bool any = chunk * 64 < n;                               // the chunk holds a valid frame (uniform)
     double w = 0.0;
     if (valid) {
-        const ap_const_doubles nm = (ap_const_doubles)(unsigned long long)p.norm + 2 * lrow;
+        const stage_const_doubles nm = (stage_const_doubles)(unsigned long long)p.norm + 2 * lrow;
         w = exp((double)p.a[lrow * p.T + t] - nm[0]) / nm[1];
     }
     const long long r0 = clip * p.rows_per_clip + arow * p.group;
-    const ap_const_floats g = (ap_const_floats)(unsigned long long)p.g + (clip * p.S * p.rows_per_clip + arow * p.group);
-    const ap_const_doubles st = (ap_const_doubles)(unsigned long long)p.stats + 2 * r0;
+    const stage_const_floats g = (stage_const_floats)(unsigned long long)p.g + (clip * p.S * p.rows_per_clip + arow * p.group);
+    const stage_const_doubles st = (stage_const_doubles)(unsigned long long)p.stats + 2 * r0;
     const long long gs = p.rows_per_clip;
     const float fill = bad ? __builtin_nanf("") : 0.f;
     double acc = 0.0;
@@ -230,15 +219,15 @@ __global__ void __launch_bounds__(256) dmel_attnpool_bwd_row_kernel(AttnPoolPara
     const long long row = owner / p.chunks;                        // the row and its logit row
     const int chunk = (int)(owner - row * p.chunks);
     const long long clip = row / p.rows_per_clip;
-    const int tc = p.lengths ? ((ap_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
-    const bool bad = tc < 1 || tc > p.T;
+    const int tc = p.lengths ? ((stage_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
+    const bool bad = stage_bad(tc, p.T);
     const int t = chunk * 64 + lane;
     const float fill = bad ? __builtin_nanf("") : 0.f;
     float dsv = fill, dav = fill;
     if (!bad && t < tc) {
-        const ap_const_doubles nm = (ap_const_doubles)(unsigned long long)p.norm + 2 * row;
-        const ap_const_doubles st = (ap_const_doubles)(unsigned long long)p.stats + 2 * row;
-        const ap_const_floats g = (ap_const_floats)(unsigned long long)p.g + (clip * p.S * p.rows_per_clip + (row - clip * p.rows_per_clip));
+        const stage_const_doubles nm = (stage_const_doubles)(unsigned long long)p.norm + 2 * row;
+        const stage_const_doubles st = (stage_const_doubles)(unsigned long long)p.stats + 2 * row;
+        const stage_const_floats g = (stage_const_floats)(unsigned long long)p.g + (clip * p.S * p.rows_per_clip + (row - clip * p.rows_per_clip));
         const double mu = st[0], var = st[1];
         double gm = 0.0, q = 0.0;
         int o = 0;
@@ -257,13 +246,8 @@ __global__ void __launch_bounds__(256) dmel_attnpool_bwd_row_kernel(AttnPoolPara
 
 static void attnpool_geometry(AttnPoolParams& p)
 {
-    int logw = 6;
-    if (p.T <= 32) {
-        logw = 0;
-        while ((1 << logw) < p.T) ++logw;
-    }
-    p.logw = logw;
-    p.W = 1 << logw;
+    p.logw = stage_logw(p.T);
+    p.W = 1 << p.logw;
     p.group = p.logit_rows > 0 ? p.rows_per_clip / p.logit_rows : 1;
     p.chunks = (p.T + 63) / 64;
     p.logsplit = p.group >= 16 ? 4 : p.group >= 8 ? 3 : p.group >= 4 ? 2 : p.group >= 2 ? 1 : 0;

@@ -21,6 +21,7 @@
 // Backward, with yh = (s - mu) rstd:  ds = gamma rstd (g - mean(g) - yh mean(g yh)), the means over the statistic's own population (eval mode
 // of the batch statistics: ds = gamma rstd g);  dweight[band] = sum g yh,  dbias[band] = sum g over the valid frames of the band's rows.
 #include "dmel_kernels.h"
+#include "dmel_stage.h"
 
 namespace dmel {
 
@@ -34,12 +35,10 @@ struct BnRow {
 
 __device__ __forceinline__ int bn_valid(const BandNormParams& p, long long clip, bool& bad)
 {
-    const int tc = p.lengths ? p.lengths[clip] : p.T;
-    bad = tc < 1 || tc > p.T;
-    return bad ? 0 : tc;
+    return stage_valid(stage_length(p.lengths, clip, p.T), p.T, bad);
 }
 
-// W lanes per row (a power of two <= 64; 64: one row per wave), 4 waves per workgroup
+// W lanes per row (a power of two <= 64; 64: one row per wave), 4 waves per workgroup; 64-bit rows: a launch may hold more than 2^31 of them
 __device__ __forceinline__ BnRow bn_row(const BandNormParams& p)
 {
     BnRow q;
@@ -51,11 +50,8 @@ __device__ __forceinline__ BnRow bn_row(const BandNormParams& p)
         q.rowok = q.row < p.rows;
         const long long clip = (q.rowok ? q.row : 0) / p.rows_per_clip;      // (a 64-bit quotient is formed in vector registers)
         const unsigned lo = __builtin_amdgcn_readfirstlane((int)(clip & 0xFFFFFFFFLL)), hi = __builtin_amdgcn_readfirstlane((int)(clip >> 32));
-        // (read through the constant address space: nothing writes the lengths while a kernel runs, and a uniform address there is a scalar load)
-        typedef const int __attribute__((address_space(4))) * const_ints;
-        const int tc = p.lengths ? ((const_ints)(unsigned long long)p.lengths)[(long long)(((unsigned long long)hi << 32) | lo)] : p.T;
-        q.bad = tc < 1 || tc > p.T;
-        q.n = q.bad ? 0 : tc;
+        const int tc = p.lengths ? ((stage_const_ints)(unsigned long long)p.lengths)[(long long)(((unsigned long long)hi << 32) | lo)] : p.T;
+        q.n = stage_valid(tc, p.T, q.bad);
     } else {
         q.row = wave * (64 >> p.logw) + (lane >> p.logw);
         q.rowok = q.row < p.rows;
@@ -68,17 +64,9 @@ __device__ __forceinline__ BnRow bn_row(const BandNormParams& p)
     return q;
 }
 
-// sum over the W lanes of a segment in fp64, the same order every run; every lane of the segment ends with the sum
-__device__ __forceinline__ double bn_seg_sum(double v, int W)
-{
-    for (int d = W >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 __device__ __forceinline__ double bn_wave_sum(double v)
 {
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
+    return stage_seg_sum(v, 64);
 }
 
 __device__ __forceinline__ double2 bn_pair(const double* base, long long i)
@@ -99,7 +87,7 @@ __global__ void __launch_bounds__(256) dmel_bandnorm_rowstat_kernel(BandNormPara
         if (t0 == 0) x0 = x;
         sum += (double)x;
     }
-    const double mean = bn_seg_sum(sum, W) / (double)(q.n > 0 ? q.n : 1);
+    const double mean = stage_seg_sum(sum, W) / (double)(q.n > 0 ? q.n : 1);
     double m2 = 0.0;
     for (int t0 = 0; t0 < q.n; t0 += 64) {
         const int t = t0 + q.j;
@@ -107,7 +95,7 @@ __global__ void __launch_bounds__(256) dmel_bandnorm_rowstat_kernel(BandNormPara
         const double d = (t < q.n) ? (double)x - mean : 0.0;
         m2 = __builtin_fma(d, d, m2);
     }
-    m2 = bn_seg_sum(m2, W);
+    m2 = stage_seg_sum(m2, W);
     if (q.rowok && q.j == 0) {
         double2 out;
         if (p.batch_stats) out = make_double2(mean, m2);          // (0, 0) for a clip with an invalid length: it contributes nothing
@@ -209,8 +197,8 @@ __global__ void __launch_bounds__(256) dmel_bandnorm_bwd_rowstat_kernel(BandNorm
             sgy = __builtin_fma(g, yh, sgy);
         }
     }
-    sg = bn_seg_sum(sg, p.W);
-    sgy = bn_seg_sum(sgy, p.W);
+    sg = stage_seg_sum(sg, p.W);
+    sgy = stage_seg_sum(sgy, p.W);
     if (q.rowok && q.j == 0) *reinterpret_cast<double2*>(p.partials + 2 * q.row) = make_double2(sg, sgy);
 }
 
@@ -275,22 +263,8 @@ __global__ void __launch_bounds__(256) dmel_bandnorm_bwd_apply_kernel(BandNormPa
 
 static void bandnorm_geometry(BandNormParams& p)
 {
-    int logw = 6;
-    if (p.T <= 32) {
-        logw = 0;
-        while ((1 << logw) < p.T) ++logw;
-    }
-    p.logw = logw;
-    p.W = 1 << logw;
-}
-
-long long bandnorm_blocks(long long rows, int T)
-{
-    BandNormParams p{};
-    p.T = T;
-    bandnorm_geometry(p);
-    const long long per_block = 4LL * (64 >> p.logw);
-    return (rows + per_block - 1) / per_block;
+    p.logw = stage_logw(p.T);
+    p.W = 1 << p.logw;
 }
 
 #define BN_LAUNCH(kernel, grid)                                                        \
@@ -304,7 +278,7 @@ long long bandnorm_blocks(long long rows, int T)
 hipError_t launch_bandnorm_fwd(BandNormParams p, hipStream_t s)
 {
     bandnorm_geometry(p);
-    const long long rows_grid = bandnorm_blocks(p.rows, p.T), band_grid = (p.n_mels + 3) / 4;
+    const long long rows_grid = stage_row_blocks(p.rows, p.T), band_grid = (p.n_mels + 3) / 4;
     if (!(p.batch_stats && p.eval)) BN_LAUNCH(dmel_bandnorm_rowstat_kernel, rows_grid);
     if (p.batch_stats) BN_LAUNCH(dmel_bandnorm_combine_kernel, band_grid);
     BN_LAUNCH(dmel_bandnorm_apply_kernel, rows_grid);
@@ -316,7 +290,7 @@ hipError_t launch_bandnorm_fwd(BandNormParams p, hipStream_t s)
 hipError_t launch_bandnorm_bwd(BandNormParams p, hipStream_t s)
 {
     bandnorm_geometry(p);
-    const long long rows_grid = bandnorm_blocks(p.rows, p.T), band_grid = (p.n_mels + 3) / 4;
+    const long long rows_grid = stage_row_blocks(p.rows, p.T), band_grid = (p.n_mels + 3) / 4;
     const bool want_p = p.dweight || p.dbias;
     const bool band_mean = p.batch_stats && !p.eval && p.ds;
     const bool row_mean = !p.batch_stats && p.ds;

@@ -25,10 +25,9 @@
 //   a_k = k, except at u = Tc - 1 where the folded taps add up to w_k = sum_{j = max(k, 1) .. n} j;  b_k = k, except at u = 0 where it is w_k.
 // h = g_d + D^T g_dd is rounded to fp32 (it travels through __shfl), ds once more.  On pad frames ds is g_static's word, or +0.0.
 #include "dmel_kernels.h"
+#include "dmel_stage.h"
 
 namespace dmel {
-
-typedef const int __attribute__((address_space(4))) * dl_const_ints;
 
 struct DlLane {
     long long row_in, clip;     // the lane's row of the (rows, T) side and its clip
@@ -41,7 +40,7 @@ __device__ __forceinline__ DlLane dl_lane(const DeltasParams& p)
     DlLane q;
     const int lane = threadIdx.x & 63;
     // (the launcher keeps rows and the number of waves below 2^31: 32-bit quotients)
-    const unsigned wid = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned wid = stage_wave();
     q.j = lane & (p.W - 1);
     q.base = lane - q.j;
     unsigned row, chunk = 0;
@@ -51,7 +50,7 @@ __device__ __forceinline__ DlLane dl_lane(const DeltasParams& p)
         q.rowok = row < (unsigned)p.rows;
         const unsigned clip = (q.rowok ? row : 0u) / (unsigned)p.rows_per_clip;
         q.clip = clip;
-        q.tc = p.lengths ? ((dl_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
+        q.tc = p.lengths ? ((stage_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
     } else {
         row = wid * (unsigned)(64 >> p.logw) + (unsigned)(lane >> p.logw);
         q.rowok = row < (unsigned)p.rows;
@@ -159,14 +158,11 @@ __global__ void __launch_bounds__(256) dmel_deltas_bwd_kernel(DeltasParams p)
 
 static void deltas_geometry(DeltasParams& p)
 {
-    p.logw = 6;
+    p.logw = stage_logw(p.T);
     p.halo = 0;
     p.step = 64;
     p.chunks = 1;
-    if (p.T <= 32) {
-        p.logw = 0;
-        while ((1 << p.logw) < p.T) ++p.logw;
-    } else if (p.T > 64) {
+    if (p.T > 64) {
         p.halo = 2 * p.n;
         p.step = 64 - 2 * p.halo;
         p.chunks = (p.T + p.step - 1) / p.step;

@@ -719,7 +719,6 @@ struct PcenParams {
     float eps;
     int W, logw;                // set by the launchers: lanes per row (next power of two >= T up to 32 frames, else 64)
 };
-long long pcen_blocks(long long rows, int T);      // workgroups of one launch
 hipError_t launch_pcen_fwd(PcenParams p, hipStream_t s);
 hipError_t launch_pcen_bwd(PcenParams p, float* dparams, hipStream_t s);      // dparams: (4, n_mels) or nullptr
 
@@ -743,7 +742,6 @@ struct BandNormParams {
     double eps, momentum;
     int W, logw;                // set by the launchers: lanes per row (next power of two >= T up to 32 frames, else 64)
 };
-long long bandnorm_blocks(long long rows, int T);  // workgroups of a launch over the rows
 hipError_t launch_bandnorm_fwd(BandNormParams p, hipStream_t s);
 hipError_t launch_bandnorm_bwd(BandNormParams p, hipStream_t s);
 
@@ -797,7 +795,6 @@ struct StatsPoolParams {
     double eps;
     int W, logw;                // set by the launcher: lanes per row (next power of two >= T up to 32 frames, else 64)
 };
-long long statspool_blocks(long long rows, int T);         // workgroups of a launch over the rows
 hipError_t launch_statspool(StatsPoolParams p, bool backward, hipStream_t s);
 
 // AttentivePool behind the mel layers (dmel_attnpool_forward / dmel_attnpool_backward, csrc/dmel_attnpool.hip): rows x T fp32 (s; the

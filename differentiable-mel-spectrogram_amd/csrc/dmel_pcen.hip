@@ -21,6 +21,7 @@
 // ... of the band in ascending order and the 64 lane sums are combined by a fixed butterfly.  No floating-point atomics: two runs give the
 // same bits.
 #include "dmel_kernels.h"
+#include "dmel_stage.h"
 
 namespace dmel {
 
@@ -173,13 +174,6 @@ __global__ void __launch_bounds__(256) dmel_pcen_fwd_kernel(PcenParams p)
     }
 }
 
-// sum over the W lanes of a segment in fp64, the same order every run; every lane of the segment ends with the sum
-__device__ __forceinline__ float pcen_seg_sum(double v, int W)
-{
-    for (int d = W >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return (float)v;
-}
-
 __global__ void __launch_bounds__(256) dmel_pcen_bwd_kernel(PcenParams p)
 {
     const PcenRow q = pcen_row(p);
@@ -227,7 +221,8 @@ __global__ void __launch_bounds__(256) dmel_pcen_bwd_kernel(PcenParams p)
         }
     }
     if (p.partials) {
-        const float4 sums = make_float4(pcen_seg_sum(pa, W), pcen_seg_sum(pd, W), pcen_seg_sum(pr, W), pcen_seg_sum(ps, W));
+        // (the fp64 sums of the row, rounded once)
+        const float4 sums = make_float4((float)stage_seg_sum(pa, W), (float)stage_seg_sum(pd, W), (float)stage_seg_sum(pr, W), (float)stage_seg_sum(ps, W));
         if (q.rowok && q.j == 0) *reinterpret_cast<float4*>(p.partials + q.row * 4) = sums;
     }
 }
@@ -261,35 +256,21 @@ __global__ void __launch_bounds__(256) dmel_pcen_reduce_kernel(const float* __re
 
 static void pcen_geometry(PcenParams& p)
 {
-    int logw = 6;
-    if (p.T <= 32) {
-        logw = 0;
-        while ((1 << logw) < p.T) ++logw;
-    }
-    p.logw = logw;
-    p.W = 1 << logw;
-}
-
-long long pcen_blocks(long long rows, int T)
-{
-    PcenParams p{};
-    p.T = T;
-    pcen_geometry(p);
-    const long long per_block = 4LL * (64 >> p.logw);
-    return (rows + per_block - 1) / per_block;
+    p.logw = stage_logw(p.T);
+    p.W = 1 << p.logw;
 }
 
 hipError_t launch_pcen_fwd(PcenParams p, hipStream_t s)
 {
     pcen_geometry(p);
-    hipLaunchKernelGGL(dmel_pcen_fwd_kernel, dim3((unsigned)pcen_blocks(p.rows, p.T)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(dmel_pcen_fwd_kernel, dim3((unsigned)stage_row_blocks(p.rows, p.T)), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_pcen_bwd(PcenParams p, float* dparams, hipStream_t s)
 {
     pcen_geometry(p);
-    hipLaunchKernelGGL(dmel_pcen_bwd_kernel, dim3((unsigned)pcen_blocks(p.rows, p.T)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(dmel_pcen_bwd_kernel, dim3((unsigned)stage_row_blocks(p.rows, p.T)), dim3(256), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !dparams) return e;
     hipLaunchKernelGGL(dmel_pcen_reduce_kernel, dim3((unsigned)((p.n_mels + 3) / 4)), dim3(256), 0, s, p.partials, p.rows, p.n_mels, dparams);

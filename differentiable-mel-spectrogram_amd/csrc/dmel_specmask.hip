@@ -17,10 +17,9 @@
 // The backward is the apply kernel on the cotangent with fill +0.0.  A length outside 1 ... T makes every element of its clip NaN (and the
 // draw leaves that clip's table rows zero).
 #include "dmel_kernels.h"
+#include "dmel_stage.h"
 
 namespace dmel {
-
-typedef const int __attribute__((address_space(4))) * sm_const_ints;
 
 struct SmWord4 { unsigned x, y, z, w; };
 
@@ -48,9 +47,9 @@ __global__ void __launch_bounds__(1024) dmel_specmask_draw_kernel(SpecMaskDrawPa
     for (long long item = threadIdx.x; item < items; item += 1024) {
         const long long image = item / n;
         const int k = (int)(item - image * n);
-        const int tc = p.lengths ? p.lengths[image / p.channels] : p.T;
+        const int tc = stage_length(p.lengths, image / p.channels, p.T);
         int lo = 0, hi = 0;
-        if (tc >= 1 && tc <= p.T) {
+        if (!stage_bad(tc, p.T)) {
             const SmWord4 w = sm_philox((unsigned)calls, (unsigned)(calls >> 32), (unsigned)image, (unsigned)(k >> 1), (unsigned)seed,
                                         (unsigned)(seed >> 32));
             const unsigned wa = (k & 1) ? w.z : w.x, wb = (k & 1) ? w.w : w.y;
@@ -106,11 +105,11 @@ __device__ __forceinline__ void sm_apply_body(const SpecMaskParams& p, unsigned 
     }
 
     const unsigned clip = image / (unsigned)p.channels;
-    const int tc = p.lengths ? ((sm_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
+    const int tc = p.lengths ? ((stage_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
     const bool bad = tc < 1 || tc > p.T;
     // the image's stripe pairs: uniform addresses in the constant address space (the draw kernel finished before this one started)
     const int n = p.n_time + p.n_freq;
-    const sm_const_ints tab = (sm_const_ints)(unsigned long long)p.stripes + (long long)image * (2 * n);
+    const stage_const_ints tab = (stage_const_ints)(unsigned long long)p.stripes + (long long)image * (2 * n);
     int lo[8], hi[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -184,7 +183,7 @@ __global__ void __launch_bounds__(256) dmel_specmask_apply_kernel(SpecMaskParams
 {
     const int lane = threadIdx.x & 63;
     // (the launcher keeps images * waves_per_image below 2^31: 32-bit quotients, one per wave)
-    const unsigned wid = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned wid = stage_wave();
     const unsigned image = wid / (unsigned)p.waves_per_image;
     if (image >= (unsigned)p.images) return;                       // whole waves
     const int chunk = (int)(wid - image * (unsigned)p.waves_per_image);

@@ -18,10 +18,9 @@
 // Backward, element-wise:  ds[t] = g_mean / Tc + g_std (s[t] - mu) / (Tc sd) + [t == am] g_max  on t < Tc, in fp64 from the stored (mu, sd)
 // and am, rounded once; +0.0 on pad frames; s is read only when std is selected, never at a pad frame.
 #include "dmel_kernels.h"
+#include "dmel_stage.h"
 
 namespace dmel {
-
-typedef const int __attribute__((address_space(4))) * sp_const_ints;
 
 struct SpRow {
     long long row, off, out;    // off = row * T; out: the row's element of group 0 of y (or g)
@@ -36,7 +35,7 @@ __device__ __forceinline__ SpRow sp_row(const StatsPoolParams& p)
     SpRow q;
     const int lane = threadIdx.x & 63;
     // (the launcher keeps rows below 2^31: 32-bit quotients)
-    const unsigned wid = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned wid = stage_wave();
     q.j = lane & (p.W - 1);
     unsigned row, clip;
     int tc;
@@ -44,27 +43,20 @@ __device__ __forceinline__ SpRow sp_row(const StatsPoolParams& p)
         row = wid;
         q.rowok = row < (unsigned)p.rows;
         clip = (q.rowok ? row : 0u) / (unsigned)p.rows_per_clip;
-        tc = p.lengths ? ((sp_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
+        tc = p.lengths ? ((stage_const_ints)(unsigned long long)p.lengths)[clip] : p.T;
     } else {
         row = wid * (unsigned)(64 >> p.logw) + (unsigned)(lane >> p.logw);
         q.rowok = row < (unsigned)p.rows;
         clip = (q.rowok ? row : 0u) / (unsigned)p.rows_per_clip;
         tc = p.lengths ? p.lengths[clip] : p.T;
     }
-    q.bad = tc < 1 || tc > p.T;
+    q.bad = stage_bad(tc, p.T);
     q.n = q.bad ? 0 : tc;
     q.row = row;
     q.off = (long long)row * p.T;
     q.out = (long long)clip * p.S * p.rows_per_clip + ((long long)row - (long long)clip * p.rows_per_clip);
     if (!q.rowok) { q.n = 0; q.bad = false; }                      // rows past the end load nothing and store nothing
     return q;
-}
-
-// sum over the W lanes of a segment in fp64, the same order every run; every lane of the segment ends with the sum
-__device__ __forceinline__ double sp_seg_sum(double v, int W)
-{
-    for (int d = W >> 1; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // a comes strictly before b in the order of the maximum, frames aside: a NaN beats a non-NaN, then the larger value (-0.0 == +0.0)
@@ -102,7 +94,7 @@ __global__ void __launch_bounds__(256) dmel_statspool_fwd_kernel(StatsPoolParams
         }
     }
     const double cnt = (double)(q.n > 0 ? q.n : 1);
-    const double mean = sp_seg_sum(sum, W) / cnt;
+    const double mean = stage_seg_sum(sum, W) / cnt;
     double sd = 0.0;
     if ((p.which & 2) || p.stats) {
         double m2 = 0.0;
@@ -113,7 +105,7 @@ __global__ void __launch_bounds__(256) dmel_statspool_fwd_kernel(StatsPoolParams
                 m2 = __builtin_fma(d, d, m2);
             }
         }
-        sd = sqrt(sp_seg_sum(m2, W) / cnt + p.eps);
+        sd = sqrt(stage_seg_sum(m2, W) / cnt + p.eps);
     }
     if (q.rowok && q.j == 0) {
         const unsigned nan = 0x7FC00000u;
@@ -168,30 +160,11 @@ __global__ void __launch_bounds__(256) dmel_statspool_bwd_kernel(StatsPoolParams
     }
 }
 
-static void statspool_geometry(StatsPoolParams& p)
-{
-    int logw = 6;
-    if (p.T <= 32) {
-        logw = 0;
-        while ((1 << logw) < p.T) ++logw;
-    }
-    p.logw = logw;
-    p.W = 1 << logw;
-}
-
-long long statspool_blocks(long long rows, int T)
-{
-    StatsPoolParams p{};
-    p.T = T;
-    statspool_geometry(p);
-    const long long per_block = 4LL * (64 >> p.logw);
-    return (rows + per_block - 1) / per_block;
-}
-
 hipError_t launch_statspool(StatsPoolParams p, bool backward, hipStream_t s)
 {
-    statspool_geometry(p);
-    const long long blocks = statspool_blocks(p.rows, p.T);
+    p.logw = stage_logw(p.T);
+    p.W = 1 << p.logw;
+    const long long blocks = stage_row_blocks(p.rows, p.T);
     if (backward) hipLaunchKernelGGL(dmel_statspool_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(dmel_statspool_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p);
     return hipGetLastError();

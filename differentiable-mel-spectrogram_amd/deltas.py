@@ -33,7 +33,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import capi
+from . import _stage, capi
+from ._stage import ptr
 
 WIN_LENGTHS = (3, 5, 7, 9)
 
@@ -50,9 +51,7 @@ class _DeltasFunction(torch.autograd.Function):
         G = int(include_static) + order
         y = torch.empty((B, G * C, M, T), dtype=s.dtype, device=s.device)
         rows, rows_per_clip, _ = _rows(s)
-        with torch.cuda.device(s.device):
-            capi.deltas_forward(s.data_ptr(), rows, rows_per_clip, T, None if lengths is None else lengths.data_ptr(), win_length, order,
-                                include_static, y.data_ptr(), torch.cuda.current_stream(s.device).cuda_stream)
+        _stage.launch(capi.deltas_forward, s, s.data_ptr(), rows, rows_per_clip, T, ptr(lengths), win_length, order, include_static, y.data_ptr())
         ctx.save_for_backward(lengths)
         ctx.win_length, ctx.order, ctx.include_static, ctx.in_shape = win_length, order, include_static, tuple(s.shape)
         return y
@@ -62,14 +61,11 @@ class _DeltasFunction(torch.autograd.Function):
         (lengths,) = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
             return (None,) * 5
-        if g.dtype != torch.float32:
-            raise RuntimeError(f"Deltas: the gradient of the output must be fp32, got {g.dtype}")
-        g = g.contiguous()
+        g = _stage.cotangent("Deltas", g)
         B, C, M, T = ctx.in_shape
         ds = torch.empty(ctx.in_shape, dtype=g.dtype, device=g.device)
-        with torch.cuda.device(g.device):
-            capi.deltas_backward(g.data_ptr(), B * C * M, C * M, T, None if lengths is None else lengths.data_ptr(), ctx.win_length, ctx.order,
-                                 ctx.include_static, ds.data_ptr(), torch.cuda.current_stream(g.device).cuda_stream)
+        _stage.launch(capi.deltas_backward, g, g.data_ptr(), B * C * M, C * M, T, ptr(lengths), ctx.win_length, ctx.order, ctx.include_static,
+                      ds.data_ptr())
         return (ds,) + (None,) * 4
 
 
@@ -98,33 +94,11 @@ class Deltas(nn.Module):
     def extra_repr(self) -> str:
         return f"win_length={self.win_length}, order={self.order}, include_static={self.include_static}"
 
-    def _lengths(self, s, frame_lengths):
-        """shape, dtype and device of ``frame_lengths``; returns them as the kernels read them (int32, contiguous).  Their values never
-        leave the device."""
-        if not torch.is_tensor(frame_lengths):
-            raise TypeError(f"Deltas: frame_lengths must be a 1-D integer tensor, got {type(frame_lengths).__name__}")
-        if frame_lengths.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"Deltas: frame_lengths must hold int32 or int64 values, got {frame_lengths.dtype}")
-        if frame_lengths.dim() != 1 or frame_lengths.shape[0] != s.shape[0]:
-            raise ValueError(f"Deltas: frame_lengths must have shape ({s.shape[0]},), got {tuple(frame_lengths.shape)}")
-        if frame_lengths.device != s.device:
-            raise RuntimeError(f"Deltas: frame_lengths is on {frame_lengths.device} but the input is on {s.device}")
-        if frame_lengths.dtype != torch.int32:
-            # int64 values clamped on the device before the narrowing: 2**32 + 5 must stay invalid (NaN), not wrap to 5
-            frame_lengths = frame_lengths.clamp(0, s.shape[-1] + 1).to(torch.int32)
-        return frame_lengths.contiguous()
-
     def forward(self, s: torch.Tensor, frame_lengths: torch.Tensor | None = None) -> torch.Tensor:
-        if not torch.is_tensor(s) or s.dim() not in (3, 4):
-            raise ValueError(f"Deltas: expected a (B, n_mels, T) or (B, C, n_mels, T) tensor, got {tuple(s.shape) if torch.is_tensor(s) else type(s).__name__}")
-        if s.dtype != torch.float32:
-            raise RuntimeError(f"Deltas takes an fp32 mel image, got {s.dtype}")
-        lengths = None if frame_lengths is None else self._lengths(s, frame_lengths)
-        if s.dim() == 3:
-            s = s.unsqueeze(1)
+        s = _stage.mel_image("Deltas", s)
+        lengths = _stage.frame_lengths_for_kernels("Deltas", s, frame_lengths)
         B, C, M, T = s.shape
         if s.numel() == 0:
             return s.new_empty((B, self.groups * C, M, T))
-        if not s.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: Deltas's input must be a CUDA/HIP tensor (no CPU fallback)")
+        _stage.require_gpu("Deltas", s)
         return _DeltasFunction.apply(s.contiguous(), lengths, self.win_length, self.order, self.include_static)

@@ -29,7 +29,8 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import capi
+from . import _stage, capi
+from ._stage import ptr
 
 ALPHA_RANGE = (0.0, 1.0)
 DELTA_MIN = 1e-3
@@ -45,9 +46,8 @@ class _PCENFunction(torch.autograd.Function):
         y = torch.empty_like(E)
         train = any(ctx.needs_input_grad[:5])
         M = torch.empty_like(E) if train else None
-        with torch.cuda.device(E.device):
-            capi.pcen_forward(E.data_ptr(), rows, n_mels, T, alpha.data_ptr(), delta.data_ptr(), r.data_ptr(), s.data_ptr(), eps,
-                              y.data_ptr(), M.data_ptr() if train else None, torch.cuda.current_stream(E.device).cuda_stream)
+        _stage.launch(capi.pcen_forward, E, E.data_ptr(), rows, n_mels, T, alpha.data_ptr(), delta.data_ptr(), r.data_ptr(), s.data_ptr(), eps,
+                      y.data_ptr(), ptr(M))
         if train:
             ctx.save_for_backward(E, M, alpha, delta, r, s)
         ctx.eps = eps
@@ -58,18 +58,14 @@ class _PCENFunction(torch.autograd.Function):
         E, M, alpha, delta, r, s = ctx.saved_tensors
         n_mels, T = E.shape[-2], E.shape[-1]
         rows = E.numel() // T if T else 0
-        g = g.contiguous()
-        if g.dtype != torch.float32:
-            raise RuntimeError(f"PCEN: the gradient of the output must be fp32, got {g.dtype}")
+        g = _stage.cotangent("PCEN", g)
         want_e, want_p = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:5])
         dE = torch.empty_like(E) if want_e else None
         # (an empty tensor launches nothing: its parameter gradients are empty sums)
         dparams = (torch.zeros if rows == 0 else torch.empty)((4, n_mels), dtype=torch.float32, device=E.device) if want_p else None
         scratch = torch.empty(max(capi.pcen_scratch_bytes(rows) // 4, 4), dtype=torch.float32, device=E.device) if want_p else None
-        with torch.cuda.device(E.device):
-            capi.pcen_backward(g.data_ptr(), E.data_ptr(), M.data_ptr(), rows, n_mels, T, alpha.data_ptr(), delta.data_ptr(), r.data_ptr(),
-                               s.data_ptr(), ctx.eps, dE.data_ptr() if want_e else None, dparams.data_ptr() if want_p else None,
-                               scratch.data_ptr() if want_p else None, torch.cuda.current_stream(E.device).cuda_stream)
+        _stage.launch(capi.pcen_backward, E, g.data_ptr(), E.data_ptr(), M.data_ptr(), rows, n_mels, T, alpha.data_ptr(), delta.data_ptr(),
+                      r.data_ptr(), s.data_ptr(), ctx.eps, ptr(dE), ptr(dparams), ptr(scratch))
         grads = [dparams[i] if ctx.needs_input_grad[1 + i] else None for i in range(4)]
         return (dE, *grads, None)
 
@@ -107,10 +103,8 @@ class PCEN(nn.Module):
         return self
 
     def forward(self, E: torch.Tensor) -> torch.Tensor:
-        if not torch.is_tensor(E) or E.dim() not in (3, 4):
-            raise ValueError(f"PCEN: expected a (B, n_mels, T) or (B, C, n_mels, T) tensor, got {tuple(E.shape) if torch.is_tensor(E) else type(E).__name__}")
-        if E.dtype != torch.float32:
-            raise RuntimeError(f"PCEN takes fp32 linear mel power (a layer with log=False, out_dtype=torch.float32), got {E.dtype}")
+        # (the checks only: this stage works on the tensor as it is given, 3-D or 4-D, and returns that shape)
+        _stage.mel_image("PCEN", E, "fp32 linear mel power (a layer with log=False, out_dtype=torch.float32)")
         if E.shape[-2] != self.n_mels:
             raise RuntimeError(f"PCEN was built for n_mels={self.n_mels} but dim -2 of the input has {E.shape[-2]} bands")
         for name in ("alpha", "delta", "r", "s"):
@@ -119,6 +113,5 @@ class PCEN(nn.Module):
                 raise RuntimeError(f"PCEN.{name} is on {p.device} but the input is on {E.device}; call pcen.to(x.device)")
             if p.dtype != torch.float32:
                 raise RuntimeError(f"PCEN.{name} must stay fp32, got {p.dtype}")
-        if not E.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: PCEN's input must be a CUDA/HIP tensor (no CPU fallback)")
+        _stage.require_gpu("PCEN", E)
         return _PCENFunction.apply(E.contiguous(), self.alpha, self.delta, self.r, self.s, self.eps)

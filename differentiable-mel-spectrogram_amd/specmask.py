@@ -35,9 +35,11 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import capi
+from . import _stage, capi
+from ._stage import ptr
 
 MAX_STRIPES = 8
+DTYPES = (torch.float32, torch.bfloat16)
 
 
 def _geometry(s):
@@ -58,19 +60,15 @@ class _SpecMaskFunction(torch.autograd.Function):
     @staticmethod
     def _apply(s, stripes, lengths, n_time, n_freq, fill, y):
         images, channels, n_mels, T = _geometry(s)
-        with torch.cuda.device(s.device):
-            capi.specmask_apply(s.data_ptr(), images * n_mels, n_mels, channels * n_mels, T, None if lengths is None else lengths.data_ptr(),
-                                stripes.data_ptr(), n_time, n_freq, s.dtype == torch.bfloat16, fill, y.data_ptr(),
-                                torch.cuda.current_stream(s.device).cuda_stream)
+        _stage.launch(capi.specmask_apply, s, s.data_ptr(), images * n_mels, n_mels, channels * n_mels, T, ptr(lengths), stripes.data_ptr(), n_time,
+                      n_freq, s.dtype == torch.bfloat16, fill, y.data_ptr())
 
     @staticmethod
     def backward(ctx, g):
         stripes, lengths = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
             return (None,) * 6
-        g = g.contiguous()
-        if g.dtype not in (torch.float32, torch.bfloat16):
-            raise RuntimeError(f"SpecMask: the gradient of the output must be fp32 or bf16, got {g.dtype}")
+        g = _stage.cotangent("SpecMask", g, DTYPES, "fp32 or bf16")
         ds = torch.empty_like(g)
         _SpecMaskFunction._apply(g, stripes, lengths, ctx.n_time, ctx.n_freq, 0.0, ds)
         return (ds,) + (None,) * 5
@@ -125,33 +123,14 @@ class SpecMask(nn.Module):
         return (f"time_mask_param={self.time_mask_param}, freq_mask_param={self.freq_mask_param}, time_stripes={self.time_stripes}, "
                 f"freq_stripes={self.freq_stripes}, max_time_fraction={self.max_time_fraction}, fill_value={self.fill_value}")
 
-    def _lengths(self, s, frame_lengths):
-        """shape, dtype and device of ``frame_lengths``; returns them as the kernels read them (int32, contiguous).  Their values never
-        leave the device."""
-        if not torch.is_tensor(frame_lengths):
-            raise TypeError(f"SpecMask: frame_lengths must be a 1-D integer tensor, got {type(frame_lengths).__name__}")
-        if frame_lengths.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"SpecMask: frame_lengths must hold int32 or int64 values, got {frame_lengths.dtype}")
-        if frame_lengths.dim() != 1 or frame_lengths.shape[0] != s.shape[0]:
-            raise ValueError(f"SpecMask: frame_lengths must have shape ({s.shape[0]},), got {tuple(frame_lengths.shape)}")
-        if frame_lengths.device != s.device:
-            raise RuntimeError(f"SpecMask: frame_lengths is on {frame_lengths.device} but the input is on {s.device}")
-        if frame_lengths.dtype != torch.int32:
-            # int64 values clamped on the device before the narrowing: 2**32 + 5 must stay invalid (NaN), not wrap to 5
-            frame_lengths = frame_lengths.clamp(0, s.shape[-1] + 1).to(torch.int32)
-        return frame_lengths.contiguous()
-
     def forward(self, s: torch.Tensor, frame_lengths: torch.Tensor | None = None) -> torch.Tensor:
-        if not torch.is_tensor(s) or s.dim() not in (3, 4):
-            raise ValueError(f"SpecMask: expected a (B, n_mels, T) or (B, C, n_mels, T) tensor, got {tuple(s.shape) if torch.is_tensor(s) else type(s).__name__}")
-        if s.dtype not in (torch.float32, torch.bfloat16):
-            raise RuntimeError(f"SpecMask takes an fp32 or bf16 mel image, got {s.dtype}")
+        # (the checks only: this stage works on the tensor as it is given, 3-D or 4-D, and returns that shape)
+        _stage.mel_image("SpecMask", s, "an fp32 or bf16 mel image", DTYPES)
         n_time, n_freq = self.time_stripes, self.freq_stripes
         if not self.training or n_time + n_freq == 0:
             return s
-        lengths = None if frame_lengths is None else self._lengths(s, frame_lengths)
-        if not s.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: SpecMask's input must be a CUDA/HIP tensor (no CPU fallback)")
+        lengths = _stage.frame_lengths_for_kernels("SpecMask", s, frame_lengths)
+        _stage.require_gpu("SpecMask", s)
         if self.rng_state.device != s.device:
             raise RuntimeError(f"SpecMask.rng_state is on {self.rng_state.device} but the input is on {s.device}; call mask.to(x.device)")
         if self.rng_state.dtype != torch.int64 or tuple(self.rng_state.shape) != (2,):
@@ -161,9 +140,7 @@ class SpecMask(nn.Module):
         s = s.contiguous()
         images, channels, n_mels, T = _geometry(s)
         stripes = torch.empty((images, n_time + n_freq, 2), dtype=torch.int32, device=s.device)
-        with torch.cuda.device(s.device):
-            capi.specmask_draw(images, channels, n_mels, T, None if lengths is None else lengths.data_ptr(), self.time_mask_param,
-                               self.time_permille, n_time, self.freq_mask_param, n_freq, self.rng_state.data_ptr(), True, stripes.data_ptr(),
-                               torch.cuda.current_stream(s.device).cuda_stream)
+        _stage.launch(capi.specmask_draw, s, images, channels, n_mels, T, ptr(lengths), self.time_mask_param, self.time_permille, n_time,
+                      self.freq_mask_param, n_freq, self.rng_state.data_ptr(), True, stripes.data_ptr())
         self._last = stripes
         return _SpecMaskFunction.apply(s, stripes, lengths, n_time, n_freq, self.fill_value)

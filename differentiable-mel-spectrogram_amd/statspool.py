@@ -27,12 +27,11 @@ stage into BandNorm or Deltas; a CPU fallback.
 """
 from __future__ import annotations
 
-import math
-
 import torch
 import torch.nn as nn
 
-from . import capi
+from . import _stage, capi
+from ._stage import ptr
 
 STATS = ("mean", "std", "max")         # the canonical order: the order of the output's groups; bit i of ``which`` selects STATS[i]
 
@@ -46,10 +45,7 @@ class _StatsPoolFunction(torch.autograd.Function):
         y = torch.empty((B, S * C, M), dtype=s.dtype, device=s.device)
         stats = torch.empty((rows, 2), dtype=torch.float64, device=s.device) if keep and which & capi.STATSPOOL_STD else None
         argmax = torch.empty((rows,), dtype=torch.int32, device=s.device) if keep and which & capi.STATSPOOL_MAX else None
-        with torch.cuda.device(s.device):
-            capi.statspool_forward(s.data_ptr(), rows, C * M, T, None if lengths is None else lengths.data_ptr(), which, eps, y.data_ptr(),
-                                   None if stats is None else stats.data_ptr(), None if argmax is None else argmax.data_ptr(),
-                                   torch.cuda.current_stream(s.device).cuda_stream)
+        _stage.launch(capi.statspool_forward, s, s.data_ptr(), rows, C * M, T, ptr(lengths), which, eps, y.data_ptr(), ptr(stats), ptr(argmax))
         ctx.save_for_backward(s if stats is not None else None, stats, argmax, lengths)
         ctx.which, ctx.in_shape = which, tuple(s.shape)
         return y
@@ -59,16 +55,11 @@ class _StatsPoolFunction(torch.autograd.Function):
         s, stats, argmax, lengths = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
             return (None,) * 5
-        if g.dtype != torch.float32:
-            raise RuntimeError(f"StatsPool: the gradient of the output must be fp32, got {g.dtype}")
-        g = g.contiguous()
+        g = _stage.cotangent("StatsPool", g)
         B, C, M, T = ctx.in_shape
         ds = torch.empty(ctx.in_shape, dtype=g.dtype, device=g.device)
-        with torch.cuda.device(g.device):
-            capi.statspool_backward(g.data_ptr(), None if s is None else s.data_ptr(), None if stats is None else stats.data_ptr(),
-                                    None if argmax is None else argmax.data_ptr(), B * C * M, C * M, T,
-                                    None if lengths is None else lengths.data_ptr(), ctx.which, ds.data_ptr(),
-                                    torch.cuda.current_stream(g.device).cuda_stream)
+        _stage.launch(capi.statspool_backward, g, g.data_ptr(), ptr(s), ptr(stats), ptr(argmax), B * C * M, C * M, T, ptr(lengths), ctx.which,
+                      ds.data_ptr())
         return (ds,) + (None,) * 4
 
 
@@ -80,20 +71,7 @@ class StatsPool(nn.Module):
 
     def __init__(self, stats=("mean", "std", "max"), eps: float = 1e-5):
         super().__init__()
-        if isinstance(stats, str):
-            stats = (stats,)
-        try:
-            given = list(stats)
-        except TypeError:
-            raise ValueError(f"StatsPool: stats must be a non-empty subset of {STATS}, got {stats!r}") from None
-        if not given or any(not isinstance(k, str) or k not in STATS for k in given):
-            raise ValueError(f"StatsPool: stats must be a non-empty subset of {STATS}, got {stats!r}")
-        if len(set(given)) != len(given):
-            raise ValueError(f"StatsPool: stats names a statistic twice: {stats!r}")
-        if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not math.isfinite(eps) or not eps > 0:
-            raise ValueError(f"StatsPool: eps must be a finite number > 0, got {eps!r}")
-        self.stats = tuple(k for k in STATS if k in given)
-        self.eps = float(eps)
+        self.stats, self.eps = _stage.pool_stats("StatsPool", STATS, stats, eps)
 
     @property
     def which(self) -> int:
@@ -108,36 +86,14 @@ class StatsPool(nn.Module):
     def extra_repr(self) -> str:
         return f"stats={self.stats}, eps={self.eps}"
 
-    def _lengths(self, s, frame_lengths):
-        """shape, dtype and device of ``frame_lengths``; returns them as the kernels read them (int32, contiguous).  Their values never
-        leave the device."""
-        if not torch.is_tensor(frame_lengths):
-            raise TypeError(f"StatsPool: frame_lengths must be a 1-D integer tensor, got {type(frame_lengths).__name__}")
-        if frame_lengths.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"StatsPool: frame_lengths must hold int32 or int64 values, got {frame_lengths.dtype}")
-        if frame_lengths.dim() != 1 or frame_lengths.shape[0] != s.shape[0]:
-            raise ValueError(f"StatsPool: frame_lengths must have shape ({s.shape[0]},), got {tuple(frame_lengths.shape)}")
-        if frame_lengths.device != s.device:
-            raise RuntimeError(f"StatsPool: frame_lengths is on {frame_lengths.device} but the input is on {s.device}")
-        if frame_lengths.dtype != torch.int32:
-            # int64 values clamped on the device before the narrowing: 2**32 + 5 must stay invalid (NaN), not wrap to 5
-            frame_lengths = frame_lengths.clamp(0, s.shape[-1] + 1).to(torch.int32)
-        return frame_lengths.contiguous()
-
     def forward(self, s: torch.Tensor, frame_lengths: torch.Tensor | None = None) -> torch.Tensor:
-        if not torch.is_tensor(s) or s.dim() not in (3, 4):
-            raise ValueError(f"StatsPool: expected a (B, n_mels, T) or (B, C, n_mels, T) tensor, got {tuple(s.shape) if torch.is_tensor(s) else type(s).__name__}")
-        if s.dtype != torch.float32:
-            raise RuntimeError(f"StatsPool takes an fp32 mel image, got {s.dtype}")
-        lengths = None if frame_lengths is None else self._lengths(s, frame_lengths)
-        if s.dim() == 3:
-            s = s.unsqueeze(1)
+        s = _stage.mel_image("StatsPool", s)
+        lengths = _stage.frame_lengths_for_kernels("StatsPool", s, frame_lengths)
         B, C, M, T = s.shape
         if B * C * M == 0:
             return s.new_empty((B, self.groups * C, M))
         if T == 0:
             raise ValueError("StatsPool: the input has no frames (T = 0): there is nothing to pool")
-        if not s.is_cuda:
-            raise RuntimeError("dmel_amd runs on MI355X only: StatsPool's input must be a CUDA/HIP tensor (no CPU fallback)")
+        _stage.require_gpu("StatsPool", s)
         keep = torch.is_grad_enabled() and s.requires_grad       # (asked here: inside an autograd function the grad mode is always off)
         return _StatsPoolFunction.apply(s.contiguous(), lengths, self.which, self.eps, keep)

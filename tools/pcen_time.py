@@ -20,48 +20,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))      # the torch restatement of the formulas is the tests' (tests/pcen_cases.py): one copy
 import pcen_cases as P  # noqa: E402
 from dmel_amd import PCEN  # noqa: E402
+from _stage_timing import ROUNDS, _alternated, _graphed  # noqa: E402
 
 DEV = "cuda:0"
 SHAPES = [(256, 1, 128, 32), (64, 1, 128, 501)]
-ROUNDS = 5
-
-
-def _train(fn, calls):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) * 1e3 / calls          # us per call
-
-
-def _alternated(variants):
-    """{name: (fn, calls per train)} -> {name: [us per call of each train]}, the variants taking turns"""
-    for fn, _ in variants.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in variants}
-    for _ in range(ROUNDS):
-        for k, (fn, calls) in variants.items():
-            times[k].append(_train(fn, calls))
-    return times
-
-
-def _graphed(fn, per_graph=20):
-    """``per_graph`` calls of fn captured into one graph: its replay is the device's time for them, without the host's"""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        fn()
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(per_graph):
-            fn()
-    return graph.replay
 
 
 def main():
