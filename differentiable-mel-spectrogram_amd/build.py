@@ -19,7 +19,7 @@ OBJ_DIR = os.path.join(PKG_DIR, "build")
 # the fused forward's sources are compiled FWD_PARTS times each (-DDMEL_FWD_SPLIT -DDMEL_FWD_PART=k): their large instantiations in parallel
 SPLIT_SOURCES = ["dmel_fwd.hip", "dmel_fwd_len.hip", "dmel_fwd_band.hip", "dmel_fwd_multi_len.hip", "dmel_fwd_band_len.hip", "dmel_fwd_fb_len.hip"]
 FWD_PARTS = 4
-SOURCES = SPLIT_SOURCES + ["dmel_aux.hip", "dmel_big.hip", "dmel_xgrad.hip", "dmel_xgrad_len.hip", "dmel_xgrad_band.hip", "dmel_xgrad_klen.hip", "dmel_pcen.hip", "dmel_bandnorm.hip", "dmel_specmask.hip", "dmel_deltas.hip", "dmel_statspool.hip", "dmel_attnpool.hip", "dmel_api.cpp", "dmel_comm.cpp"]
+SOURCES = SPLIT_SOURCES + ["dmel_aux.hip", "dmel_big.hip", "dmel_xgrad.hip", "dmel_xgrad_len.hip", "dmel_xgrad_band.hip", "dmel_xgrad_klen.hip", "dmel_pcen.hip", "dmel_bandnorm.hip", "dmel_specmask.hip", "dmel_deltas.hip", "dmel_statspool.hip", "dmel_attnpool.hip", "dmel_api.cpp", "dmel_tables.cpp", "dmel_comm.cpp"]
 PUBLIC_HEADER = os.path.join(os.path.dirname(PKG_DIR), "include", "dmel.h")
 # every object is stale when any shared file under csrc/ is newer: a new header needs no entry here
 HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc"))) + [PUBLIC_HEADER]

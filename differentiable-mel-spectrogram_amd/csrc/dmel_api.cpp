@@ -1,13 +1,16 @@
 // dmel_api.cpp -- host side of libdmel_hip.so: the C ABI of include/dmel.h.
 //
-// Owns everything that is not a kernel: the HTK mel filterbank of models.py:42-48 and its packing into non-zero MFMA B-fragments, FFT twiddle tables,
-// per-plan workspace, argument checking and kernel dispatch.  No torch types, no oracle code.  In order: tables; scratch and workspaces; the forward
+// Owns everything that is not a kernel or table arithmetic: per-plan workspace, argument checking and kernel dispatch.  No torch types, no oracle
+// code.  In order: tables (the builders of dmel_tables.h compute them on the host -- the HTK mel filterbank of models.py:42-48, its packing into
+// non-zero MFMA B-fragments, twiddles, the wave-local schedule --; upload() is the one place that allocates their device copies and records them with
+// their owner; build_tables chooses the bank, calls, uploads); scratch and workspaces; the forward
 // (FwdCall describes a call, launch_forward_n issues it for one n_fft through forward_big / _naive / _fused); the host steps of the sync-free lambd
 // tracking around dmel_lamtrack.h, once for K tracked values; the extern "C" entry points, which check, fill a call description by name and hand it on.
 #include "../../include/dmel.h"
 #include "dmel_kernels.h"
 #include "dmel_lamtrack.h"
 #include "dmel_stage.h"
+#include "dmel_tables.h"
 
 #include <algorithm>
 #include <cmath>
@@ -50,15 +53,23 @@ namespace {
             return fail(DMEL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
     } while (0)
 
-// torch.linspace (fp32, CPU): symmetric evaluation around the midpoint
-void linspace_f32(float start, float end, int steps, std::vector<float>& out)
+// Device copies of host tables.  upload() is the one place that allocates them: it records every allocation with its owner, which
+// frees what was uploaded into it.  A second pointer to an uploaded table (tw1p == tw1) is an alias, not an owner.
+struct DeviceTables {
+    std::vector<void*> owned;
+    void release() { for (void* q : owned) (void)hipFree(q); owned.clear(); }
+};
+
+// *dev = a device copy of `host`, at least min_elems elements long (elements beyond host.size() are left unwritten)
+template <class T, class D> dmel_status upload(DeviceTables* owner, const std::vector<T>& host, D** dev, size_t min_elems = 0)
 {
-    out.resize(steps);
-    if (steps == 1) { out[0] = start; return; }
-    const float step = (end - start) / (float)(steps - 1);
-    const int half = steps / 2;
-    for (int i = 0; i < steps; ++i)
-        out[i] = i < half ? std::fmaf(step, (float)i, start) : std::fmaf(-step, (float)(steps - i - 1), end);   // (torch's CPU kernel fuses the multiply-add: tests/golden/g8_fbanks.npz)
+    if (host.empty() && min_elems == 0) return DMEL_OK;       // no such table: the pointer stays as it is
+    void* d = nullptr;
+    DMEL_HIP(hipMalloc(&d, std::max(host.size(), min_elems) * sizeof(T)));
+    owner->owned.push_back(d);
+    *dev = static_cast<D*>(d);
+    if (!host.empty()) DMEL_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+    return DMEL_OK;
 }
 
 struct NfftTables {
@@ -89,14 +100,8 @@ struct NfftTables {
     int wl_phases = 0, wl_total4 = 0;
     int wl_len4[dmel::kWlMaxPhases] = {};
     int wl_mg[dmel::kWlMaxPhases] = {};   // per phase: bit 0 / 1 = merge round 1 / 2 is needed
-    void release()
-    {
-        if (tw1p == tw1) tw1p = nullptr;
-        if (tw2p == tw2) tw2p = nullptr;
-        void* ptrs[] = {tw1, tw2, tw1p, tw2p, ent_b, ent_pre, tile_ranges, fb_dense, tw_long, fbT, band, rowband, rowpk, ent_h, fb_nyq, wl_b4, wl_lane, wl_merge};
-        for (void* q : ptrs) (void)hipFree(q);
-        *this = NfftTables();
-    }
+    DeviceTables dev;            // what was uploaded into these tables
+    void release() { dev.release(); *this = NfftTables(); }
 };
 
 }  // namespace
@@ -120,6 +125,7 @@ struct dmel_plan {
     std::map<int, float2*> big_wodd;   // per even N: exp(-2 pi i n / N), n < N/2 (split mode of the big kernel)
     std::map<int, BigTab> big_tabs;
     std::map<int, float2*> big_tw;
+    DeviceTables big_dev;              // owner of the three maps' tables
     float2* big_win = nullptr; size_t big_win_n = 0;
     float2* big_z = nullptr; size_t big_z_n = 0;
     float* fbw = nullptr;          // workspace of dmel_backward_fb (spectrogram (B, F, T) + slice partials) and dmel_backward_x
@@ -184,46 +190,7 @@ void prof_span(dmel_plan* pl, size_t a, size_t b, int kind)
     if (a != (size_t)-1 && b != (size_t)-1) pl->spans.push_back({a, b, kind});
 }
 
-// The contraction phase of an 8-wave plan (and of a 4-wave plan with up to four mel tiles per group): wave tl owns tile tl; the
-// units (4 k-steps = 16 bins) of a tile beyond a common limit L go, in contiguous pieces, to the run 1 of other waves (one piece per
-// wave).  L = the smallest limit for which "largest remainder first onto largest spare first" fits.  own[w]: units wave w takes of its
-// own tile; pieces: (helper wave, tile, first unit, units).  Pure host arithmetic (dmel_contraction_partition_host exposes it to tests).
-struct Piece { int wave, tile, a, n; };
-void deal_ksteps(const int* units, int ntg, int W, int* own, std::vector<Piece>* pieces)
-{
-    int total = 0, umax = 0;
-    for (int tl = 0; tl < ntg; ++tl) { total += units[tl]; umax = std::max(umax, units[tl]); }
-    for (int L = std::max(1, (total + W - 1) / W); ; ++L) {
-        pieces->clear();
-        int spare[8], rem[8];
-        bool used[8] = {false, false, false, false, false, false, false, false};
-        for (int w = 0; w < 8; ++w) {
-            if (w >= W) { own[w] = 0; rem[w] = 0; spare[w] = 0; used[w] = true; continue; }
-            own[w] = w < ntg ? std::min(units[w], L) : 0;
-            rem[w] = w < ntg ? units[w] - own[w] : 0;
-            spare[w] = L - own[w];
-        }
-        bool ok = true;
-        for (;;) {
-            int t = -1;
-            for (int tl = 0; tl < ntg; ++tl) if (rem[tl] > 0 && (t < 0 || rem[tl] > rem[t])) t = tl;
-            if (t < 0) break;
-            int h = -1;
-            for (int w = 0; w < 8; ++w) if (!used[w] && w != t && spare[w] > 0 && (h < 0 || spare[w] > spare[h])) h = w;
-            if (h < 0) { ok = false; break; }
-            const int n = std::min(spare[h], rem[t]);
-            pieces->push_back({h, t, units[t] - rem[t], n});
-            used[h] = true; rem[t] -= n;
-        }
-        if (ok) return;
-        if (L >= umax) {                      // (not reached: at L = umax nothing is left over)
-            pieces->clear();
-            for (int w = 0; w < 8; ++w) own[w] = w < ntg ? units[w] : 0;
-            return;
-        }
-    }
-}
-
+// the tables of one n_fft: look up the cache, choose the bank, call the builders (dmel_tables.h), upload, insert
 dmel_status build_tables(dmel_plan* pl, int N, NfftTables** out)
 {
     auto it = pl->tables.find(N);
@@ -235,383 +202,47 @@ dmel_status build_tables(dmel_plan* pl, int N, NfftTables** out)
     } guard{&tb};
     tb.n_fft = N;
     tb.F = N / 2 + 1;
-    const int M = pl->cfg.n_mels;
-    std::vector<float> fb((size_t)tb.F * M);
+    const int F = tb.F, M = pl->cfg.n_mels;
+    dmel_status st = DMEL_OK;
+#define DMEL_UP(...) do { if ((st = upload(&tb.dev, __VA_ARGS__)) != DMEL_OK) return st; } while (0)
+    std::vector<float> fb((size_t)F * M);
     auto cit = pl->custom_fb.find(N);
-    if (pl->dense_dev.count(N)) {
-        std::fill(fb.begin(), fb.end(), 1.0f);        // structure only: every block present; dmel_plan_set_filterbank_dev fills the values
-    } else if (cit != pl->custom_fb.end()) {
-        fb = cit->second;
-    } else {
-        dmel_status st = dmel_mel_fbanks_host(tb.F, pl->cfg.f_min, pl->f_max, M, pl->cfg.sample_rate, fb.data());
-        if (st != DMEL_OK) return st;
-    }
-    DMEL_HIP(hipMalloc(&tb.fb_dense, fb.size() * sizeof(float)));
-    DMEL_HIP(hipMemcpy(tb.fb_dense, fb.data(), fb.size() * sizeof(float), hipMemcpyHostToDevice));
-
-    {
-        std::vector<float2> tw((size_t)std::max(1, N / 2));
-        for (int k = 0; k < N / 2; ++k) {
-            const double th = -2.0 * M_PI * (double)k / (double)N;
-            tw[k] = make_float2((float)std::cos(th), (float)std::sin(th));
-        }
-        DMEL_HIP(hipMalloc(&tb.tw_long, tw.size() * sizeof(float2)));
-        DMEL_HIP(hipMemcpy(tb.tw_long, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
-        std::vector<int2> rowband(tb.F);
-        for (int f = 0; f < tb.F; ++f) {
-            int lo = M, hi = 0;
-            for (int m = 0; m < M; ++m)
-                if (fb[(size_t)f * M + m] != 0.f) { lo = std::min(lo, m); hi = m + 1; }
-            rowband[f] = make_int2(hi > lo ? lo : 0, hi > lo ? hi : 0);
-        }
-        DMEL_HIP(hipMalloc(&tb.rowband, rowband.size() * sizeof(int2)));
-        DMEL_HIP(hipMemcpy(tb.rowband, rowband.data(), rowband.size() * sizeof(int2), hipMemcpyHostToDevice));
-        std::vector<float4> rowpk(tb.F);
-        for (int f = 0; f < tb.F; ++f) {
-            const int b0 = rowband[f].x, nb = rowband[f].y - rowband[f].x;
-            float bits0, bitsn;
-            std::memcpy(&bits0, &b0, 4); std::memcpy(&bitsn, &nb, 4);
-            rowpk[f] = make_float4(nb > 0 ? fb[(size_t)f * M + b0] : 0.f, nb > 1 ? fb[(size_t)f * M + b0 + 1] : 0.f, bits0, bitsn);
-            if (nb > 2) tb.long_rows = true;
-        }
-        DMEL_HIP(hipMalloc(&tb.rowpk, rowpk.size() * sizeof(float4)));
-        DMEL_HIP(hipMemcpy(tb.rowpk, rowpk.data(), rowpk.size() * sizeof(float4), hipMemcpyHostToDevice));
-    }
-    const bool is_pow2 = (N & (N - 1)) == 0;
-    if (N > dmel::kMaxFastNfft || !is_pow2) {
-        std::vector<float> fbT((size_t)M * tb.F);
-        std::vector<int2> band(M);
-        for (int m = 0; m < M; ++m) {
-            int lo = tb.F, hi = 0;
-            for (int f = 0; f < tb.F; ++f) {
-                const float c = fb[(size_t)f * M + m];
-                fbT[(size_t)m * tb.F + f] = c;
-                if (c != 0.f) { lo = std::min(lo, f); hi = f + 1; }
-            }
-            band[m] = make_int2(hi > lo ? lo : 0, hi > lo ? hi : 0);
-        }
-        DMEL_HIP(hipMalloc(&tb.fbT, fbT.size() * sizeof(float)));
-        DMEL_HIP(hipMemcpy(tb.fbT, fbT.data(), fbT.size() * sizeof(float), hipMemcpyHostToDevice));
-        DMEL_HIP(hipMalloc(&tb.band, band.size() * sizeof(int2)));
-        DMEL_HIP(hipMemcpy(tb.band, band.data(), band.size() * sizeof(int2), hipMemcpyHostToDevice));
-    } else if (N >= dmel::kMinFastNfft) {
-        // twiddle tables of a plan (R, C): tw1 (R, G) = w_N^(lg q), tw2 (R, C) = w_G^(r p1)
-        auto make_tw = [&](bool pair, float2** d1, float2** d2) -> dmel_status {
-            int R = 0, C = 0;
-            if (!dmel::forward_plan_rc(N, pair, &R, &C)) return fail(DMEL_ERR_UNSUPPORTED, "n_fft has no FFT plan");
-            const int G = N / R;
-            std::vector<float2> tw1((size_t)R * G), tw2((size_t)R * C);
-            for (int q = 0; q < R; ++q)
-                for (int lg = 0; lg < G; ++lg) {
-                    const double th = -2.0 * M_PI * (double)((long long)lg * q % N) / (double)N;
-                    tw1[(size_t)q * G + lg] = make_float2((float)std::cos(th), (float)std::sin(th));
-                }
-            for (int p1 = 0; p1 < R; ++p1)
-                for (int r = 0; r < C; ++r) {
-                    const double th = -2.0 * M_PI * (double)(r * p1 % G) / (double)G;
-                    tw2[(size_t)p1 * C + r] = make_float2((float)std::cos(th), (float)std::sin(th));
-                }
-            DMEL_HIP(hipMalloc(d1, tw1.size() * sizeof(float2)));
-            DMEL_HIP(hipMemcpy(*d1, tw1.data(), tw1.size() * sizeof(float2), hipMemcpyHostToDevice));
-            DMEL_HIP(hipMalloc(d2, tw2.size() * sizeof(float2)));
-            DMEL_HIP(hipMemcpy(*d2, tw2.data(), tw2.size() * sizeof(float2), hipMemcpyHostToDevice));
-            return DMEL_OK;
-        };
-        {
-            dmel_status stw = make_tw(false, &tb.tw1, &tb.tw2);
-            if (stw != DMEL_OK) return stw;
-            int r0 = 0, c0 = 0, r1 = 0, c1 = 0;
-            dmel::forward_plan_rc(N, false, &r0, &c0); dmel::forward_plan_rc(N, true, &r1, &c1);
-            if (r0 == r1 && c0 == c1) { tb.tw1p = tb.tw1; tb.tw2p = tb.tw2; }
-            else if ((stw = make_tw(true, &tb.tw1p, &tb.tw2p)) != DMEL_OK) return stw;
-        }
-
-        // Non-zero 4 x 16 blocks of the filterbank as MFMA B-fragments.  Mel tiles are handled in
-        // groups of 8 (128 mel bands); inside a group a 4-wave plan gives wave w tiles w and 7-w (the HTK bands
-        // widen with frequency, so pairing a narrow and a wide tile balances the four waves), an 8-wave plan
-        // deals the k-steps themselves (below).
-        tb.KS = (tb.F + 3) / 4;
-        tb.NT = (M + 15) / 16;
-        tb.groups = (tb.NT + 7) / 8;
-        tb.n_dense = tb.KS * tb.NT;
-        const int waves = dmel::forward_waves(N);
-        std::vector<int4> ranges((size_t)tb.groups * waves * 2, make_int4(0, 0, 0, -1));
-        std::vector<float> bfr;
-        tb.n_entries = 0;
-        // run of k-steps [ks_a, ks_b) of mel tile `tile` appended to the B-fragment stream
-        auto emit = [&](int tile, int ks_a, int ks_b) {
-            int4 tr = make_int4(ks_a, ks_b - ks_a, (int)bfr.size(), tile);
-            for (int ks = ks_a; ks < ks_b; ++ks)
-                for (int l = 0; l < 64; ++l) {
-                    const int f = 4 * ks + (l >> 4), m = 16 * tile + (l & 15);
-                    bfr.push_back((f < tb.F && m < M) ? fb[(size_t)f * M + m] : 0.f);
-                }
-            return tr;
-        };
-        for (int g = 0; g < tb.groups; ++g) {
-            const int ntg = std::min(8, tb.NT - 8 * g);
-            // the band of a mel tile is one contiguous run of k-steps: [first, first + nks) in units of 4 k-steps (16 bins)
-            int first_of[8], units[8];
-            for (int tl = 0; tl < ntg; ++tl) {
-                const int tile = 8 * g + tl;
-                int first = tb.KS, last = -1;
-                for (int ks = 0; ks < tb.KS; ++ks)
-                    for (int l = 0; l < 64; ++l) {
-                        const int f = 4 * ks + (l >> 4), m = 16 * tile + (l & 15);
-                        if (f < tb.F && m < M && fb[(size_t)f * M + m] != 0.f) { first = std::min(first, ks); last = std::max(last, ks); }
-                    }
-                if (last < first) { first_of[tl] = 0; units[tl] = 0; continue; }      // an all-zero tile still needs its outputs written
-                tb.n_entries += last - first + 1;
-                first = first / 4 * 4;                       // groups of 4 k-steps start at multiples of 16 bins
-                first_of[tl] = first; units[tl] = (last - first + 1 + 3) / 4;
-            }
-            if (waves == 8 || (ntg <= waves && g < 32)) {         // (FwdParams::xch_groups is a 32-bit mask: groups beyond it keep whole tiles -- ADVICE r04)
-                // (4-wave plans, n_fft <= 512: only when every tile has a wave of its own -- up to 64 mels, the reference's experiments --
-                // since run 1 is then free to carry a piece; with more tiles wave w owns tiles w and 7 - w whole, as before)
-                // Wave tl owns tile tl (run 0: it writes the tile's outputs).  The HTK bands widen with frequency -- at 128 mels the last
-                // tile has five times the k-steps of the first, at 64 mels four tiles meet eight waves -- so the k-steps of the wide
-                // tiles beyond a common limit L are dealt, in contiguous pieces, to the run 1 of waves with narrow or no tiles of their
-                // own (one piece per wave; their sums reach the owner through LDS, dmel_fwd_kernel's exchange).  L = the smallest
-                // limit for which largest-remainder-first onto largest-spare-first fits.  (Round 3 split every tile in two halves,
-                // wave tl and 7 - tl: the slowest wave carried 24 k-steps at BASELINE config 2 where 19.5 is the mean, 56 / 36.5 at
-                // config 5, 120 / 68 at the reference's ESC-50 shape at n_fft 4096.)
-                const int W = waves;
-                int own[8];
-                std::vector<Piece> pieces;
-                deal_ksteps(units, ntg, W, own, &pieces);
-                int mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (const Piece& pc : pieces) mask[pc.tile] |= 1 << pc.wave;
-                for (int tl = 0; tl < ntg; ++tl) {
-                    int4 tr = units[tl] > 0 ? emit(8 * g + tl, first_of[tl], first_of[tl] + 4 * own[tl]) : make_int4(0, 0, 0, 8 * g + tl);
-                    tr.w |= mask[tl] << 16;
-                    ranges[(size_t)(g * W + tl) * 2 + 0] = tr;
-                }
-                for (const Piece& pc : pieces) {
-                    int4 tr = emit(8 * g + pc.tile, first_of[pc.tile] + 4 * pc.a, first_of[pc.tile] + 4 * (pc.a + pc.n));
-                    tr.w |= 1 << 30;                                   // a piece: summed into its owner's tile, not written by this wave
-                    ranges[(size_t)(g * W + pc.wave) * 2 + 1] = tr;
-                }
-                if (W != 8 && !pieces.empty()) tb.xch_groups |= 1u << g;       // g < 32 here
-            } else {
-                // 4 waves: wave w owns tiles w and 7-w whole
-                for (int tl = 0; tl < ntg; ++tl) {
-                    const int w = tl < 4 ? tl : 7 - tl, loc = tl < 4 ? 0 : 1;
-                    ranges[(size_t)(g * 4 + w) * 2 + loc] = units[tl] > 0 ? emit(8 * g + tl, first_of[tl], first_of[tl] + 4 * units[tl]) : make_int4(0, 0, 0, 8 * g + tl);
-                }
-            }
-        }
-        tb.ent_b_floats = (int)bfr.size();
-        if ((cit != pl->custom_fb.end() || pl->dense_dev.count(N)) && dmel::forward_has_hsplit(N)) {
-            // the same matrix as B fragments of v_mfma_f32_16x16x32_bf16, split into two bf16 halves (DMEL_FLAG_MFMA_BF16X3):
-            // [(tile * (N/64) + kstep) * 2 + (hi | lo)][lane][8]: lane l holds rows 32 kstep + 8 (l >> 4) + e of column 16 tile + (l & 15)
-            const int ks32 = N / 64;
-            auto bf16_rne = [](float v) -> unsigned short {
-                unsigned u; std::memcpy(&u, &v, 4);
-                if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);      // NaN stays NaN
-                return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-            };
-            std::vector<unsigned short> eh((size_t)tb.NT * ks32 * 2 * 64 * 8);
-            for (int tile = 0; tile < tb.NT; ++tile)
-                for (int ks = 0; ks < ks32; ++ks)
-                    for (int l = 0; l < 64; ++l)
-                        for (int e = 0; e < 8; ++e) {
-                            const int f = 32 * ks + 8 * (l >> 4) + e, m = 16 * tile + (l & 15);
-                            const float v = (m < M) ? fb[(size_t)f * M + m] : 0.f;
-                            const unsigned short hi = bf16_rne(v);
-                            unsigned hu = (unsigned)hi << 16; float hf; std::memcpy(&hf, &hu, 4);
-                            const unsigned short lo = bf16_rne(v - hf);
-                            const size_t base = ((size_t)(tile * ks32 + ks) * 2) * 64 * 8;
-                            eh[base + (size_t)l * 8 + e] = hi;
-                            eh[base + 64 * 8 + (size_t)l * 8 + e] = lo;
-                        }
-            DMEL_HIP(hipMalloc(&tb.ent_h, eh.size() * sizeof(unsigned short)));
-            DMEL_HIP(hipMemcpy(tb.ent_h, eh.data(), eh.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-            DMEL_HIP(hipMalloc(&tb.fb_nyq, (size_t)M * sizeof(float)));
-            DMEL_HIP(hipMemcpy(tb.fb_nyq, fb.data() + (size_t)(tb.F - 1) * M, (size_t)M * sizeof(float), hipMemcpyHostToDevice));
-        }
-        if (dmel::forward_has_wlc(N) && (M + 3) / 4 <= 16 * dmel::kWlMaxPhases) {
-            // kTrainW: the schedule of the wave-local contraction (FwdParams::wl_*).  A quad = 4 consecutive mel bands; its band =
-            // the bins where any of them is non-zero.  A block of the 4x4x1 MFMA walks one PIECE of a band, one bin per step; a phase
-            // holds 16 pieces and is as long as its longest, rounded up to 4 steps.  Whole quads are one piece.  Where a wave holds ONE
-            // frame (n_fft >= 2048: two of the four rows idle, phases 100-330 steps long) a wide quad is split over 2 or 4 blocks of one
-            // phase -- pieces of its band, B operands restricted to the piece -- and the partial sums are merged across lanes after the
-            // phase's loop (wl_merge: one or two rounds of ds_bpermute + add; the final piece's lanes carry the mel band).
-            const int Q = (M + 3) / 4;
-            struct Piece { int quad, lo, w, group, idx, s; };
-            std::vector<int> first(Q, 0), width(Q, 0);
-            for (int q = 0; q < Q; ++q) {
-                int lo = tb.F, hi = -1;
-                for (int f = 0; f < tb.F; ++f)
-                    for (int j = 0; j < 4 && 4 * q + j < M; ++j)
-                        if (fb[(size_t)f * M + 4 * q + j] != 0.f) { lo = std::min(lo, f); hi = std::max(hi, f); }
-                first[q] = hi >= lo ? lo : 0; width[q] = hi >= lo ? hi - lo + 1 : 0;
-            }
-            const bool may_split = dmel::forward_wlc_one_frame(N) && !pl->dense_dev.count(N) && std::getenv("DMEL_WLC_NOSPLIT") == nullptr;
-            // split factors: pieces no longer than w*, s in {1, 2, 4}; w* by exhaustive search over the step count of the resulting phases
-            auto make_groups = [&](int wstar, std::vector<std::vector<Piece>>& phases) -> int {
-                struct Grp { int quad, s, len; };
-                std::vector<Grp> gs;
-                for (int q = 0; q < Q; ++q) {
-                    int sp = 1;
-                    while (may_split && (width[q] + sp - 1) / sp > wstar && sp < 4) sp *= 2;
-                    gs.push_back({q, sp, (width[q] + sp - 1) / sp});
-                }
-                std::stable_sort(gs.begin(), gs.end(), [](const Grp& a, const Grp& b) { return a.len > b.len; });
-                phases.clear();
-                std::vector<int> used;
-                int gid = 0;
-                for (const Grp& g : gs) {
-                    size_t ph = 0;
-                    while (ph < phases.size() && used[ph] + g.s > 16) ++ph;
-                    if (ph == phases.size()) { phases.emplace_back(); used.push_back(0); }
-                    for (int i = 0; i < g.s; ++i) {
-                        const int lo = first[g.quad] + i * g.len;
-                        const int w = std::max(0, std::min(g.len, first[g.quad] + width[g.quad] - lo));
-                        phases[ph].push_back({g.quad, lo, w, gid, i, g.s});
-                    }
-                    used[ph] += g.s; ++gid;
-                }
-                if ((int)phases.size() > dmel::kWlMaxPhases) return 1 << 30;
-                // cost in steps: the phases' lengths plus 40 per phase -- measured, not derived: config 3's three phases of 100 steps in all
-                // run as long as its two phases of 136 (45.9-46.2 against 45.5-46.1 us, 40 more vector instructions per wave: kept whole),
-                // config 5's three of 104 beat its two of 160 by 4 % (66.1-67.9 against 68.9-71.0 us); and -- decisively -- the staged epilogue
-                // is lost beyond four phases (config 3 in five phases: 53.0 us)
-                int total = 0;
-                for (auto& ph : phases) { int wm = 0; for (auto& pc : ph) wm = std::max(wm, pc.w); total += std::max(4, (wm + 3) / 4 * 4) + 40 + (ph.size() && ph[0].s > 1 ? 2 : 0); }
-                if ((int)phases.size() > 4) total += 1000;
-                return total;
-            };
-            std::vector<std::vector<Piece>> phases;
-            {
-                int wmaxq = 4;
-                for (int q = 0; q < Q; ++q) wmaxq = std::max(wmaxq, width[q]);
-                int best = 1 << 30, best_w = wmaxq;
-                if (may_split)
-                    for (int wstar = 4; wstar <= wmaxq; ++wstar) {
-                        std::vector<std::vector<Piece>> trial;
-                        const int t = make_groups(wstar, trial);
-                        if (t < best) { best = t; best_w = wstar; }
-                    }
-                make_groups(best_w, phases);
-                // (narrowest phase first, as before: the lane table and the first B groups of phase 0 are the ones requested early)
-                std::reverse(phases.begin(), phases.end());
-            }
-            tb.wl_phases = (int)phases.size();
-            std::vector<int2> lanes((size_t)tb.wl_phases * 64);
-            std::vector<int> merge((size_t)tb.wl_phases * 64, 0);
-            std::vector<float4> b4;
-            tb.wl_total4 = 0;
-            for (int ph = 0; ph < tb.wl_phases; ++ph) {
-                const std::vector<Piece>& pcs = phases[ph];
-                const int nq = (int)pcs.size();
-                int wmax = 0;
-                for (int i = 0; i < nq; ++i) wmax = std::max(wmax, pcs[i].w);
-                // Bank conflicts of the A operand reads (dmel_kernels.h, slot_stride_f2): the 8 blocks of each 32-lane group must sit
-                // at bins that differ modulo 8.  A block may start anywhere in [lo, hi] -- the piece must fit into the phase's L steps
-                // and the run must not pass bin F - 1 -- so each piece is matched to one of the 16 (group, residue) places it can
-                // reach (augmenting paths; 16 x 16); if that fails the phase gets four more steps.
-                int L = std::max(4, (wmax + 3) / 4 * 4), slot_of[16], k0_of[16];
-                for (;; L += 4) {
-                    int lo[16], hi[16], owner[16];
-                    for (int i = 0; i < nq; ++i) {
-                        hi[i] = std::max(0, std::min(pcs[i].lo, tb.F - L));
-                        lo[i] = std::min(hi[i], std::max(0, pcs[i].lo + pcs[i].w - L));
-                    }
-                    auto can = [&](int i, int r) { for (int k = hi[i]; k >= lo[i] && k > hi[i] - 8; --k) if ((k & 7) == r) return true; return false; };
-                    std::fill(owner, owner + 16, -1);
-                    bool seen[16];
-                    std::function<bool(int)> place = [&](int i) -> bool {
-                        for (int sl = 0; sl < 16; ++sl) {
-                            if (seen[sl] || !can(i, sl & 7)) continue;
-                            seen[sl] = true;
-                            if (owner[sl] < 0 || place(owner[sl])) { owner[sl] = i; return true; }
-                        }
-                        return false;
-                    };
-                    bool ok = true;
-                    for (int i = 0; i < nq && ok; ++i) {               // longest (least freedom) first
-                        std::fill(seen, seen + 16, false);
-                        ok = place(i);
-                    }
-                    if (!ok && L < wmax + 64) continue;
-                    std::fill(slot_of, slot_of + 16, -1);
-                    if (ok) { for (int sl = 0; sl < 16; ++sl) if (owner[sl] >= 0) slot_of[owner[sl]] = sl; }
-                    else {                                        // (not reached with 16 places for 16 pieces: any residue has two)
-                        bool used[16] = {};
-                        for (int i = 0; i < nq; ++i) for (int sl = 0; sl < 16; ++sl) if (!used[sl]) { used[sl] = true; slot_of[i] = sl; break; }
-                    }
-                    for (int i = 0; i < nq; ++i) {
-                        k0_of[i] = hi[i];
-                        for (int k = hi[i]; k >= lo[i] && k > hi[i] - 8; --k) if ((k & 7) == (slot_of[i] & 7)) { k0_of[i] = k; break; }
-                    }
-                    break;
-                }
-                const int n4 = wmax > 0 ? L / 4 : 0;
-                tb.wl_len4[ph] = n4;
-                const size_t base = b4.size();
-                b4.resize(base + (size_t)n4 * 64, make_float4(0.f, 0.f, 0.f, 0.f));
-                for (int sl = 0; sl < 16; ++sl)                  // places nobody took: no mel band, a bin of their residue
-                    for (int j = 0; j < 4; ++j) { lanes[(size_t)ph * 64 + 4 * sl + j] = make_int2(8 * (sl & 7), -1); merge[(size_t)ph * 64 + 4 * sl + j] = (4 * sl + j) | ((4 * sl + j) << 8); }
-                int mg = 0;
-                for (int i = 0; i < nq; ++i) {
-                    const Piece& pc = pcs[i];
-                    const int b = slot_of[i], k0 = k0_of[i];
-                    // the pieces of this piece's group in this phase (they were placed together), in the order of their index
-                    int blk[4] = {b, b, b, b};
-                    for (int i2 = 0; i2 < nq; ++i2) if (pcs[i2].group == pc.group) blk[pcs[i2].idx] = slot_of[i2];
-                    // merge tree: round 1: piece 0 += piece 1, piece 2 += piece 3; round 2: piece 0 += piece 2; the result sits with piece 0
-                    int p1 = b, p2 = b, f1 = 0, f2 = 0;
-                    if (pc.s >= 2 && pc.idx == 0) { p1 = blk[1]; f1 = 1; }
-                    if (pc.s == 4 && pc.idx == 2) { p1 = blk[3]; f1 = 1; }
-                    if (pc.s == 4 && pc.idx == 0) { p2 = blk[2]; f2 = 1; }
-                    if (pc.s >= 2) mg |= 1;
-                    if (pc.s == 4) mg |= 2;
-                    const bool fin = pc.idx == 0;
-                    for (int j = 0; j < 4; ++j) {
-                        const int m = 4 * pc.quad + j;
-                        lanes[(size_t)ph * 64 + 4 * b + j] = make_int2(8 * k0, (fin && m < M) ? m : -1);
-                        merge[(size_t)ph * 64 + 4 * b + j] = (4 * p1 + j) | ((4 * p2 + j) << 8) | (f1 << 16) | (f2 << 17);
-                        if (m >= M) continue;
-                        for (int st = 0; st < 4 * n4; ++st) {
-                            const int f = k0 + st;
-                            const float v = (f < tb.F && f >= pc.lo && f < pc.lo + pc.w) ? fb[(size_t)f * M + m] : 0.f;
-                            float4& e = b4[base + (size_t)(st / 4) * 64 + 4 * b + j];
-                            (st % 4 == 0 ? e.x : st % 4 == 1 ? e.y : st % 4 == 2 ? e.z : e.w) = v;
-                        }
-                    }
-                }
-                tb.wl_mg[ph] = mg;
-                tb.wl_total4 += n4;
-            }
-            DMEL_HIP(hipMalloc(&tb.wl_lane, lanes.size() * sizeof(int2)));
-            DMEL_HIP(hipMemcpy(tb.wl_lane, lanes.data(), lanes.size() * sizeof(int2), hipMemcpyHostToDevice));
-            DMEL_HIP(hipMalloc(&tb.wl_merge, merge.size() * sizeof(int)));
-            DMEL_HIP(hipMemcpy(tb.wl_merge, merge.data(), merge.size() * sizeof(int), hipMemcpyHostToDevice));
-            DMEL_HIP(hipMalloc(&tb.wl_b4, std::max<size_t>(b4.size(), 64) * sizeof(float4)));
-            if (!b4.empty()) DMEL_HIP(hipMemcpy(tb.wl_b4, b4.data(), b4.size() * sizeof(float4), hipMemcpyHostToDevice));
-        }
-        {   // register-resident prefix of every run of group 0, at a fixed position per (wave, run)
-            const int nbpre = dmel::forward_nbpre(N);
-            std::vector<float> pre((size_t)waves * 2 * nbpre * 64, 0.f);
-            for (int w = 0; w < waves; ++w)
-                for (int loc = 0; loc < 2; ++loc) {
-                    const int4 tr = ranges[(size_t)w * 2 + loc];
-                    const int n = std::min(tr.y, nbpre);
-                    tb.pre_groups[w * 2 + loc] = (n + 3) / 4;
-                    if (n > 0)
-                        std::copy(bfr.begin() + tr.z, bfr.begin() + tr.z + (size_t)n * 64, pre.begin() + ((size_t)(w * 2 + loc) * nbpre) * 64);
-                }
-            DMEL_HIP(hipMalloc(&tb.ent_pre, pre.size() * sizeof(float)));
-            DMEL_HIP(hipMemcpy(tb.ent_pre, pre.data(), pre.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        const size_t nb = std::max<size_t>(bfr.size(), 64);
-        DMEL_HIP(hipMalloc(&tb.ent_b, nb * sizeof(float)));
-        if (!bfr.empty())
-            DMEL_HIP(hipMemcpy(tb.ent_b, bfr.data(), bfr.size() * sizeof(float), hipMemcpyHostToDevice));
-        DMEL_HIP(hipMalloc(&tb.tile_ranges, ranges.size() * sizeof(int4)));
-        DMEL_HIP(hipMemcpy(tb.tile_ranges, ranges.data(), ranges.size() * sizeof(int4), hipMemcpyHostToDevice));
-    }
-    auto ins = pl->tables.emplace(N, tb);
+    const bool dense_dev = pl->dense_dev.count(N) != 0, custom = cit != pl->custom_fb.end();
+    if (dense_dev) std::fill(fb.begin(), fb.end(), 1.0f);        // structure only: every block present; dmel_plan_set_filterbank_dev fills the values
+    else if (custom) fb = cit->second;
+    else if ((st = dmel_mel_fbanks_host(F, pl->cfg.f_min, pl->f_max, M, pl->cfg.sample_rate, fb.data())) != DMEL_OK) return st;
+    DMEL_UP(fb, &tb.fb_dense);
+    dmel::HostTables h;
+    if (!dmel::build_host_tables(fb, N, M, custom || dense_dev, !dense_dev && std::getenv("DMEL_WLC_NOSPLIT") == nullptr, &h))
+        return fail(DMEL_ERR_UNSUPPORTED, "n_fft has no FFT plan");
+    tb.long_rows = h.rows.long_rows;
+    tb.KS = h.bs.KS; tb.NT = h.bs.NT; tb.groups = h.bs.groups; tb.n_entries = h.bs.n_entries; tb.n_dense = h.bs.n_dense;
+    tb.xch_groups = h.bs.xch_groups; tb.ent_b_floats = (int)h.bs.ent_b.size();
+    std::copy(h.pre.pre_groups, h.pre.pre_groups + 16, tb.pre_groups);
+    tb.wl_phases = h.wl.phases; tb.wl_total4 = h.wl.total4;
+    std::copy(h.wl.len4, h.wl.len4 + dmel::kWlMaxPhases, tb.wl_len4);
+    std::copy(h.wl.mg, h.wl.mg + dmel::kWlMaxPhases, tb.wl_mg);
+    // (in the order the tables have always been allocated; upload leaves the pointer of an empty table null, the three with a minimum length exist whenever their neighbours do)
+    DMEL_UP(h.tw_long, &tb.tw_long, 1);
+    DMEL_UP(h.rows.rowband, &tb.rowband);
+    DMEL_UP(h.rows.rowpk, &tb.rowpk);
+    DMEL_UP(h.tbank.fbT, &tb.fbT);
+    DMEL_UP(h.tbank.band, &tb.band);
+    DMEL_UP(h.tw.tw1, &tb.tw1);
+    DMEL_UP(h.tw.tw2, &tb.tw2);
+    if (h.twp_same) { tb.tw1p = tb.tw1; tb.tw2p = tb.tw2; }
+    DMEL_UP(h.twp.tw1, &tb.tw1p);
+    DMEL_UP(h.twp.tw2, &tb.tw2p);
+    DMEL_UP(h.h.ent_h, &tb.ent_h);
+    DMEL_UP(h.h.fb_nyq, &tb.fb_nyq);
+    DMEL_UP(h.wl.lane, &tb.wl_lane);
+    DMEL_UP(h.wl.merge, &tb.wl_merge);
+    DMEL_UP(h.wl.b4, &tb.wl_b4, h.wl.lane.empty() ? 0 : 64);
+    DMEL_UP(h.pre.ent_pre, &tb.ent_pre);
+    DMEL_UP(h.bs.ent_b, &tb.ent_b, h.bs.tile_ranges.empty() ? 0 : 64);
+    DMEL_UP(h.bs.tile_ranges, &tb.tile_ranges);
+#undef DMEL_UP
+    auto ins = pl->tables.emplace(N, std::move(tb));
     guard.keep = true;
     *out = &ins.first->second;
     return DMEL_OK;
@@ -710,77 +341,37 @@ dmel_status grow_floats(float** buf, size_t* have, size_t need, hipStream_t s, c
     return DMEL_OK;
 }
 
-// in-place radix-2 FFT in double precision (host: the transform of Bluestein's chirp filter, once per DFT length)
-void host_fft(std::vector<double>& re, std::vector<double>& im)
+// a plan-owned twiddle table of the big path, exp(-2 pi i k / n) for k < n / 2, made on first use
+dmel_status big_twiddles(dmel_plan* pl, std::map<int, float2*>* tabs, int n, const float2** out)
 {
-    const size_t n = re.size();
-    for (size_t i = 1, j = 0; i < n; ++i) {
-        size_t bit = n >> 1;
-        for (; j & bit; bit >>= 1) j ^= bit;
-        j ^= bit;
-        if (i < j) { std::swap(re[i], re[j]); std::swap(im[i], im[j]); }
+    auto it = tabs->find(n);
+    if (it == tabs->end()) {
+        float2* d = nullptr;
+        const dmel_status st = upload(&pl->big_dev, dmel::build_long_twiddles(n), &d, 1);
+        if (st != DMEL_OK) return st;
+        it = tabs->emplace(n, d).first;
     }
-    for (size_t len = 2; len <= n; len <<= 1) {
-        const double ang = -2.0 * M_PI / (double)len;
-        for (size_t s0 = 0; s0 < n; s0 += len)
-            for (size_t k = 0; k < len / 2; ++k) {
-                const double wr = std::cos(ang * (double)k), wi = std::sin(ang * (double)k);
-                const size_t a = s0 + k, b = a + len / 2;
-                const double tr = re[b] * wr - im[b] * wi, ti = re[b] * wi + im[b] * wr;
-                re[b] = re[a] - tr; im[b] = im[a] - ti;
-                re[a] += tr; im[a] += ti;
-            }
-    }
+    *out = it->second;
+    return DMEL_OK;
 }
 
 // tables of the big path for DFT length N: twiddles of the power-of-two FFT behind it and, when N is not a power of two,
 // Bluestein's chirp c[n] = exp(-i pi n^2 / N) and the transform of its filter
 dmel_status big_tables_for(dmel_plan* pl, int N, dmel_plan::BigTab* out, const float2** tw)
 {
-    const bool pow2 = (N & (N - 1)) == 0;
-    int M = N;
-    if (!pow2) { M = 1; while (M < 2 * N - 1) M <<= 1; }
+    const int M = dmel::big_fft_length(N);
     if (M > dmel::kMaxBigFft)
         return fail(DMEL_ERR_UNSUPPORTED, "transform length " + std::to_string(N) + " needs an FFT of " + std::to_string(M) +
                     " points; the HIP path stops at " + std::to_string(dmel::kMaxBigFft));
-    auto tit = pl->big_tw.find(M);
-    if (tit == pl->big_tw.end()) {
-        std::vector<float2> t((size_t)std::max(1, M / 2));
-        for (int k = 0; k < M / 2; ++k) {
-            const double th = -2.0 * M_PI * (double)k / (double)M;
-            t[k] = make_float2((float)std::cos(th), (float)std::sin(th));
-        }
-        float2* d = nullptr;
-        DMEL_HIP(hipMalloc(&d, t.size() * sizeof(float2)));
-        DMEL_HIP(hipMemcpy(d, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
-        tit = pl->big_tw.emplace(M, d).first;
-    }
-    *tw = tit->second;
+    dmel_status st = big_twiddles(pl, &pl->big_tw, M, tw);
+    if (st != DMEL_OK) return st;
     auto bit = pl->big_tabs.find(N);
     if (bit == pl->big_tabs.end()) {
         dmel_plan::BigTab bt;
         bt.M = M; bt.logM = 0; while ((1 << bt.logM) < M) ++bt.logM;
-        if (!pow2) {
-            std::vector<float2> chirp(N);
-            std::vector<double> hr(M, 0.0), hi(M, 0.0);
-            for (int k = 0; k < N; ++k) {
-                const long long q = ((long long)k * k) % (2LL * N);        // k^2 mod 2N: the phase argument stays small
-                const double a = M_PI * (double)q / (double)N;
-                chirp[k] = make_float2((float)std::cos(a), (float)(-std::sin(a)));
-                hr[k] = std::cos(a); hi[k] = std::sin(a);
-                if (k) { hr[M - k] = std::cos(a); hi[M - k] = std::sin(a); }
-            }
-            host_fft(hr, hi);
-            std::vector<float2> hbr(M);
-            for (int j = 0; j < M; ++j) {
-                unsigned r = 0;
-                for (int bbit = 0; bbit < bt.logM; ++bbit) r |= ((unsigned)(j >> bbit) & 1u) << (bt.logM - 1 - bbit);
-                hbr[r] = make_float2((float)(hr[j] / M), (float)(hi[j] / M));     // position r of a DIF output holds bin brev(r) = j
-            }
-            DMEL_HIP(hipMalloc(&bt.chirp, chirp.size() * sizeof(float2)));
-            DMEL_HIP(hipMemcpy(bt.chirp, chirp.data(), chirp.size() * sizeof(float2), hipMemcpyHostToDevice));
-            DMEL_HIP(hipMalloc(&bt.hbr, hbr.size() * sizeof(float2)));
-            DMEL_HIP(hipMemcpy(bt.hbr, hbr.data(), hbr.size() * sizeof(float2), hipMemcpyHostToDevice));
+        if (M != N) {
+            if ((st = upload(&pl->big_dev, dmel::build_chirp(N), &bt.chirp)) != DMEL_OK) return st;
+            if ((st = upload(&pl->big_dev, dmel::build_chirp_filter(N, M), &bt.hbr)) != DMEL_OK) return st;
         }
         bit = pl->big_tabs.emplace(N, bt).first;
     }
@@ -892,19 +483,7 @@ dmel_status forward_big(dmel_plan* pl, NfftTables* tb, const dmel::LamArgs& lam,
         if (H & (H - 1)) { Mh = 1; while (Mh < 2 * H - 1) Mh <<= 1; }
         if (H >= 2 && dmel::big_can_split(Mh, pl->cfg.n_mels)) {
             if ((st = big_tables_for(pl, H, &bt, &tw)) != DMEL_OK) return st;
-            auto wit = pl->big_wodd.find(N);
-            if (wit == pl->big_wodd.end()) {
-                std::vector<float2> w((size_t)H);
-                for (int n = 0; n < H; ++n) {
-                    const double th = -2.0 * M_PI * (double)n / (double)N;
-                    w[n] = make_float2((float)std::cos(th), (float)std::sin(th));
-                }
-                float2* d = nullptr;
-                DMEL_HIP(hipMalloc(&d, w.size() * sizeof(float2)));
-                DMEL_HIP(hipMemcpy(d, w.data(), w.size() * sizeof(float2), hipMemcpyHostToDevice));
-                wit = pl->big_wodd.emplace(N, d).first;
-            }
-            wodd = wit->second;
+            if ((st = big_twiddles(pl, &pl->big_wodd, N, &wodd)) != DMEL_OK) return st;
             split = true;
         }
     }
@@ -1341,8 +920,8 @@ dmel_status dmel_contraction_partition_host(const int32_t* units, int32_t n_tile
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_contraction_partition_host: bad arguments");
     int u[8] = {0, 0, 0, 0, 0, 0, 0, 0}, o[8];
     for (int t = 0; t < n_tiles; ++t) { if (units[t] < 0) return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_contraction_partition_host: negative extent"); u[t] = units[t]; }
-    std::vector<Piece> pieces;
-    deal_ksteps(u, n_tiles, waves, o, &pieces);
+    std::vector<dmel::Piece> pieces;
+    dmel::deal_ksteps(u, n_tiles, waves, o, &pieces);
     for (int w = 0; w < 8; ++w) own[w] = o[w];
     *n_pieces = (int32_t)pieces.size();
     for (size_t i = 0; i < pieces.size() && i < 8; ++i) {
@@ -1356,23 +935,7 @@ dmel_status dmel_mel_fbanks_host(int32_t n_freqs, double f_min, double f_max, in
 {
     if (n_freqs < 1 || n_mels < 1 || sample_rate < 2 || !fb)
         return fail(DMEL_ERR_INVALID_ARGUMENT, "dmel_mel_fbanks_host: bad arguments");
-    std::vector<float> all_freqs, m_pts, f_pts(n_mels + 2);
-    linspace_f32(0.0f, (float)(sample_rate / 2), n_freqs, all_freqs);
-    const double m_min = 2595.0 * std::log10(1.0 + f_min / 700.0);
-    const double m_max = 2595.0 * std::log10(1.0 + f_max / 700.0);
-    linspace_f32((float)m_min, (float)m_max, n_mels + 2, m_pts);
-    // 10 ** (m / 2595) as torch evaluates it: the CORRECTLY ROUNDED fp32 power (measured against torch 2.10: all 130 points of the 128-band bank;
-    // glibc's powf is 1 ulp off at 19 of them, which moved filterbank entries by up to 1.5e-5 -- tests/golden/g8_fbanks.npz)
-    for (int i = 0; i < n_mels + 2; ++i) {
-        const float e = m_pts[i] / 2595.0f;
-        f_pts[i] = 700.0f * ((float)std::pow(10.0, (double)e) - 1.0f);
-    }
-    for (int f = 0; f < n_freqs; ++f)
-        for (int m = 0; m < n_mels; ++m) {
-            const float down = (-1.0f * (f_pts[m] - all_freqs[f])) / (f_pts[m + 1] - f_pts[m]);
-            const float up = (f_pts[m + 2] - all_freqs[f]) / (f_pts[m + 2] - f_pts[m + 1]);
-            fb[(size_t)f * n_mels + m] = std::max(0.0f, std::min(down, up));
-        }
+    dmel::mel_fbanks_htk(n_freqs, f_min, f_max, n_mels, sample_rate, fb);
     return DMEL_OK;
 }
 
@@ -1471,9 +1034,7 @@ dmel_status dmel_plan_release(dmel_plan* plan)
     for (auto& kv : plan->tables) kv.second.release();
     for (hipEvent_t e : plan->ev_pool) (void)hipEventDestroy(e);
     (void)hipFree(plan->own_scratch); (void)hipFree(plan->fbw); (void)hipFree(plan->xmw);
-    for (auto& kv : plan->big_tabs) { (void)hipFree(kv.second.chirp); (void)hipFree(kv.second.hbr); }
-    for (auto& kv : plan->big_tw) (void)hipFree(kv.second);
-    for (auto& kv : plan->big_wodd) (void)hipFree(kv.second);
+    plan->big_dev.release();
     (void)hipFree(plan->big_win); (void)hipFree(plan->big_z);
     (void)hipFree(plan->exec_counter);
     if (plan->host_words) (void)hipHostFree(plan->host_words);

@@ -424,7 +424,7 @@ __global__ void __launch_bounds__(256) dmel_repack_kernel(RepackParams p)
         int blk = (int)blockIdx.x - p.runs * kRepackRunSplit;
         const long long n = (long long)p.F * p.M;
         if (blk < p.blocks_h) {
-            // the split-bf16 fragments of kTrainH (build_tables is the host's version of this loop): one 16-byte entry per (block, lane)
+            // the split-bf16 fragments of kTrainH (build_split_bf16, dmel_tables.cpp, is the host's version of this loop): one 16-byte entry per (block, lane)
             const int NT = (p.M + 15) / 16;
             const long long ne = (long long)NT * p.ks32 * 64;
             const long long q = (long long)blk * 256 + tid;
@@ -450,7 +450,7 @@ __global__ void __launch_bounds__(256) dmel_repack_kernel(RepackParams p)
         }
         blk -= p.blocks_h;
         if (blk < p.blocks_w) {
-            // the B operands of kTrainW (build_tables is the host's version): one 16-byte entry = four steps of one lane
+            // the B operands of kTrainW (wl_fill, dmel_tables.cpp, is the host's version): one 16-byte entry = four steps of one lane
             const long long q = (long long)blk * 256 + tid;
             if (q < (long long)p.wl_total4 * 64) {
                 const int l = (int)(q & 63);

@@ -200,9 +200,7 @@ DMEL_FWD_PARTS_OF(FwdVariant)
 hipError_t launch_forward(int n_fft, int mode, int tpw, const FwdParams& p, int grid, hipStream_t s) { return fwd_launch<FwdVariant>(n_fft, mode, tpw, p, grid, s); }
 hipError_t forward_prepare_attributes() { return fwd_set_attr<FwdVariant>(); }
 
-bool forward_has_hsplit(int n_fft) { return n_fft >= kHsplitMinNfft && n_fft <= kHsplitMaxNfft && (n_fft & (n_fft - 1)) == 0; }
-bool forward_has_wlc(int n_fft) { return wlc_size(n_fft); }
-bool forward_wlc_one_frame(int n_fft) { return wlc_size(n_fft) && n_fft >= 2048; }      // (G = 64: the frame fills the wave)
+// (forward_has_hsplit, _has_wlc, _wlc_one_frame, _plan_rc, _waves, _nbpre: dmel_tables.cpp, where a program without kernels links them)
 bool forward_has_wlc_wide(int n_fft) { return wlc_wide_size(n_fft); }
 bool forward_window_in_lds(int n_fft) { return n_fft >= kMinFastNfft && n_fft <= kWinLdsMaxNfft; }
 
@@ -210,12 +208,6 @@ bool forward_window_in_lds(int n_fft) { return n_fft >= kMinFastNfft && n_fft <=
 template <class F> static bool with_geom(int n_fft, bool pair, F&& f)
 {
     return with_nfft(n_fft, [&](auto nn) { constexpr int N = decltype(nn)::value; f(pair ? geom<N, true>() : geom<N, false>()); });
-}
-
-// (R, C) of the plan for n_fft: the host builds the twiddle tables from these
-bool forward_plan_rc(int n_fft, bool pair, int* R, int* C)
-{
-    return with_geom(n_fft, pair, [&](const FftGeom& g) { *R = g.R; *C = g.C; });
 }
 
 int forward_lds_bytes(int n_fft, int mode)
@@ -277,21 +269,6 @@ int forward_tiles_per_wg(int n_fft, int mode, int batch, int tiles_per_clip)
     const long long wg1 = (long long)batch * tiles_per_clip, wg2 = (long long)batch * ((tiles_per_clip + 1) / 2);
     const long long r1 = (wg1 + resident - 1) / resident, r2 = (wg2 + resident - 1) / resident;
     return 19 * r2 < 10 * r1 ? 2 : 1;
-}
-
-// the layout of tile_ranges / ent_pre depends on these two; they are the same for both plans of a size
-int forward_waves(int n_fft)
-{
-    int v = -1;
-    with_geom(n_fft, false, [&](const FftGeom& g) { v = g.WAVES; });
-    return v;
-}
-
-int forward_nbpre(int n_fft)
-{
-    int v = -1;
-    with_geom(n_fft, false, [&](const FftGeom& g) { v = g.NBPRE; });
-    return v;
 }
 
 #endif   // DMEL_FWD_PART == 0

@@ -1279,7 +1279,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                 if (DMEL_WL_NEXT && ph + 1 < p.wl_phases) wl_ring_init(p.wl_len4[ph + 1], off4);
                 floatx4 tot = acc0 + acc1;
                 if constexpr (FPW == 1) {
-                    // quads split over several blocks of this phase (the host's schedule, dmel_api.cpp): the pieces' partial sums -- rows P
+                    // quads split over several blocks of this phase (the host's schedule, dmel_tables.cpp): the pieces' partial sums -- rows P
                     // and D of this wave's one frame -- are added across lanes, the piece that carries the mel band receives last
                     const int mg = p.wl_mg[ph];
                     if (mg != 0) {
@@ -1684,7 +1684,7 @@ __global__ void __launch_bounds__((geom_mode<N, MODE>().THREADS), (geom_mode<N, 
                     tot[decltype(l)::value][decltype(m)::value] = acc[decltype(l)::value][decltype(m)::value][0] + acc[decltype(l)::value][decltype(m)::value][1]; }); });
                 if (WAVES == 8 || ((p.xch_groups >> (grp & 31)) & 1u)) {
                     // run 1 of a wave is a piece of some OTHER wave's tile (the host deals the k-steps of the wide tiles over the
-                    // waves with narrow or no tiles of their own: build_tables): every wave leaves its run-1 sums in its own slot
+                    // waves with narrow or no tiles of their own: build_b_stream, dmel_tables.cpp): every wave leaves its run-1 sums in its own slot
                     // and an owner adds the slots of its helpers in ascending order (fixed order: deterministic)
                     // (one 16-row tile at a time through the same 8 KB: two tiles at once would put the 16-frame workgroup of
                     // n_fft 1024 past half of the CU's LDS)

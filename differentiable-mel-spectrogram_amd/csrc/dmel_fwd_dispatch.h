@@ -8,30 +8,12 @@
 //   template <int N, int MODE, int TPW> kernels[]      the kernel (or kernels) of one instantiation
 //   static int pick(const Params&)                     which of them a launch takes
 //
-// and ends with DMEL_FWD_PARTS_OF(V).  Everything else -- the map from n_fft to N, the split into parts, the entry points -- is here.
+// and ends with DMEL_FWD_PARTS_OF(V).  Everything else -- the split into parts, the entry points -- is here; the map from n_fft to N is with_nfft (dmel_kernels.h).
 #pragma once
 #include "dmel_kernels.h"
 #include "dmel_wavefft.h"
 
 namespace dmel {
-
-// the map from a run-time n_fft of the fused kernel to the compile-time N: f(IC<N>{})
-template <class F> static bool with_nfft(int n_fft, F&& f)
-{
-    switch (n_fft) {
-        case 32: f(IC<32>{}); return true;
-        case 64: f(IC<64>{}); return true;
-        case 128: f(IC<128>{}); return true;
-        case 256: f(IC<256>{}); return true;
-        case 512: f(IC<512>{}); return true;
-        case 1024: f(IC<1024>{}); return true;
-        case 2048: f(IC<2048>{}); return true;
-        case 4096: f(IC<4096>{}); return true;
-        case 8192: f(IC<8192>{}); return true;
-        case 16384: f(IC<16384>{}); return true;
-    }
-    return false;
-}
 
 // -DDMEL_FWD_SPLIT -DDMEL_FWD_PART=<k>, k = 0..3: build.py compiles each of these files four times for libdmel_hip.so so that the
 // instantiations of the large transforms -- minutes of compile time each -- build in parallel: part 0 holds everything that is not a template

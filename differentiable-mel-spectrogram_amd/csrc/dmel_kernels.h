@@ -326,7 +326,7 @@ constexpr int slot_stride_f2(int N, int R, int C, int pairing = 0, int split = 0
     // kTrainW reads its A operands with ds_read_b32 too, but lane 4 b + i of a 32-lane group takes row i = (frame, P | D) of
     // block b's current bin: dwords {2 k, 2 k + 1} of the two slots of a wave.  With the slots 64 bytes apart modulo 128 a block
     // covers the bank pairs {k, k + 8} (mod 16): conflict-free as soon as the 8 blocks of a group sit at bins that differ
-    // modulo 8, which the host's schedule arranges (build_tables).  (12 dwords apart, as above: 5 500 cycles per wave for 88 MFMAs.)
+    // modulo 8, which the host's schedule arranges (wl_place_phase, dmel_tables.cpp).  (12 dwords apart, as above: 5 500 cycles per wave for 88 MFMAs.)
     if (wl) return ((need + 127) / 128 * 128 + 64) / 8;
     return ((need + 127) / 128 * 128 + 48) / 8;
 }
@@ -381,6 +381,25 @@ template <int N, int MODE> constexpr FftGeom geom_mode() { return geom<N, mode_p
 // second pass over the clip it saves is not what a one-round launch waits for --, config 4's batch on one GPU 131 us against 110: a
 // CU's next workgroup starts only when all 16 waves of the previous one have finished.  (wlc_wide_size(1024) = true builds it; DMEL_WLC=2.)
 constexpr bool wlc_wide_size(int n_fft) { return false; }
+
+// the map from a run-time n_fft of the fused kernel to the compile-time N: f(IC<N>{})
+template <int I> struct IC { static constexpr int value = I; };
+template <class F> static bool with_nfft(int n_fft, F&& f)
+{
+    switch (n_fft) {
+        case 32: f(IC<32>{}); return true;
+        case 64: f(IC<64>{}); return true;
+        case 128: f(IC<128>{}); return true;
+        case 256: f(IC<256>{}); return true;
+        case 512: f(IC<512>{}); return true;
+        case 1024: f(IC<1024>{}); return true;
+        case 2048: f(IC<2048>{}); return true;
+        case 4096: f(IC<4096>{}); return true;
+        case 8192: f(IC<8192>{}); return true;
+        case 16384: f(IC<16384>{}); return true;
+    }
+    return false;
+}
 
 // One 4(k) x 16(mel) block of the filterbank, pre-arranged as the B operand of
 // v_mfma_f32_16x16x4_f32: lane l holds fb[4*ks + (l >> 4)][16*tile + (l & 15)].

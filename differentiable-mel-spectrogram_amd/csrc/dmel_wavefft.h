@@ -8,8 +8,7 @@ namespace dmel {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-// ---- compile-time helpers -------------------------------------------------------------------
-template <int I> struct IC { static constexpr int value = I; };
+// ---- compile-time helpers (IC<I>: dmel_kernels.h) ---------------------------------------------
 template <int B, int E, class F> __device__ __forceinline__ void static_for(F&& f)
 {
     if constexpr (B < E) { f(IC<B>{}); static_for<B + 1, E>(f); }
@@ -219,7 +218,7 @@ __device__ __forceinline__ void wave_sync()
 // (tools/wavefft_sim.py is the index model; the plain layout of the fused forward: FftPlan::PAIRING = 0, SPLIT = 0).
 //   in : lane lg holds points n = lg + G a in z[a]
 //   sl : the frame's LDS slot, R * ex_stride(G, C) complex entries, for the one transposition
-//   tw1: (R, G) w_N^(lg q), tw2: (R, C) w_G^(r p1)      (the plan's tables, dmel_api.cpp)
+//   tw1: (R, G) w_N^(lg q), tw2: (R, C) w_G^(r p1)      (the plan's tables, dmel_tables.cpp)
 //   out: lane (qp, r) = (lg / C, lg % C) produces Z[qp + R p1 + R^2 p2] for p1 = 0 .. R - 1
 // The caller fences before reusing `sl` (store may write to it: every read of the transposition precedes the first store).
 template <int R, int C, int G, class Store>
